@@ -36,7 +36,15 @@ Implementations (``--impl``):
 wall-clock over the steady epochs INCLUDING the full validation pass and the
 checkpoint write of every epoch (reference examples/ray_ddp_example.py:61-76).
 
+A plain run (``--gpus 1 --steps K --warmup W``) does only what the headline
+figure needs: set up, warm up, time the K steps, print the result line.
+``--full`` adds every other measurement of the default configuration (today:
+the stock step timed in the same job, ``--compare-stock``).  ``--dump-outputs
+DIR`` writes the state the last timed step left (``DIR/<name>.npy``); inputs
+and initial weights are seeded, so two builds can be compared array for array.
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--via engine|trainer]
+                       [--full] [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -136,7 +144,18 @@ def parse(argv=None):
                          "owner Adam / all-gather) on this node's links during warm-up and keeps the faster")
     ap.add_argument("--comm", choices=["auto", "xgmi", "rccl", "torch"], default="auto",
                     help="N>1 gradient allreduce: native xGMI (auto/xgmi), native RCCL, or c10d")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (training "
+                         "state and loss, as a caller receives them) to DIR/<name>.npy, float32 / float64, at most "
+                         "64 MB in all (a fixed seeded sample of a larger array)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: a plain run only sets up, warms up, times the "
+                         "steps and prints the result line; --full also times the stock step in the same job, as "
+                         "--compare-stock (no effect with --model resnet50, --impl torch*, --via trainer or "
+                         "--device cpu, which have nothing beyond their headline)")
     args = ap.parse_args(argv)
+    if args.full:
+        args.compare_stock = True
     rn = args.model == "resnet50"
     if args.steps is None:
         args.steps = 20 if rn else 2000
@@ -206,6 +225,36 @@ def sync(dev):
 def log(rank, msg):
     if rank == 0:
         print(f"[bench] {msg}", file=sys.stderr, flush=True)
+
+
+DUMP_LIMIT = 64_000_000  # bytes on disk (64 MB): every file of one --dump-outputs together
+NPY_HEADER = 256  # allowance per file for the .npy header (128 bytes for these arrays)
+
+
+def dump_outputs(path, arrays) -> None:
+    """``--dump-outputs``: write ``{name: tensor}`` as ``path/<name>.npy`` (float32;
+    float64 stays float64).  Whole arrays while the files fit ``DUMP_LIMIT``
+    together; otherwise each array above its equal share is cut to a sample of
+    distinct elements: the sorted head of a permutation seeded per array (seed 0),
+    so an array's sample depends on its own size and share only, the same in
+    every run."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    flat = {k: v.detach() if v.dtype == torch.float64 else v.detach().float() for k, v in arrays.items()}
+    budget = DUMP_LIMIT - NPY_HEADER * len(flat)
+    total = sum(t.numel() * t.element_size() for t in flat.values())
+    share = budget // max(1, len(flat))
+    for name, t in flat.items():
+        if total > budget and t.numel() * t.element_size() > share:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randperm(t.numel(), generator=g)[: share // t.element_size()].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+
+def _flat_params(model) -> torch.Tensor:
+    return torch.cat([p.detach().float().reshape(-1) for p in model.parameters()])
 
 
 # ----------------------------------------------------------- native engine
@@ -286,7 +335,14 @@ def make_native(args, world, rank, dev, x, y, force_split=False):
         info["dp_proto"] = eng.dp_proto
         if tuned is not None:
             info["dp_proto_tuning_us_per_step"] = tuned
-    return eng.run, (lambda: float(eng.recent_stats(20)[:, 0].mean())), replica_checksum, info
+
+    def outputs():
+        # the training state the last step left, and its (loss, correct, count, step) row
+        eng.sync_optimizer_state()  # owner protocol: Adam moments live on their owners (collective)
+        return {"params": eng.params, "exp_avg": eng.exp_avg, "exp_avg_sq": eng.exp_avg_sq,
+                "last_step_stats": eng.recent_stats(1).reshape(-1)}
+
+    return eng.run, (lambda: float(eng.recent_stats(20)[:, 0].mean())), replica_checksum, info, outputs
 
 
 def tune_dp_proto(eng, world, rank, dev, gsteps, candidates=("packed", "owner"), windows=8):
@@ -418,7 +474,11 @@ def make_torch(args, world, rank, dev, x, y):
             opt.step()
             state["loss"] = loss.detach()
 
-    return run, (lambda: float(state["loss"].item())), None, {"route": "torch-ddp" if world > 1 else "single"}
+    def outputs():
+        return {"params": _flat_params(model), "loss": state["loss"].reshape(1)}
+
+    return (run, (lambda: float(state["loss"].item())), None, {"route": "torch-ddp" if world > 1 else "single"},
+            outputs)
 
 
 def make_torch_graph(args, world, rank, dev, x, y):
@@ -470,7 +530,10 @@ def make_torch_graph(args, world, rank, dev, x, y):
         for _ in range(n % G):
             step()
 
-    return run, (lambda: float(loss_buf.item())), None, {"route": "single", "hip_graph_steps": G}
+    def outputs():
+        return {"params": _flat_params(model), "loss": loss_buf.reshape(1)}
+
+    return run, (lambda: float(loss_buf.item())), None, {"route": "single", "hip_graph_steps": G}, outputs
 
 
 # ----------------------------------------------------------------- ResNet
@@ -621,7 +684,10 @@ def make_resnet(args, world, rank, dev, x, y, bucket_mb=None):
 
             info = dict(info, hip_graph=True)
 
-    return run, (lambda: float(state["loss"].item())), checksum, info
+    def outputs():
+        return {"params": _flat_params(model), "loss": state["loss"].reshape(1)}
+
+    return run, (lambda: float(state["loss"].item())), checksum, info, outputs
 
 
 # ------------------------------------------------------------ measurement
@@ -687,19 +753,23 @@ def run_rank(args):
     sweep = None
     if rn and args.bucket_sweep:
         sweep = [float(v) for v in args.bucket_sweep.split(",") if v]
-    run, last_loss, checksum, info = maker(args, world, rank, dev, x, y)
+    run, last_loss, checksum, info, outputs = maker(args, world, rank, dev, x, y)
     if world > 1 and args.impl == "native" and not rn:
         # self-check of the xGMI data path before anything is timed: the capture ran
         # one real step; a few more, then the error word and replica equality
         run(min(args.warmup, 8))
         sync(dev)
         if not (comm_healthy(world) and replicas_agree(world, checksum)):
-            run, last_loss, checksum, info = degrade_to_split(args, world, rank, dev, x, y)
+            run, last_loss, checksum, info, outputs = degrade_to_split(args, world, rank, dev, x, y)
     run(args.warmup)
     log(rank, f"world={world} route={info.get('route')} device={dev}")
     per_rank = []
     elapsed = timed(run, args.steps, world, dev, per_rank)
     diag = dp_diagnostics(world, per_rank, args.steps)
+    if args.dump_outputs:
+        arrays = outputs()  # every rank: the owner protocol consolidates its Adam state collectively
+        if rank == 0:
+            dump_outputs(args.dump_outputs, arrays)
     curve = None
     if sweep:
         curve = {}
@@ -938,6 +1008,9 @@ def run_trainer(args):
     env = rank_env()
     out_path = tempfile.mktemp(prefix="rla-bench-", suffix=".json")
     clock = _EpochClock(out_path, trace=os.environ.get("RLA_BENCH_TRACE") == "1")
+    # the same initial weights and batch order in every run, as the engine path has them:
+    # seeds this process and, through PL_GLOBAL_SEED, every worker the accelerator starts
+    pl.seed_everything(int(os.environ.get("PL_GLOBAL_SEED", "0")))
     if rn:
         # BASELINE config 5 through the framework: LightningResNet50 on the resident
         # synthetic ImageNet set (`--steps` batches per rank and epoch), the whole step
@@ -997,6 +1070,9 @@ def run_trainer(args):
             ray.shutdown()
     if env is not None and env[1] != 0:
         return None
+    if args.dump_outputs:
+        # what Trainer.fit hands back: the fitted weights (loaded into the caller's model)
+        dump_outputs(args.dump_outputs, {k: v for k, v in model.state_dict().items() if v.is_floating_point()})
     with open(out_path) as f:
         rows = json.load(f)
     os.unlink(out_path)
@@ -1139,6 +1215,10 @@ def launch_spawn(args, argv) -> int:
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parse(argv)
+    if args.dump_outputs:
+        # ranks started elsewhere (runtime actors) parse argv again: the last value wins
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
+        argv += ["--dump-outputs", args.dump_outputs]
     if args.via == "trainer":
         res = run_trainer(args)
         if res is not None:

@@ -66,6 +66,91 @@ def test_bench_single_rank_cpu():
     assert out["n_gpus"] == 1 and out["vs_baseline"] is None and out["dtype"] == "fp32"
 
 
+def _load_dump(path):
+    import numpy as np
+
+    return {f[:-4]: np.load(os.path.join(path, f)) for f in sorted(os.listdir(path)) if f.endswith(".npy")}
+
+
+def _dump_twice(tmp_path, *args, timeout=300):
+    """Two runs of the same command line with --dump-outputs; asserts that the two
+    dumps hold the same finite float32 arrays, bit for bit.  Returns (arrays, result line)."""
+    import numpy as np
+
+    dumps = []
+    for name in ("a", "b"):
+        out, _ = _bench(*args, "--dump-outputs", str(tmp_path / name), timeout=timeout)
+        dumps.append(_load_dump(tmp_path / name))
+    a, b = dumps
+    assert a and set(a) == set(b)
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all(), k
+        assert np.array_equal(a[k], b[k]), k
+    return a, out
+
+
+N_PARAMS = 784 * 32 + 32 + 32 * 64 + 64 + 64 * 10 + 10
+
+
+def test_bench_dump_outputs_cpu_repeatable(tmp_path):
+    """--dump-outputs: the state the last timed step left, float32, identical from run
+    to run (seeded data and weights); --steps is the number of timed steps."""
+    import numpy as np
+
+    a, out = _dump_twice(tmp_path, "--device", "cpu", "--steps", "5", "--warmup", "1", "--n-data", "512")
+    assert out["steps"] == 5 and out["ms_per_step"] > 0 and "stock" not in out
+    assert set(a) == {"params", "exp_avg", "exp_avg_sq", "last_step_stats"}
+    assert a["params"].shape == a["exp_avg"].shape == a["exp_avg_sq"].shape == (N_PARAMS,)
+    # (loss, correct, count, step) of the last of the 1 + 5 steps
+    assert a["last_step_stats"][2] == 32 and a["last_step_stats"][3] == 6
+    assert np.abs(a["exp_avg"]).max() > 0
+
+
+def test_bench_dump_outputs_stock_cpu_repeatable(tmp_path):
+    """The stock step's dump (--impl torch): flattened parameters and the last loss."""
+    a, out = _dump_twice(tmp_path, "--device", "cpu", "--impl", "torch", "--steps", "5", "--warmup", "1",
+                         "--n-data", "512")
+    assert out["config"]["impl"] == "torch" and set(a) == {"params", "loss"}
+    assert a["params"].shape == (N_PARAMS,) and a["loss"].shape == (1,)
+    assert abs(float(a["loss"][0]) - out["config"]["final_train_loss"]) < 1e-3
+
+
+def test_bench_dump_outputs_via_trainer_cpu_repeatable(tmp_path):
+    """--via trainer: the fit is seeded (initial weights in this process, the batch order
+    in the workers through PL_GLOBAL_SEED), so the fitted weights it dumps repeat."""
+    a, out = _dump_twice(tmp_path, "--device", "cpu", "--via", "trainer", "--trainer-epochs", "1", timeout=600)
+    assert out["config"]["via"] == "trainer"
+    assert {k: v.shape for k, v in a.items()} == {
+        "layer_1.weight": (32, 784), "layer_1.bias": (32,), "layer_2.weight": (64, 32), "layer_2.bias": (64,),
+        "layer_3.weight": (10, 64), "layer_3.bias": (10,)}
+
+
+def test_dump_outputs_samples_large_arrays(tmp_path):
+    """More than 64 MB: arrays above their share are cut to a sample of distinct elements
+    that depends on nothing but the array's size and share (the same in every run, whatever
+    else is dumped before it); small ones stay whole, float64 stays float64; the files
+    together, headers included, stay within 64e6 bytes."""
+    import importlib
+
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    assert bench.DUMP_LIMIT == 64_000_000
+    big = torch.arange(20 << 20, dtype=torch.float32)  # 80 MiB; exact integers below 2^24
+    arrays = {"big": big, "small": torch.ones(3, dtype=torch.bfloat16), "f64": torch.ones(2, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), dict(reversed(list(arrays.items()))))
+    a, b = _load_dump(tmp_path / "a"), _load_dump(tmp_path / "b")
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64_000_000
+    assert a["small"].dtype == np.float32 and a["small"].shape == (3,) and a["f64"].dtype == np.float64
+    assert a["big"].dtype == np.float32 and 0 < a["big"].size < big.numel()
+    assert np.array_equal(a["big"], b["big"]) and (np.diff(a["big"]) >= 0).all()
+    exact = a["big"][a["big"] < 2 ** 24]
+    assert exact.size > a["big"].size // 2 and (np.diff(exact) > 0).all()  # no element twice
+
+
 def test_bench_refuses_non_finite_training():
     """a run whose training state goes non-finite (an injected NaN
     learning rate) is not a result -- bench.py exits non-zero and prints no JSON line."""
@@ -98,6 +183,22 @@ def test_bench_two_ranks_share_gpu():
 def test_bench_compare_stock_one_gpu():
     out, _ = _bench("--steps", "200", "--warmup", "20", "--compare-stock")
     assert out["stock"]["impl"] == "torch" and 0 < out["stock"]["value"] < out["value"]
+
+
+@pytest.mark.gpu
+def test_bench_full_and_dump_outputs_one_gpu(tmp_path):
+    """The native step's dump on the GPU repeats bit for bit over two runs; --steps sets the
+    number of steps the graph replays execute; --full adds the in-job stock comparison."""
+    import numpy as np
+
+    d, out = _dump_twice(tmp_path, "--steps", "40", "--warmup", "10", "--full")
+    assert out["steps"] == 40 and out["ms_per_step"] > 0 and out["dtype"] == "bf16"
+    assert out["stock"]["impl"] == "torch" and out["stock"]["value"] > 0
+    assert set(d) == {"params", "exp_avg", "exp_avg_sq", "last_step_stats"}
+    assert d["params"].shape == (N_PARAMS,) and np.abs(d["exp_avg"]).max() > 0
+    # optimizer steps executed: the capture's eager step and first replay, the warm-up, the 40 timed
+    g = out["config"]["hip_graph_steps"]
+    assert g == 20 and d["last_step_stats"][2] == 32 and d["last_step_stats"][3] == 1 + g + 10 + 40
 
 
 @pytest.mark.gpu
