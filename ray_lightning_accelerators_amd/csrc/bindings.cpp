@@ -796,6 +796,7 @@ std::vector<Tensor> conv3x3_impl(Tensor x, Tensor w, int64_t N, int64_t H, int64
   rla::Conv3x3Geom g{(int)N, (int)H, (int)W, (int)Cin, (int)Cout, 0,
                      rla::conv3x3_pick_tm((int)N, (int)H, (int)W, (int)Cout),
                      rla::conv3x3_wpb((int)N, (int)H, (int)W, (int)Cout)};
+  // vrows is a function of (N, H, W, tm, wpb) alone: a pinned plan CU count changes wpb, hence the key
   static std::map<std::tuple<int64_t, int64_t, int64_t, int, int>, int> vrows_cache;
   static std::mutex mu;
   {
@@ -900,6 +901,38 @@ bool conv3x3_supported(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cou
   return rla::conv3x3_ok(g);
 }
 
+// Read-only plan queries (tests): what the launches above would run for a shape, under the
+// current plan CU count (set_plan_cus) and the RLA_CONV3X3_TM / RLA_CONV3X3_GENERIC switches.
+// The arguments are the conv3x3 / conv3x3_stats binding's own (flip: Cin = dy's channels);
+// returns (tm, wpb, vrows, pieces_per_thread, nx, fixed)
+std::vector<int64_t> conv3x3_plan(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout, bool flip, bool stats,
+                                  bool pre) {
+  TORCH_CHECK(conv3x3_supported(N, H, W, Cin, Cout), "conv3x3_plan: unsupported shape");
+  TORCH_CHECK(!(flip && stats) && (!pre || stats), "conv3x3_plan: statistics are a forward epilogue, pre needs them");
+  rla::Conv3x3Geom g{(int)N, (int)H, (int)W, (int)Cin, (int)Cout, 0,
+                     rla::conv3x3_pick_tm((int)N, (int)H, (int)W, (int)Cout),
+                     rla::conv3x3_wpb((int)N, (int)H, (int)W, (int)Cout)};
+  g.vrows = rla::conv3x3_vrows(g);
+  TORCH_CHECK(!pre || rla::conv3x3_pre_ok(g), "conv3x3_plan: pre needs Cin <= 512");
+  const rla::Conv3x3Instance ins = rla::conv3x3_instance(g, pre);
+  return {g.tm, g.wpb, g.vrows, rla::conv3x3_pieces_per_thread(g), ins.nx, ins.fixed ? 1 : 0};
+}
+
+// (tnw, gy, gx, tiles_per_blk, variant) of conv1x1_stats (bwd: of conv1x1_bn_bwd); variant 0 / 1:
+// weights resident beside 6 / 4 x stages, 2: streamed
+std::vector<int64_t> conv1x1_plan(int64_t M, int64_t K, int64_t N, bool bwd) {
+  TORCH_CHECK(bwd ? rla::conv1x1_bn_bwd_ok(M, (int)K, (int)N) : rla::conv1x1_stats_ok(M, (int)K, (int)N),
+              "conv1x1_plan: unsupported shape");
+  const rla::Conv1x1Plan p = rla::conv1x1_stats_plan(M, (int)N, bwd);
+  return {p.tnw, p.gy, p.gx, p.tiles_per_blk, rla::conv1x1_variant((int)K, p)};
+}
+
+int64_t stem_grid(int64_t N, int64_t H, int64_t W) {
+  const rla::StemGeom g{(int)N, (int)H, (int)W, (int)((H - 1) / 2 + 1), (int)((W - 1) / 2 + 1)};
+  TORCH_CHECK(rla::stem_ok(g), "stem_grid: unsupported shape");
+  return rla::stem_grid(g);
+}
+
 Tensor dp_pack_roundtrip(Tensor x, int64_t tag) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous(), "x: contiguous fp32 on the GPU");
   Tensor y = at::empty_like(x);
@@ -973,6 +1006,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("N"), py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("OH"), py::arg("OW"), py::arg("Cout"),
         py::arg("KH"), py::arg("KW"), py::arg("sh"), py::arg("sw"), py::arg("ph"), py::arg("pw"),
         py::arg("splits") = 0, py::arg("algo") = 0);
+  m.def("set_plan_cus", [](int64_t n) { rla::set_plan_cus((int)std::min<int64_t>(std::max<int64_t>(n, 0), 1 << 20)); },
+        "pin the CU count the persistent conv kernels' work splits are planned for (process-wide; n <= 0: the "
+        "device's); the tests use it to run production per-workgroup geometry on small tensors",
+        py::arg("n"));
+  m.def("plan_cus", []() { return (int64_t)rla::plan_cus(); }, "the effective planning CU count");
+  m.def("conv3x3_plan", &conv3x3_plan, "the 3x3 kernel's (tm, wpb, vrows, pieces_per_thread, nx, fixed)", py::arg("N"),
+        py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"), py::arg("flip") = false,
+        py::arg("stats") = false, py::arg("pre") = false);
+  m.def("conv1x1_plan", &conv1x1_plan, "the 1x1 statistics kernel's (tnw, gy, gx, tiles_per_blk, variant)",
+        py::arg("M"), py::arg("K"), py::arg("N"), py::arg("bwd") = false);
+  m.def("stem_grid", &stem_grid, "workgroups (= partial rows) of the stem kernels", py::arg("N"), py::arg("H"),
+        py::arg("W"));
   m.def("conv3x3", &conv3x3, "3x3 / stride 1 / pad 1 NHWC bf16 convolution on MFMA -> [N, H, W, Cout]",
         py::arg("x"), py::arg("w"), py::arg("N"), py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"),
         py::arg("flip") = false);

@@ -394,17 +394,6 @@ __global__ __launch_bounds__(kC1Threads, 2) void conv1x1_stats_kernel(const uint
   }
 }
 
-int c1_cu_count() {
-  static int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-      v = 256;
-    return v;
-  }();
-  return n;
-}
-
 }  // namespace
 
 bool conv1x1_stats_ok(int64_t M, int K, int N) {
@@ -413,15 +402,16 @@ bool conv1x1_stats_ok(int64_t M, int K, int N) {
 
 bool conv1x1_pre_ok(int64_t M, int K, int N) { return conv1x1_stats_ok(M, K, N) && K <= kPreMaxK; }
 
-Conv1x1Plan conv1x1_stats_plan(int64_t M, int N) {
+Conv1x1Plan conv1x1_stats_plan(int64_t M, int N, bool bwd) {
   Conv1x1Plan p;
   // 32-channel wave columns only where N needs them: choosing them to keep a K = 256 /
-  // 512 weight block resident measured slower (profiles/r4_c1/c1stats_probe_v4_wide.log)
-  p.tnw = N % 128 == 0 ? 2 : 1;
+  // 512 weight block resident measured slower (profiles/r4_c1/c1stats_probe_v4_wide.log);
+  // bwd: always (the epilogue prefetch's register budget)
+  p.tnw = !bwd && N % 128 == 0 ? 2 : 1;
   p.gy = N / (64 * p.tnw);
   const int mt = (int)((M + 127) / 128);
   // ~2 resident workgroups per CU over the whole grid; gx a multiple of 8 (XCD deal)
-  int want = 2 * c1_cu_count() / p.gy;
+  int want = 2 * plan_cus() / p.gy;
   if (want < 8) want = 8;
   if (want > mt) want = mt;
   p.tiles_per_blk = (mt + want - 1) / want;
@@ -430,12 +420,17 @@ Conv1x1Plan conv1x1_stats_plan(int64_t M, int N) {
   return p;
 }
 
-void launch_conv1x1_stats(const uint16_t* x, const uint16_t* w, uint16_t* y, int64_t M, int K, int N,
-                          const Conv1x1Plan& p, float* part, hipStream_t s, const float* pre_ss, int64_t* nbt_inc) {
-  const dim3 grid(p.gx * p.gy), block(kC1Threads);
+int conv1x1_variant(int K, const Conv1x1Plan& p) {
   // resident weights where they fit beside the x ring: 6 x-only stages (4 in flight)
   // with a 16 KB weight block, 4 stages with 32 KB; else x + w stream through 4 stages
   const int64_t wbytes = (int64_t)K * 64 * p.tnw * 2;
+  return wbytes <= 16384 ? 0 : (wbytes <= 32768 ? 1 : 2);
+}
+
+void launch_conv1x1_stats(const uint16_t* x, const uint16_t* w, uint16_t* y, int64_t M, int K, int N,
+                          const Conv1x1Plan& p, float* part, hipStream_t s, const float* pre_ss, int64_t* nbt_inc) {
+  const dim3 grid(p.gx * p.gy), block(kC1Threads);
+  const int variant = conv1x1_variant(K, p);
 #define RLA_C1_LAUNCH(T, R, NS)                                                                                   \
   do {                                                                                                            \
     if (pre_ss)                                                                                                   \
@@ -446,16 +441,16 @@ void launch_conv1x1_stats(const uint16_t* x, const uint16_t* w, uint16_t* y, int
                          p.tiles_per_blk, part);                                                                  \
   } while (0)
   if (p.tnw == 2) {
-    if (wbytes <= 16384)
+    if (variant == 0)
       RLA_C1_LAUNCH(2, true, 6);
-    else if (wbytes <= 32768)
+    else if (variant == 1)
       RLA_C1_LAUNCH(2, true, 4);
     else
       RLA_C1_LAUNCH(2, false, 4);
   } else {
-    if (wbytes <= 16384)
+    if (variant == 0)
       RLA_C1_LAUNCH(1, true, 6);
-    else if (wbytes <= 32768)
+    else if (variant == 1)
       RLA_C1_LAUNCH(1, true, 4);
     else
       RLA_C1_LAUNCH(1, false, 4);
@@ -470,18 +465,7 @@ bool conv1x1_bn_bwd_ok(int64_t M, int K, int N) {
 void launch_conv1x1_bn_bwd(const uint16_t* dy1, const uint16_t* wt, uint16_t* d, int64_t M, int K, int N,
                            const uint16_t* dy2, const uint16_t* yb, const uint16_t* xb, float* part, int* rows,
                            hipStream_t s) {
-  Conv1x1Plan p = conv1x1_stats_plan(M, N);
-  if (p.tnw != 1) {  // 32-channel wave columns: the epilogue prefetch's register budget
-    p.tnw = 1;
-    p.gy = N / 64;
-    const int mt = (int)((M + 127) / 128);
-    int want = 2 * c1_cu_count() / p.gy;
-    if (want < 8) want = 8;
-    if (want > mt) want = mt;
-    p.tiles_per_blk = (mt + want - 1) / want;
-    const int gx = (mt + p.tiles_per_blk - 1) / p.tiles_per_blk;
-    p.gx = (gx + 7) / 8 * 8;
-  }
+  const Conv1x1Plan p = conv1x1_stats_plan(M, N, true);  // K <= 128: the resident 6-stage variant
   *rows = p.gx;
   if (part == nullptr) return;  // size query
   hipLaunchKernelGGL((conv1x1_stats_kernel<1, true, 6, true>), dim3(p.gx * p.gy), dim3(kC1Threads), 0, s, dy1, wt, d,

@@ -39,6 +39,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <atomic>
+
 #include "common.h"
 #include "kernels.h"
 
@@ -515,7 +517,13 @@ int conv3x3_pieces_per_thread(const Conv3x3Geom& g) {
   return (g.vrows * (g.W + 2) * 2 + kCvThreads - 1) / kCvThreads;
 }
 
-static int cu_count() {
+// The CU count every persistent kernel's work split is planned for (this file's
+// conv3x3_wpb, conv1x1_stats_plan, stem_grid): the device's, unless set_plan_cus pinned
+// one.  The pin is process-wide and read on every plan call; the tests use it to
+// reproduce a full-size layer's per-workgroup geometry with small tensors.
+static std::atomic<int> g_plan_cus{0};
+
+static int device_cus() {
   static int n = [] {
     int dev = 0, v = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
@@ -526,9 +534,16 @@ static int cu_count() {
   return n;
 }
 
+void set_plan_cus(int n) { g_plan_cus.store(n > 0 ? n : 0, std::memory_order_relaxed); }
+
+int plan_cus() {
+  const int n = g_plan_cus.load(std::memory_order_relaxed);
+  return n > 0 ? n : device_cus();
+}
+
 int conv3x3_wpb(int N, int H, int W, int Cout) {
   // one workgroup per CU: cu / tiles_n pixel ranges per output-channel block (at least one)
-  const int tiles_n = Cout / kTN, cu = cu_count();
+  const int tiles_n = Cout / kTN, cu = plan_cus();
   const int64_t M = (int64_t)N * H * W;
   int64_t w = tiles_n > 0 ? cu / tiles_n : 1;
   if (w < 1) w = 1;
@@ -555,8 +570,6 @@ bool conv3x3_ok(const Conv3x3Geom& g) {
          (int64_t)g.Cin * 9 * g.Cout < (1ll << 31);
 }
 
-// the compile-time-shape instance (WC, CC) when the layer is one of them and its halo
-// needs exactly NX pieces per thread; false: use the run-time-shape kernel
 struct C3Pre {
   const float* ss;
   int64_t* nbt;
@@ -569,36 +582,49 @@ static void launch_one(const uint16_t* x, const uint16_t* w, uint16_t* y, const 
                      g, part, pre.ss, pre.nbt);
 }
 
-template <int NX, bool FLIP, int JB, int DEPTH, int WC, int CC, bool ST, bool PRE>
-static bool launch_fixed(const uint16_t* x, const uint16_t* w, uint16_t* y, const Conv3x3Geom& g, hipStream_t st,
-                         dim3 grid, float* part, const C3Pre& pre) {
+// The compile-time-shape instances (tile size, NX, WC, CC): ResNet-50's stride-1 3x3
+// shapes (bottleneck conv2 forward; the input gradient of the same layers reads dy
+// with the same width and channel count).  28x28 at 512-pixel tiles: a workgroup's
+// range is one whole image (784 pixels = a 512 + a 272 tile).
+struct C3Fixed {
+  int tm, nx, wc, cc;
+};
+constexpr C3Fixed kC3Fixed[] = {
+    {512, 7, 56, 64}, {512, 5, 28, 128}, {256, 4, 28, 128}, {256, 4, 14, 256}, {256, 4, 7, 512}};
+
+Conv3x3Instance conv3x3_instance(const Conv3x3Geom& g, bool pre) {
   static const bool generic = getenv("RLA_CONV3X3_GENERIC") != nullptr;  // A/B switch: run-time-shape kernel
-  if (generic || g.W != WC || g.Cin != CC || conv3x3_pieces_per_thread(g) > NX ||
-      conv3x3_pieces_per_thread(g) < NX - 1)
-    return false;
-  launch_one<NX, FLIP, JB, DEPTH, WC, CC, ST, PRE>(x, w, y, g, st, grid, part, pre);
-  return true;
+  const int pieces = conv3x3_pieces_per_thread(g);
+  // a compile-time-shape instance when the layer is one of them and its halo needs NX
+  // or NX - 1 pieces per thread.  Not with PRE: those instances already hold every VGPR
+  // and AGPR, the transform's temporaries spilled (732-1232 B of scratch per lane) --
+  // PRE runs the run-time-shape kernel
+  if (!pre && !generic)
+    for (const C3Fixed& f : kC3Fixed)
+      if (g.tm == f.tm && g.W == f.wc && g.Cin == f.cc && pieces <= f.nx && pieces >= f.nx - 1)
+        return Conv3x3Instance{f.nx, true};
+  return Conv3x3Instance{pieces <= 4 ? 4 : (pieces >= kMaxNX ? kMaxNX : pieces), false};
 }
 
 template <bool FLIP, int JB, int DEPTH, bool ST, bool PRE>
 static void launch_nx(const uint16_t* x, const uint16_t* w, uint16_t* y, const Conv3x3Geom& g, hipStream_t st,
                       dim3 grid, float* part, const C3Pre& pre) {
-  // ResNet-50's stride-1 3x3 shapes (bottleneck conv2 forward; the input gradient of
-  // the same layers reads dy with the same width and channel count).  Not with PRE:
-  // those instances already hold every VGPR and AGPR, the transform's temporaries
-  // spilled (732-1232 B of scratch per lane) -- PRE runs the run-time-shape kernel
-  if constexpr (PRE) {
-  } else if constexpr (JB == 4) {
-    if (launch_fixed<7, FLIP, JB, DEPTH, 56, 64, ST, PRE>(x, w, y, g, st, grid, part, pre)) return;
-    // 28x28: a workgroup's range is one whole image (784 pixels = a 512 + a 272 tile)
-    if (launch_fixed<5, FLIP, JB, DEPTH, 28, 128, ST, PRE>(x, w, y, g, st, grid, part, pre)) return;
-  } else {
-    if (launch_fixed<4, FLIP, JB, DEPTH, 28, 128, ST, PRE>(x, w, y, g, st, grid, part, pre)) return;
-    if (launch_fixed<4, FLIP, JB, DEPTH, 14, 256, ST, PRE>(x, w, y, g, st, grid, part, pre)) return;
-    if (launch_fixed<4, FLIP, JB, DEPTH, 7, 512, ST, PRE>(x, w, y, g, st, grid, part, pre)) return;
+  const Conv3x3Instance ins = conv3x3_instance(g, PRE);
+  if constexpr (!PRE) {
+    if (ins.fixed) {  // (g.tm, g.W) names the kC3Fixed row conv3x3_instance matched
+      if constexpr (JB == 4) {
+        if (g.W == 56) launch_one<7, FLIP, JB, DEPTH, 56, 64, ST, PRE>(x, w, y, g, st, grid, part, pre);
+        else launch_one<5, FLIP, JB, DEPTH, 28, 128, ST, PRE>(x, w, y, g, st, grid, part, pre);
+      } else {
+        if (g.W == 28) launch_one<4, FLIP, JB, DEPTH, 28, 128, ST, PRE>(x, w, y, g, st, grid, part, pre);
+        else if (g.W == 14) launch_one<4, FLIP, JB, DEPTH, 14, 256, ST, PRE>(x, w, y, g, st, grid, part, pre);
+        else launch_one<4, FLIP, JB, DEPTH, 7, 512, ST, PRE>(x, w, y, g, st, grid, part, pre);
+      }
+      return;
+    }
   }
-  switch (conv3x3_pieces_per_thread(g)) {
-    case 1: case 2: case 3: case 4:
+  switch (ins.nx) {
+    case 4:
       launch_one<4, FLIP, JB, DEPTH, 0, 0, ST, PRE>(x, w, y, g, st, grid, part, pre);
       break;
     case 5:

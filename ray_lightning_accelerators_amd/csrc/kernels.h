@@ -134,7 +134,11 @@ bool conv1x1_stats_ok(int64_t M, int K, int N);
 // pre_ss ([4, K] BatchNorm stats, K <= 512): x is a deferred BatchNorm + ReLU's input,
 // each x fragment becomes bf16(relu(x * scale + shift)) in the kernel (nbt_inc += 1)
 bool conv1x1_pre_ok(int64_t M, int K, int N);
-Conv1x1Plan conv1x1_stats_plan(int64_t M, int N);
+// bwd: launch_conv1x1_bn_bwd's plan (32-channel wave columns whatever N)
+Conv1x1Plan conv1x1_stats_plan(int64_t M, int N, bool bwd = false);
+// the weight path launch_conv1x1_stats takes: 0 resident beside a 6-stage x ring (<= 16 KB
+// weight block), 1 resident beside 4 stages (<= 32 KB), 2 streamed with x
+int conv1x1_variant(int K, const Conv1x1Plan& p);
 void launch_conv1x1_stats(const uint16_t* x, const uint16_t* w, uint16_t* y, int64_t M, int K, int N,
                           const Conv1x1Plan& p, float* part, hipStream_t s, const float* pre_ss = nullptr,
                           int64_t* nbt_inc = nullptr);
@@ -316,10 +320,22 @@ struct Conv3x3Geom {
   int tm;     // pixels per workgroup tile: 256 or 512 (conv3x3_pick_tm)
   int wpb;    // workgroups per 64-channel output block = contiguous pixel ranges (conv3x3_wpb)
 };
+// The CU count the persistent kernels' work splits are planned for (conv3x3_wpb,
+// conv1x1_stats_plan, stem_grid): the device's, unless set_plan_cus(n > 0) pinned one
+// for the whole process (n <= 0 restores the device value).  Read on every plan call.
+int plan_cus();
+void set_plan_cus(int n);
 int conv3x3_wpb(int N, int H, int W, int Cout);
 int conv3x3_pick_tm(int N, int H, int W, int Cout);
 int conv3x3_vrows(const Conv3x3Geom& g);
+int conv3x3_pieces_per_thread(const Conv3x3Geom& g);  // 16-byte halo pieces per thread and chunk
 bool conv3x3_ok(const Conv3x3Geom& g);
+// the template instance launch_conv3x3 runs for g (pre: with pre_ss)
+struct Conv3x3Instance {
+  int nx;      // halo pieces per thread the instance is compiled for
+  bool fixed;  // compile-time width and input channels
+};
+Conv3x3Instance conv3x3_instance(const Conv3x3Geom& g, bool pre);
 // flip: input gradient -- x is dy [N, H, W, Cin], w the FORWARD weight [Cin][3][3][Cout]
 // (Cin = the forward's output channels), y is dx [N, H, W, Cout]
 // part (forward only, or null): BatchNorm partial sums of bf16(y), [g.wpb][2][Cout] fp32

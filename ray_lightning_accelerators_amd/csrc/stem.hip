@@ -445,17 +445,6 @@ __global__ __launch_bounds__(256) void stem_wgrad_reduce_kernel(const float* __r
   if (r < 7 && s < 7 && c < 3) out[co * 147 + r * 21 + s * 3 + c] = a;
 }
 
-int st_cu_count() {
-  static int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-      v = 256;
-    return v;
-  }();
-  return n;
-}
-
 }  // namespace
 
 bool stem_ok(const StemGeom& g) {
@@ -466,7 +455,7 @@ bool stem_ok(const StemGeom& g) {
 
 int stem_grid(const StemGeom& g) {
   const int ntile = g.N * ((g.OH + kT - 1) / kT);
-  const int cu = st_cu_count();
+  const int cu = plan_cus();
   return ntile < cu ? ntile : cu;
 }
 

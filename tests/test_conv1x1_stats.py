@@ -13,6 +13,7 @@ gpu = pytest.mark.gpu
 # column count that is not a multiple of 128 (one 32-channel block per wave), K = 32;
 # together they reach every launch variant (resident weights at 2 or 1 workgroups
 # per CU, streamed weights, 32- and 64-channel wave columns)
+# (on a 256-CU part each runs one tile per workgroup; test_conv_partition.py covers the multi-tile paths)
 SHAPES = [
     (2 * 56 * 56, 64, 256),
     (2 * 56 * 56, 256, 64),

@@ -8,6 +8,7 @@ gpu = pytest.mark.gpu
 
 # (N, H, W, Cin, Cout): ResNet-50's stride-1 conv2 shapes at small batch, plus tiles
 # that cross image boundaries (H*W not a multiple of 256, tiny images) and a tail
+# (on a 256-CU part each runs one tile per workgroup; test_conv_partition.py covers the multi-tile paths)
 SHAPES = [
     (2, 56, 56, 64, 64),
     (2, 28, 28, 128, 128),
