@@ -1,10 +1,16 @@
-"""Stride-1 1x1 convolution on NHWC bf16 activations, backend chosen per operation.
+"""Convolutions on NHWC bf16 activations, the backend chosen per operation and shape.
+
+Every ResNet-50 convolution goes through this file: the stride-1 1x1 layers
+(``Conv1x1NHWC`` / ``_Conv1x1Fn``), the KxK and strided layers (``conv_nhwc`` /
+``_ConvNHWCFn``) and the 7x7 stem (``stem_conv`` / ``_StemFn``), each forward, input
+gradient (dgrad) and weight gradient (wgrad; fp32, the master weight's gradient).
+The backends are the in-tree MFMA kernels (``*_hip``), a hipBLASLt GEMM and MIOpen.
 
 A 1x1 convolution over a channels_last tensor IS a GEMM on the [N*H*W, C] view:
 
   forward  y[M, Cout]  = x[M, Cin]  . W^T
   dgrad    dx[M, Cin]  = dy[M, Cout] . W
-  wgrad    dW[Cout, Cin] = dy^T . x      (fp32 output: the fp32 master gradient)
+  wgrad    dW[Cout, Cin] = dy^T . x
 
 MIOpen runs these as convolutions; for ResNet-50's shapes it is the faster choice
 for some (e.g. the wgrad of the large 56x56 layers) and far slower for others: its
@@ -12,29 +18,37 @@ wgrad costs ~80 us whatever the size (zero-fill + split-K atomics + a bf16->fp32
 cast, profiles/r3_rn50/kernel_stats_rn50_steady.csv) and its forward of the
 14x14 / 7x7 layers runs 2-5x a hipBLASLt GEMM (profiles/r3_rn50/conv1x1_probe_perop.log).
 So every (operation, shape) picks its backend once, timed on the device at first
-use (like cudnn.benchmark), and the GEMM wgrad writes fp32 directly -- no zero
-fill, no atomics, no cast kernel.
+use (like cudnn.benchmark): each operation builds ONE table ``{name: callable}``,
+``_pick`` names the winner and that table's callable runs.  ``RLA_CONV1X1`` and
+``RLA_CONV_WGRAD`` pin a backend by its name in the table (``miopen|gemm|hip|...``).
+
+Around the convolutions themselves:
+
+* ``GradFork``: two convolutions reading one tensor sum their input gradients in place;
+* ``BNStats``: a forward whose kernel has the BatchNorm statistics of its output in
+  the epilogue hands them to that BatchNorm, which then skips its own pass;
+* deferred BatchNorm (ops/bn.py DeferredApply, ``pre``): the input is a BatchNorm +
+  ReLU's *input* and the forward and weight-gradient kernels apply the map to
+  their operands, so the activation is never written.
 
 ``Conv1x1NHWC`` is a drop-in ``nn.Conv2d(cin, cout, 1, bias=False)`` (same
 parameter and state-dict key); anything outside the fast path (CPU, fp32, NCHW,
-odd alignment) runs the stock convolution.  ``RLA_CONV1X1=miopen|gemm|auto``.
+odd alignment) runs the stock convolution.
 """
 from __future__ import annotations
 
 import functools
 import os
-from typing import Dict, Optional, Tuple
+from typing import Callable, Dict, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
 from torch import nn
 
-_choice: Dict[Tuple[str, int, int, int], str] = {}
-_timings: Dict[Tuple[str, int, int, int], Dict[str, float]] = {}
+# keyed by (op, M, Cin, Cout) for the 1x1 layers, (op, M, Cin, Cout, KH, KW, stride, pad) for KxK
+_choice: Dict[Tuple, str] = {}
+_timings: Dict[Tuple, Dict[str, float]] = {}
 stats = {"fast": 0, "fallback": 0, "bn_dgrad_fused": 0, "stem": 0, "pre_applied": 0}
-
-_conv = torch.ops.aten.convolution
-_conv_bwd = torch.ops.aten.convolution_backward
 
 
 def _mode() -> str:
@@ -100,6 +114,49 @@ def _pick(op: str, key: Tuple[int, ...], cands) -> str:
 def choices() -> Dict[str, Dict[str, float]]:
     """The autotuned backends so far: ``"op M Cin Cout" -> {backend: us, ..., "pick": name}``."""
     return {" ".join(map(str, k)): dict(_timings.get(k, {}), pick=c) for k, c in _choice.items()}
+
+
+def _run(op: str, key: Tuple[int, ...], cands: Dict[str, Callable]):
+    """The result of ``op``'s picked backend: the callable that ``_pick`` timed, run once more."""
+    return cands[_pick(op, key, cands)]()
+
+
+def _run_stats(op: str, key: Tuple[int, ...], cands: Dict[str, Callable], fused: str, bn_stats: "BNStats"):
+    """``_run`` for a forward whose output a training BatchNorm reads: ``cands[fused]``
+    returns (y, part) from a statistics epilogue and hands ``part`` to that BatchNorm;
+    the others return y alone and BatchNorm then runs its own partial pass, so they
+    are timed with that pass (and run without it)."""
+    timed = {name: fn if name == fused else (lambda fn=fn: _bn_partial(fn())) for name, fn in cands.items()}
+    name = _pick(op, key, timed)
+    if name != fused:
+        return cands[name]()
+    y, bn_stats.part = cands[name]()
+    return y
+
+
+# the library calls, one spelling each (stride / padding as pairs; dilation 1, groups 1, no bias)
+
+def _miopen_fwd(x: torch.Tensor, w4: torch.Tensor, stride=(1, 1), padding=(0, 0)) -> torch.Tensor:
+    return torch.ops.aten.convolution(x, w4, None, list(stride), list(padding), [1, 1], False, [0, 0], 1)
+
+
+def _miopen_bwd(dy: torch.Tensor, x: torch.Tensor, w4: torch.Tensor, stride, padding, need_dx: bool, need_dw: bool):
+    """(dx, dw) of one MIOpen call, None where not asked for; dw in fp32 (MIOpen's is bf16)."""
+    dx, dw = torch.ops.aten.convolution_backward(dy, x, w4, None, list(stride), list(padding), [1, 1], False, [0, 0],
+                                                 1, [need_dx, need_dw, False])[:2]
+    return dx, (dw.float() if need_dw else None)
+
+
+def _gemm_fwd(x2: torch.Tensor, wb: torch.Tensor) -> torch.Tensor:
+    return torch.mm(x2, wb.t())
+
+
+def _gemm_dgrad(dy2: torch.Tensor, wb: torch.Tensor) -> torch.Tensor:
+    return torch.mm(dy2, wb)
+
+
+def _gemm_wgrad(dy2: torch.Tensor, x2: torch.Tensor) -> torch.Tensor:
+    return torch.ops.aten.mm.dtype(dy2.t(), x2, torch.float32)  # fp32 straight from the GEMM: no cast kernel
 
 
 def wgrad_ok(cin: int, cout: int) -> bool:
@@ -173,11 +230,8 @@ def conv3x3_stats_hip(x: torch.Tensor, wb: torch.Tensor, pre=None):
 
     n, cin, h, w = x.shape
     cout = wb.size(0)
-    if pre is not None:
-        y, part = require().conv3x3_stats(x.permute(0, 2, 3, 1), wb.permute(0, 2, 3, 1), n, h, w, cin, cout,
-                                          pre.st, pre.take_nbt())
-    else:
-        y, part = require().conv3x3_stats(x.permute(0, 2, 3, 1), wb.permute(0, 2, 3, 1), n, h, w, cin, cout)
+    pre_args = () if pre is None else (pre.st, pre.take_nbt())
+    y, part = require().conv3x3_stats(x.permute(0, 2, 3, 1), wb.permute(0, 2, 3, 1), n, h, w, cin, cout, *pre_args)
     return y.permute(0, 3, 1, 2), part
 
 
@@ -268,7 +322,7 @@ def _acc_dgrad(d: torch.Tensor, dy2: torch.Tensor, wb: torch.Tensor) -> None:
     if d.permute(0, 2, 3, 1).is_contiguous():
         _nhwc2d(d).addmm_(dy2, wb)
     else:
-        d.add_(_from2d(torch.mm(dy2, wb), d.size(0), d.size(2), d.size(3)))
+        d.add_(_from2d(_gemm_dgrad(dy2, wb), d.size(0), d.size(2), d.size(3)))
 
 
 class BNStats:
@@ -297,10 +351,8 @@ def conv1x1_stats_hip(x: torch.Tensor, wb: torch.Tensor, pre=None):
     from . import require
 
     n, _, h, w = x.shape
-    if pre is not None:
-        y2, part = require().conv1x1_stats(_nhwc2d(x), wb, pre.st, pre.take_nbt())
-    else:
-        y2, part = require().conv1x1_stats(_nhwc2d(x), wb)
+    pre_args = () if pre is None else (pre.st, pre.take_nbt())
+    y2, part = require().conv1x1_stats(_nhwc2d(x), wb, *pre_args)
     return _from2d(y2, n, h, w), part
 
 
@@ -338,36 +390,24 @@ class _Conv1x1Fn(torch.autograd.Function):
         x2 = _nhwc2d(x)
         key = (x2.size(0), cin, cout)
         w4 = wb.view(cout, cin, 1, 1)
-        ctx.pre_st = None
+        ctx.pre_st = pre.st if pre is not None else None
+        cands = {
+            "gemm": lambda: _from2d(_gemm_fwd(x2, wb), n, h, w),
+            "miopen": lambda: _miopen_fwd(x, w4),
+        }
         if pre is not None:
             # x is a deferred BatchNorm + ReLU's input (ops/bn.py DeferredApply): the
             # kernels apply its map to their operands; the caller checked conv1x1_pre_ok
+            # (and passes no fork and no fuse_bn)
             y, part = conv1x1_stats_hip(x, wb, pre)
             if bn_stats is not None:
                 bn_stats.part = part
-            ctx.pre_st = pre.st
-            ctx.save_for_backward(x, wb)
-            ctx.key, ctx.fork, ctx.fold = key, None, None
-            return y
-        if bn_stats is not None and conv1x1_stats_ok(x2.size(0), cin, cout):
+        elif bn_stats is not None and conv1x1_stats_ok(x2.size(0), cin, cout):
             # the next BatchNorm's statistics: in this GEMM's epilogue, or the library
             # forward + BN's own partial pass -- whichever is faster for the shape
-            be = _pick("fwd_st", key, {
-                "hip": lambda: conv1x1_stats_hip(x, wb),
-                "gemm": lambda: _bn_partial(_from2d(torch.mm(x2, wb.t()), n, h, w)),
-                "miopen": lambda: _bn_partial(_conv(x, w4, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1)),
-            })
+            y = _run_stats("fwd_st", key, {"hip": lambda: conv1x1_stats_hip(x, wb), **cands}, "hip", bn_stats)
         else:
-            be = _pick("fwd", key, {
-                "gemm": lambda: torch.mm(x2, wb.t()),
-                "miopen": lambda: _conv(x, w4, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1),
-            })
-        if be == "hip":
-            y, bn_stats.part = conv1x1_stats_hip(x, wb)
-        elif be == "gemm":
-            y = _from2d(torch.mm(x2, wb.t()), n, h, w)
-        else:
-            y = _conv(x, w4, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1)
+            y = _run("fwd", key, cands)
         ctx.save_for_backward(x, wb)
         ctx.key = key
         ctx.fork = fork
@@ -389,26 +429,22 @@ class _Conv1x1Fn(torch.autograd.Function):
         dy = dy.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
         dy2, x2 = _nhwc2d(dy), _nhwc2d(x)
         w4 = wb.view(cout, cin, 1, 1)
+        geo = ((1, 1), (0, 0))  # stride, padding
+        st = ctx.pre_st  # x is a deferred BatchNorm + ReLU's input: no fork, no fold
+        dgrad = {
+            "gemm": lambda: _from2d(_gemm_dgrad(dy2, wb), n, h, w),
+            "miopen": lambda: _miopen_bwd(dy, x, w4, *geo, True, False)[0],
+        }
+        wgrad = {
+            "gemm": lambda: _gemm_wgrad(dy2, x2).view(cout, cin, 1, 1),
+            "miopen": lambda: _miopen_bwd(dy, x, w4, *geo, False, True)[1],
+        }
+        if wgrad_ok(cin, cout) or st is not None:
+            wgrad["hip"] = lambda: wgrad_hip(dy, x, (1, 1), *geo, pre_ss=st)
         dx = dw = None
         be_d = be_w = None
         fork = ctx.fork if ctx.needs_input_grad[0] else None
         fold = ctx.fold
-        if ctx.pre_st is not None:
-            # deferred-BatchNorm input: the input gradient (w.r.t. the activation) does not
-            # read x; the weight gradient stages relu(x * scale + shift) in its kernel
-            if ctx.needs_input_grad[0]:
-                be_d = _pick("dgrad", ctx.key, {
-                    "gemm": lambda: torch.mm(dy2, wb),
-                    "miopen": lambda: _conv_bwd(dy, x, w4, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
-                                                [True, False, False])[0],
-                })
-                if be_d == "gemm":
-                    dx = _from2d(torch.mm(dy2, wb), n, h, w)
-                else:
-                    dx = _conv_bwd(dy, x, w4, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1, [True, False, False])[0]
-            if ctx.needs_input_grad[1]:
-                dw = wgrad_hip(dy, x, (1, 1), (1, 1), (0, 0), pre_ss=ctx.pre_st)
-            return dx, dw, None, None, None, None, None
         if fold is not None and fold.dres is not None and ctx.needs_input_grad[0]:
             # d = (dy . W + dres_next) * (x > 0) and its BatchNorm partial sums in one
             # kernel; the producer BatchNorm's backward takes d as its dy
@@ -426,36 +462,19 @@ class _Conv1x1Fn(torch.autograd.Function):
             # second of a forked pair: dx += dy . W in the GEMM itself (beta = 1)
             dx = _fork_dx(fork, None, lambda d: _acc_dgrad(d, dy2, wb))
         elif ctx.needs_input_grad[0]:
-            be_d = _pick("dgrad", ctx.key, {
-                "gemm": lambda: torch.mm(dy2, wb),
-                "miopen": lambda: _conv_bwd(dy, x, w4, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
-                                            [True, False, False]),
-            })
+            be_d = _pick("dgrad", ctx.key, dgrad)
         if ctx.needs_input_grad[1]:
-            cands = {
-                "gemm": lambda: torch.ops.aten.mm.dtype(dy2.t(), x2, torch.float32),
-                "miopen": lambda: _conv_bwd(dy, x, w4, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
-                                            [False, True, False])[1].float(),
-            }
-            if wgrad_ok(cin, cout):
-                cands["hip"] = lambda: wgrad_hip(dy, x, (1, 1), (1, 1), (0, 0))
-            be_w = _pick("wgrad", ctx.key, cands)
+            # deferred-BatchNorm input: the input gradient (w.r.t. the activation) does not
+            # read x; the weight gradient stages relu(x * scale + shift), on the MFMA kernel only
+            be_w = "hip" if st is not None else _pick("wgrad", ctx.key, wgrad)
         if be_d == "miopen" and be_w == "miopen" and fork is None:
             # both from MIOpen: one call (its host cost is tens of us per call)
-            dx, dw = _conv_bwd(dy, x, w4, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1, [True, True, False])[:2]
-            return dx, dw.float(), None, None, None, None, None
-        if be_d == "gemm":
-            dx = _fork_dx(fork, lambda: _from2d(torch.mm(dy2, wb), n, h, w), None)
-        elif be_d == "miopen":
-            dx = _fork_dx(fork, lambda: _conv_bwd(dy, x, w4, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
-                                                  [True, False, False])[0], None)
-        if be_w == "hip":
-            dw = wgrad_hip(dy, x, (1, 1), (1, 1), (0, 0))
-        elif be_w == "gemm":
-            dw = torch.ops.aten.mm.dtype(dy2.t(), x2, torch.float32).view(cout, cin, 1, 1)
-        elif be_w == "miopen":
-            dw = _conv_bwd(dy, x, w4, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
-                           [False, True, False])[1].float()
+            dx, dw = _miopen_bwd(dy, x, w4, *geo, True, True)
+        else:
+            if be_d is not None:
+                dx = _fork_dx(fork, dgrad[be_d], None)
+            if be_w is not None:
+                dw = wgrad[be_w]()
         return dx, dw, None, None, None, None, None
 
 
@@ -509,45 +528,33 @@ class Conv1x1NHWC(nn.Conv2d):
 
 
 class _ConvNHWCFn(torch.autograd.Function):
-    """KxK (or strided) bf16 NHWC convolution: MIOpen forward and dgrad, the weight
-    gradient from MIOpen or the MFMA kernel (``wgrad_hip``), picked per shape on
-    device time.  The weight gradient reaches the fp32 master weight in fp32."""
+    """KxK (or strided) bf16 NHWC convolution: MIOpen or, for 3x3 / stride 1 / pad 1, the
+    MFMA kernels for the forward and dgrad; the weight gradient from MIOpen or the MFMA
+    kernel (``wgrad_hip``); each picked per shape on device time.  The weight gradient
+    reaches the fp32 master weight in fp32."""
 
     @staticmethod
     def forward(ctx, x, weight, wb, stride, padding, fork=None, bn_stats=None, pre=None):
-        ctx.pre_st = None
+        ctx.pre_st = pre.st if pre is not None else None
+        ctx.c3 = pre is not None or conv3x3_ok(x, wb, stride, padding)
+        cands = {"miopen": lambda: _miopen_fwd(x, wb, stride, padding)}
         if pre is not None:
             # x is a deferred BatchNorm + ReLU's input (ops/bn.py DeferredApply): the
-            # forward stages the activation itself (conv_nhwc chose this path)
+            # forward stages the activation itself (conv_nhwc chose this path: 3x3 /
+            # stride 1 / pad 1, no fork)
             y, bn_stats.part = conv3x3_stats_hip(x, wb, pre)
-            ctx.pre_st = pre.st
-            ctx.c3 = True
-            ctx.save_for_backward(x, wb)
-            ctx.geo = (tuple(stride), tuple(padding))
-            ctx.fork = None
-            return y
-        ctx.c3 = conv3x3_ok(x, wb, stride, padding)
-        be = "miopen"
-        if ctx.c3:
+        elif not ctx.c3:
+            y = cands["miopen"]()  # the only backend of a strided or non-3x3 forward
+        else:
             key = (x.size(0) * x.size(2) * x.size(3), x.size(1), wb.size(0), 3, 3, 1, 1)
             if bn_stats is not None and conv3x3_stats_enabled():
                 # the next BatchNorm's statistics: in this kernel's epilogue, or the
                 # library forward + BN's own partial pass -- whichever is faster
-                be = _pick("fwd_kxk_st", key, {
-                    "miopen": lambda: _bn_partial(_conv(x, wb, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1)),
-                    "hip_st": lambda: conv3x3_stats_hip(x, wb),
-                })
+                cands["hip_st"] = lambda: conv3x3_stats_hip(x, wb)
+                y = _run_stats("fwd_kxk_st", key, cands, "hip_st", bn_stats)
             else:
-                be = _pick("fwd_kxk", key, {
-                    "miopen": lambda: _conv(x, wb, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1),
-                    "hip": lambda: conv3x3_hip(x, wb),
-                })
-        if be == "hip_st":
-            y, bn_stats.part = conv3x3_stats_hip(x, wb)
-        elif be == "hip":
-            y = conv3x3_hip(x, wb)
-        else:
-            y = _conv(x, wb, None, list(stride), list(padding), [1, 1], False, [0, 0], 1)
+                cands["hip"] = lambda: conv3x3_hip(x, wb)
+                y = _run("fwd_kxk", key, cands)
         ctx.save_for_backward(x, wb)
         ctx.geo = (tuple(stride), tuple(padding))
         ctx.fork = fork
@@ -560,18 +567,27 @@ class _ConvNHWCFn(torch.autograd.Function):
         x, wb = ctx.saved_tensors
         stride, padding = ctx.geo
         dy = dy.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+        cout, cin, kh, kw = wb.shape
+        st = ctx.pre_st  # x is a deferred BatchNorm + ReLU's input (3x3 / stride 1 / pad 1, no fork)
+        dgrad = {"miopen": lambda: _miopen_bwd(dy, x, wb, stride, padding, True, False)[0]}
+        if ctx.c3:
+            dgrad["hip"] = lambda: conv3x3_dgrad_hip(dy, wb)
+        # deferred-BatchNorm input: the weight gradient stages relu(x * scale + shift) (halo
+        # or generic MFMA kernel, csrc/conv_wgrad.hip PRE), which MIOpen cannot; the input
+        # gradient does not read x
+        wgrad = {"miopen": lambda: _miopen_bwd(dy, x, wb, stride, padding, False, True)[1]} if st is None else {}
+        wgrad["hip"] = lambda: wgrad_hip(dy, x, (kh, kw), stride, padding, pre_ss=st)
+        if (kh, kw, stride, padding) == (3, 3, (1, 1), (1, 1)):
+            # "hip" is the halo kernel here; the generic tap-GEMM kernel competes too
+            wgrad["hip_gen"] = lambda: wgrad_hip(dy, x, (kh, kw), stride, padding, algo=1, pre_ss=st)
         dx = dw = None
-        be = None
         fork = ctx.fork if ctx.needs_input_grad[0] else None
-        if fork is not None and fork.users >= 2 and fork.dx is not None and wb.shape[2:] == (1, 1) \
+        if fork is not None and fork.users >= 2 and fork.dx is not None and (kh, kw) == (1, 1) \
                 and padding == (0, 0):
             # second of a forked pair, strided 1x1: GEMM over the output pixels, added
             # into every stride-th input pixel of the parked dgrad (1/s^2 of it)
-            cout, cin = wb.shape[:2]
             n_, _, oh_, ow_ = dy.shape
-            w2 = wb.reshape(cout, cin)
-
-            g2 = torch.mm(_nhwc2d(dy), w2)
+            g2 = _gemm_dgrad(_nhwc2d(dy), wb.reshape(cout, cin))
 
             def acc(d):
                 # (measured and reverted, round 5: the same sum as ONE strided batched
@@ -593,70 +609,23 @@ class _ConvNHWCFn(torch.autograd.Function):
 
             dx = _fork_dx(fork, None, acc)
             fork = None  # the input gradient is settled
-        if ctx.pre_st is not None:
-            # deferred-BatchNorm input: the weight gradient stages relu(x * scale + shift)
-            # (halo or generic MFMA kernel, csrc/conv_wgrad.hip PRE); the input gradient
-            # does not read x
-            cout, cin, kh, kw = wb.shape
-            if ctx.needs_input_grad[1]:
-                key = (x.size(0) * dy.size(2) * dy.size(3), cin, cout, kh, kw, stride[0], padding[0])
-                st = ctx.pre_st
-                bw = _pick("wgrad_kxk_pre", key, {
-                    "hip": lambda: wgrad_hip(dy, x, (kh, kw), stride, padding, pre_ss=st),
-                    "hip_gen": lambda: wgrad_hip(dy, x, (kh, kw), stride, padding, algo=1, pre_ss=st),
-                })
-                dw = wgrad_hip(dy, x, (kh, kw), stride, padding, algo=0 if bw == "hip" else 1, pre_ss=st)
-            if ctx.needs_input_grad[0]:
-                key = (x.size(0) * x.size(2) * x.size(3), cin, cout, 3, 3, 1, 1)
-                be_d = _pick("dgrad_kxk", key, {
-                    "miopen": lambda: _conv_bwd(dy, x, wb, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
-                                                [True, False, False])[0],
-                    "hip": lambda: conv3x3_dgrad_hip(dy, wb),
-                })
-                if be_d == "hip":
-                    dx = conv3x3_dgrad_hip(dy, wb)
-                else:
-                    dx = _conv_bwd(dy, x, wb, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1, [True, False, False])[0]
-            return dx, dw, None, None, None, None, None, None
-        if ctx.needs_input_grad[1]:
-            cout, cin, kh, kw = wb.shape
-            key = (x.size(0) * dy.size(2) * dy.size(3), cin, cout, kh, kw, stride[0], padding[0])
-            cands = {
-                "miopen": lambda: _conv_bwd(dy, x, wb, None, list(stride), list(padding), [1, 1], False, [0, 0], 1,
-                                            [False, True, False])[1].float(),
-                "hip": lambda: wgrad_hip(dy, x, (kh, kw), stride, padding),
-            }
-            if (kh, kw, tuple(stride), tuple(padding)) == (3, 3, (1, 1), (1, 1)):
-                # "hip" is the halo kernel here; the generic tap-GEMM kernel competes too
-                cands["hip_gen"] = lambda: wgrad_hip(dy, x, (kh, kw), stride, padding, algo=1)
-            be = _pick("wgrad_kxk", key, cands)
         need_dx = bool(ctx.needs_input_grad[0]) and dx is None
-        be_d = None
-        if need_dx and ctx.c3:
-            cout, cin = wb.shape[:2]
+        be_d = be_w = None
+        if ctx.needs_input_grad[1]:
+            key = (x.size(0) * dy.size(2) * dy.size(3), cin, cout, kh, kw, stride[0], padding[0])
+            be_w = _pick("wgrad_kxk" if st is None else "wgrad_kxk_pre", key, wgrad)
+        if need_dx:  # MIOpen is the only backend of a strided or non-3x3 input gradient
             key = (x.size(0) * x.size(2) * x.size(3), cin, cout, 3, 3, 1, 1)
-            be_d = _pick("dgrad_kxk", key, {
-                "miopen": lambda: _conv_bwd(dy, x, wb, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
-                                            [True, False, False])[0],
-                "hip": lambda: conv3x3_dgrad_hip(dy, wb),
-            })
-        if be_d == "hip":
-            dx = _fork_dx(fork, lambda: conv3x3_dgrad_hip(dy, wb), None)
-            need_dx = False
-        if be == "miopen":
+            be_d = _pick("dgrad_kxk", key, dgrad) if ctx.c3 else "miopen"
+        if be_d == "miopen" and be_w == "miopen":
             # MIOpen for both gradients: one call, as F.conv2d's autograd makes it
-            mask = [need_dx, True, False]
-            dxm, dw = _conv_bwd(dy, x, wb, None, list(stride), list(padding), [1, 1], False, [0, 0], 1, mask)[:2]
-            if need_dx:
-                dx = _fork_dx(fork, lambda: dxm, None)
-            return dx, dw.float(), None, None, None, None, None, None
-        if need_dx:
-            dx = _fork_dx(fork, lambda: _conv_bwd(dy, x, wb, None, list(stride), list(padding), [1, 1], False,
-                                                  [0, 0], 1, [True, False, False])[0], None)
-        if be == "hip":
-            dw = wgrad_hip(dy, x, (kh, kw), stride, padding)
-        elif be == "hip_gen":
-            dw = wgrad_hip(dy, x, (kh, kw), stride, padding, algo=1)
+            dxm, dw = _miopen_bwd(dy, x, wb, stride, padding, True, True)
+            dx = _fork_dx(fork, lambda: dxm, None)
+        else:
+            if be_d is not None:
+                dx = _fork_dx(fork, dgrad[be_d], None)
+            if be_w is not None:
+                dw = wgrad[be_w]()
         return dx, dw, None, None, None, None, None, None
 
 
@@ -717,7 +686,7 @@ class _StemFn(torch.autograd.Function):
         dy = dy.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
         dx = dw = None
         if ctx.needs_input_grad[0]:
-            dx = _conv_bwd(dy, x, wb, None, [2, 2], [3, 3], [1, 1], False, [0, 0], 1, [True, False, False])[0]
+            dx = _miopen_bwd(dy, x, wb, (2, 2), (3, 3), True, False)[0]
         if ctx.needs_input_grad[1]:
             dw = stem_wgrad_hip(x, dy)
         return dx, dw, None, None
