@@ -10,7 +10,9 @@
 //
 //   head(t)   one workgroup per 32 batch rows (the per-sample chain is row-
 //             independent): H1 = relu(H1pre[t] + b1) (4 KB read instead of X + W1),
-//             layers 2/3, log_softmax/NLL/accuracy, dH2, dH1.  Hands the
+//             layers 2/3, log_softmax/NLL/accuracy (one (row, class slot) element per
+//             thread; the rows' loss statistics parked in LDS and reduced where
+//             they are consumed, off the chain), dH2, dH1.  Hands the
 //             transposed activations / deltas (H1^T, H2^T, dH2^T, dZ^T, dH1^T;
 //             bf16, [rows][Bp]) to the tail through HBM and zeroes its rows of
 //             the other H1pre slot.  With several row blocks, each writes its
@@ -80,7 +82,7 @@ struct Cfg3 {
   static constexpr size_t odZ = oZ + (size_t)BC * 16 * 4;
   static constexpr size_t odZT = odZ + (size_t)BC * kDZS * 2;
   static constexpr size_t oY = odZT + (size_t)16 * TS * 2;
-  static constexpr size_t oMisc = oY + (size_t)BC * 4;
+  static constexpr size_t oMisc = oY + (size_t)BC * 4;  // 64 spare bytes (the loss statistics live in sZ)
   static constexpr size_t oBias = oMisc + 64;
   // K-split partial sums (fp32), reduced in fixed group order: layer 3 [KG3][BC][16],
   // dH1 [KG1][BC][L1]
@@ -245,6 +247,55 @@ struct PreWave {
 // pass ended ~1.2 us after block 0's (profiles/r4_dp/dp_phases_wire16.log).
 constexpr int kRepHookLoads = 6;
 
+// All-reduce over one 16-lane DPP row (the softmax section's batch row): four
+// row_ror steps (8, 4, 2, 1), VALU only -- no LDS round trip per step as with
+// ds_bpermute shuffles.  Every lane of the row ends with the row's result.
+template <int N>
+__device__ __forceinline__ int row_ror(int v) {
+  return __builtin_amdgcn_update_dpp(0, v, 0x120 | N, 0xf, 0xf, false);
+}
+__device__ __forceinline__ float row16_max(float v) {
+  v = fmaxf(v, __int_as_float(row_ror<8>(__float_as_int(v))));
+  v = fmaxf(v, __int_as_float(row_ror<4>(__float_as_int(v))));
+  v = fmaxf(v, __int_as_float(row_ror<2>(__float_as_int(v))));
+  return fmaxf(v, __int_as_float(row_ror<1>(__float_as_int(v))));
+}
+__device__ __forceinline__ int row16_min(int v) {
+  v = min(v, row_ror<8>(v));
+  v = min(v, row_ror<4>(v));
+  v = min(v, row_ror<2>(v));
+  return min(v, row_ror<1>(v));
+}
+__device__ __forceinline__ int row16_or(int v) {
+  v |= row_ror<8>(v);
+  v |= row_ror<4>(v);
+  v |= row_ror<2>(v);
+  return v | row_ror<1>(v);
+}
+
+// The softmax section parks each batch row's (NLL, correct, counted) in the row's
+// logit slots [kStatSlot, kStatSlot + 3) of sZ (classes use slots [0, kNC)).
+// head_stats sums them over the block's 32 rows: whole-wave call (one wave), after a
+// barrier that follows the softmax section; every lane returns the totals.  Order
+// as when wave 0 held one row per lane: rows on lanes 0..31, zeros above, 64-lane
+// xor butterfly from 32 down, then added to 0.f -- the stats keep their bits.
+constexpr int kStatSlot = 12;
+struct HeadStats {
+  float loss, correct, cnt;
+};
+__device__ __forceinline__ HeadStats head_stats(const float* sZ) {
+  const int lane = threadIdx.x & 63;
+  const float4 q = ld4(sZ + (lane & 31) * 16 + kStatSlot);
+  float loss = lane < 32 ? q.x : 0.f, correct = lane < 32 ? q.y : 0.f, cnt = lane < 32 ? q.z : 0.f;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    loss += __shfl_xor(loss, off, 64);
+    correct += __shfl_xor(correct, off, 64);
+    cnt += __shfl_xor(cnt, off, 64);
+  }
+  return HeadStats{0.f + loss, 0.f + correct, 0.f + cnt};
+}
+
 template <int BC, int L1, int L2, bool MULTI, bool REP, class Hook = NoHook>
 __device__ __forceinline__ void head_body(const MLP3Args& a, char* smem, RepPre* pre = nullptr,
                                           const Hook& hook = Hook{}) {
@@ -259,7 +310,6 @@ __device__ __forceinline__ void head_body(const MLP3Args& a, char* smem, RepPre*
   __bf16* sdZ = (__bf16*)(smem + C::odZ);
   __bf16* sdZT = (__bf16*)(smem + C::odZT);
   int* sY = (int*)(smem + C::oY);
-  float* misc = (float*)(smem + C::oMisc);
   float* sBias = (float*)(smem + C::oBias);
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r16 = lane & 15, g = lane >> 4;
@@ -295,10 +345,7 @@ __device__ __forceinline__ void head_body(const MLP3Args& a, char* smem, RepPre*
     const int64_t bgi = bt < L1 ? O::B1 + bt : (bt < L1 + L2 ? O::B2 + (bt - L1) : O::B3 + (bt - L1 - L2));
     bias_v = P[bgi];
   }
-  if (tid == 0) {
-    misc[0] = 0.f; misc[1] = 0.f; misc[2] = 0.f;
-    if (stamp_ok) a.stamps[0] = __builtin_amdgcn_s_memrealtime();
-  }
+  if (stamp_ok) a.stamps[0] = __builtin_amdgcn_s_memrealtime();
   // the tail of this step accumulates the next step's H1pre into the other slot;
   // in fragment order this block's rows are one contiguous BC * L1 range
   if constexpr (!REP) {
@@ -539,56 +586,56 @@ __device__ __forceinline__ void head_body(const MLP3Args& a, char* smem, RepPre*
       }
     }
 
-    // ---------------- log_softmax / NLL / accuracy / dZ (one row per lane) -------------
-    if (w < (BC + 63) / 64) {
-      const int r = w * 64 + lane;
-      float loss = 0.f, correct = 0.f, cnt = 0.f;
-      bf16x8 d8[2];
-      d8[0] = zero8();
-      d8[1] = zero8();
-      const int y = (r < BC) ? sY[r] : -1;
-      if (y >= 0) {
-        float z[kNC];
-        float m = -INFINITY;
-        int arg = 0;
-#pragma unroll
-        for (int j = 0; j < kNC; ++j) {
-          z[j] = sZ[r * 16 + j];
-          if (z[j] > m) { m = z[j]; arg = j; }
-        }
-        float sum = 0.f, pr[kNC], zy = 0.f;
-#pragma unroll
-        for (int j = 0; j < kNC; ++j) {
-          pr[j] = __expf(z[j] - m);
-          sum += pr[j];
-          zy = (j == y) ? z[j] : zy;
-        }
+    // ---------------- log_softmax / NLL / accuracy / dZ ----------------
+    // One (row, class slot) element per thread: tid -> (r = tid / 16, j = tid % 16),
+    // so a wave covers 4 rows and a row is one 16-lane DPP row.  (One row per lane of
+    // wave 0 -- 10 serial exps, 16 scalar dZ^T writes, then the loss butterfly -- kept
+    // seven waves at the next barrier for ~1 us, profiles/r6_h1copies.)  Same bits as
+    // the row-per-lane form: the row maximum is exact in any order, the arg-max is the
+    // lowest index that attains it, every lane computes its own exp once, and the row
+    // sum is added in class order j = 0..9 from 0.f by every lane of the row (the exps
+    // go through sZ, whose rows 4w..4w+3 only this wave touches).  Slots j >= 10 and
+    // rows without a label write zeros.  The per-row loss / correct / count are parked
+    // in the row's unused logit slots; head_stats reduces them off this path.
+    {
+      static_assert(BC * 16 == kThreads && kNC <= kStatSlot, "one (row, class slot) per thread");
+      const int r = tid >> 4, j = tid & 15;
+      const int y = sY[r];
+      const bool cls = j < kNC;
+      const float zl = sZ[r * 16 + j];  // slots >= kNC were never written: selected away
+      const float z = cls ? zl : -INFINITY;
+      const float m = row16_max(z);
+      const int arg = row16_min(cls && z == m ? j : 16);
+      // the label's logit: the bits of at most one lane of the row (0.f if none)
+      const float zy = __int_as_float(row16_or(cls && j == y ? __float_as_int(z) : 0));
+      const float p = __expf(z - m);
+      if (cls) sZ[r * 16 + j] = p;
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      const float4 pa = ld4(sZ + r * 16), pb = ld4(sZ + r * 16 + 4);
+      const float2 pc = *reinterpret_cast<const float2*>(sZ + r * 16 + 8);
+      static_assert(kNC == 10, "row sum below");
+      __bf16 d = (__bf16)0.f;
+      {
+#pragma clang fp contract(off)
+        float sum = 0.f;
+        sum += pa.x; sum += pa.y; sum += pa.z; sum += pa.w;
+        sum += pb.x; sum += pb.y; sum += pb.z; sum += pb.w;
+        sum += pc.x; sum += pc.y;
         const float inv = 1.f / sum;
-        loss = m + __logf(sum) - zy;
-        correct = (arg == y) ? 1.f : 0.f;
-        cnt = 1.f;
-#pragma unroll
-        for (int j = 0; j < kNC; ++j) d8[j >> 3][j & 7] = (__bf16)((pr[j] * inv - (j == y ? 1.f : 0.f)) * invB);
+        if (y >= 0 && cls) d = (__bf16)(fmaf(p, inv, -(j == y ? 1.f : 0.f)) * invB);
+        if (j == 0) {
+          const bool ok = y >= 0;
+          float* st = sZ + r * 16 + kStatSlot;
+          st[0] = ok ? (m + __logf(sum)) - zy : 0.f;
+          st[1] = ok && arg == y ? 1.f : 0.f;
+          st[2] = ok ? 1.f : 0.f;
+        }
       }
-      if (r < BC) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q) *reinterpret_cast<bf16x8*>(sdZ + r * kDZS + 8 * q) = d8[q];
-        *reinterpret_cast<bf16x8*>(sdZ + r * kDZS + 16) = zero8();
-        *reinterpret_cast<bf16x8*>(sdZ + r * kDZS + 24) = zero8();
-#pragma unroll
-        for (int j = 0; j < 16; ++j) sdZT[j * C::TS + r] = (j < kNC) ? d8[j >> 3][j & 7] : (__bf16)0.f;
-      }
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        loss += __shfl_xor(loss, off, 64);
-        correct += __shfl_xor(correct, off, 64);
-        cnt += __shfl_xor(cnt, off, 64);
-      }
-      if (lane == 0) {
-        atomicAdd(&misc[0], loss);
-        atomicAdd(&misc[1], correct);
-        atomicAdd(&misc[2], cnt);
-      }
+      sdZ[r * kDZS + j] = d;
+      sdZ[r * kDZS + 16 + j] = (__bf16)0.f;
+      sdZT[j * C::TS + r] = d;
     }
     __syncthreads();
     if constexpr (!REP) copy_rows(sdZT, 16, A::DZT, row0);
@@ -666,12 +713,14 @@ __device__ __forceinline__ void head_body(const MLP3Args& a, char* smem, RepPre*
     __syncthreads();
     if (stamp_ok) a.stamps[3] = __builtin_amdgcn_s_memrealtime();
   }
-  if constexpr (REP) return;  // loss stats stay in misc[0..3); block 0 publishes them
+  if constexpr (REP) return;  // the rows' loss stats stay parked in sZ; block 0 reduces and publishes them
+  if (w != 0) return;
+  const HeadStats hs = head_stats(sZ);  // here, where they are consumed: off the path to the dH2 barrier
   if (tid == 0 && nchunks > 1) {
     // several row blocks: partial sums for tail block 0's ordered reduction
-    a.head_part[c * 4 + 0] = misc[0];
-    a.head_part[c * 4 + 1] = misc[1];
-    a.head_part[c * 4 + 2] = misc[2];
+    a.head_part[c * 4 + 0] = hs.loss;
+    a.head_part[c * 4 + 1] = hs.correct;
+    a.head_part[c * 4 + 2] = hs.cnt;
   }
   if (tid == 0 && c == 0) {
     // the advanced state goes to the NEXT copy: this launch's gather blocks are
@@ -687,9 +736,9 @@ __device__ __forceinline__ void head_body(const MLP3Args& a, char* smem, RepPre*
     if (a.stats && nchunks == 1) {
       const int s = (int)((t - 1) % (a.stats_ring > 0 ? a.stats_ring : 1));
       float* st = a.stats + s * 4;
-      st[0] = misc[0] * invB;
-      st[1] = misc[1];
-      st[2] = misc[2];
+      st[0] = hs.loss * invB;
+      st[1] = hs.correct;
+      st[2] = hs.cnt;
       st[3] = (float)t;
     }
     if (a.stamps) a.stamps[4] = __builtin_amdgcn_s_memrealtime();
@@ -1909,11 +1958,13 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args a) {
     stamp_max(a, 6);  // probe builds: the latest small-parameter block end
   } else {
     // block 0: stats, the consumed H1pre slot zeroed (the invariant), then the advanced state
+    // the rows' parked loss stats, summed by wave 0 before it polls for the acks
+    HeadStats hs{0.f, 0.f, 0.f};
+    if (w == 0) hs = head_stats((const float*)(smem + C::oZ));
     one_wait_acks(a, seq, &sh_fail);
     uint4* z = reinterpret_cast<uint4*>(a.h1pre + slot * H1Copies<L1>::G * (int64_t)Bp * L1);
     for (int i = tid; i < H1Copies<L1>::G * Bp * L1 / 4; i += kThreads) z[i] = make_uint4(0u, 0u, 0u, 0u);
     if (tid == 0) {
-      const float* misc = (const float*)(smem + C::oMisc);
       const int64_t t = c0 + 1;
       int64_t nc = cursor + 1, nob = ob;
       if (nc >= a.n_batches) { nc = 0; nob ^= 1; }
@@ -1922,9 +1973,9 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args a) {
       a.counters[kSeq] = seq + 1;
       if (a.stats) {
         float* sr = a.stats + (int)((t - 1) % (a.stats_ring > 0 ? a.stats_ring : 1)) * 4;
-        sr[0] = misc[0] * (1.f / (float)B);
-        sr[1] = misc[1];
-        sr[2] = misc[2];
+        sr[0] = hs.loss * (1.f / (float)B);
+        sr[1] = hs.correct;
+        sr[2] = hs.cnt;
         sr[3] = (float)t;
       }
       if (a.stamps) a.stamps[4] = __builtin_amdgcn_s_memrealtime();
