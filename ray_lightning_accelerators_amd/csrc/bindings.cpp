@@ -843,6 +843,92 @@ std::vector<Tensor> conv3x3_stats(Tensor x, Tensor w, int64_t N, int64_t H, int6
   return conv3x3_impl(x, w, N, H, W, Cin, Cout, false, true, pre_ss, nbt_inc);
 }
 
+// 3x3 / stride 2 / pad 1 NHWC bf16 convolution forward (csrc/conv3x3s2.hip): x [N, H, W, Cin]
+// and w [Cout, 3, 3, Cin] as contiguous memory; returns y as contiguous [N, OH, OW, Cout].
+// stats: also the next BatchNorm's partial sums of bf16(y) -> {y, part [rows, 2, Cout]}
+rla::Conv3x3S2Geom conv3x3s2_full_geom(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout) {
+  rla::Conv3x3S2Geom g = rla::conv3x3s2_geom((int)N, (int)H, (int)W, (int)Cin, (int)Cout);
+  // vrows walks every tile of the partition and is a function of (N, H, W, wpb) alone (a
+  // pinned plan CU count changes wpb, hence the key): the last few answers are kept, a
+  // model has a handful of such layers
+  struct Slot {
+    int64_t n, h, w;
+    int wpb, vrows;
+  };
+  static Slot slots[16];
+  static int used = 0, next = 0;
+  static std::mutex mu;
+  std::lock_guard<std::mutex> lk(mu);
+  for (int i = 0; i < used; ++i)
+    if (slots[i].n == N && slots[i].h == H && slots[i].w == W && slots[i].wpb == g.wpb) {
+      g.vrows = slots[i].vrows;
+      return g;
+    }
+  g.vrows = rla::conv3x3s2_vrows(g);
+  slots[next] = Slot{N, H, W, g.wpb, g.vrows};
+  next = (next + 1) % 16;
+  if (used < 16) ++used;
+  return g;
+}
+
+// the arguments a geometry can be built from (int ranges; Cout % 64 before conv3x3_wpb divides by Cout / 64)
+bool conv3x3s2_args_ok(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout) {
+  return N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cout % 64 == 0 && Cin < (int64_t(1) << 30) &&
+         Cout < (int64_t(1) << 30) && N * (H + 2) * (W + 2) < (int64_t(1) << 30);
+}
+
+bool conv3x3s2_supported(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout) {
+  return conv3x3s2_args_ok(N, H, W, Cin, Cout) && rla::conv3x3s2_ok(conv3x3s2_full_geom(N, H, W, Cin, Cout));
+}
+
+std::vector<Tensor> conv3x3s2_impl(Tensor x, Tensor w, int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout,
+                                   bool stats) {
+  TORCH_CHECK(x.is_cuda() && w.is_cuda(), "conv3x3s2: GPU tensors");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16, "conv3x3s2: bf16 inputs");
+  TORCH_CHECK(x.is_contiguous() && w.is_contiguous(), "conv3x3s2: contiguous NHWC / [Cout,3,3,Cin] memory");
+  TORCH_CHECK(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv3x3s2: bad geometry");
+  TORCH_CHECK(x.numel() == N * H * W * Cin, "conv3x3s2: x has ", x.numel(), " elements");
+  TORCH_CHECK(w.numel() == Cout * 9 * Cin, "conv3x3s2: w has ", w.numel(), " elements");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+              "conv3x3s2: 16-byte aligned inputs");
+  TORCH_CHECK(conv3x3s2_args_ok(N, H, W, Cin, Cout), "conv3x3s2: unsupported shape (Cout % 64, size)");
+  const at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  const rla::Conv3x3S2Geom g = conv3x3s2_full_geom(N, H, W, Cin, Cout);  // once per launch
+  TORCH_CHECK(rla::conv3x3s2_ok(g), "conv3x3s2: unsupported shape (Cin % 16, Cout % 64, halo tile size)");
+  Tensor y = at::empty({N, g.OH, g.OW, Cout}, x.options());
+  Tensor part;
+  if (stats) part = at::empty({g.wpb, 2, Cout}, x.options().dtype(at::kFloat));
+  TORCH_CHECK(rla::launch_conv3x3s2(reinterpret_cast<const uint16_t*>(x.data_ptr()),
+                                    reinterpret_cast<const uint16_t*>(w.data_ptr()),
+                                    reinterpret_cast<uint16_t*>(y.data_ptr()), g, cur_stream(x),
+                                    stats ? part.data_ptr<float>() : nullptr),
+              "conv3x3s2: launch refused");
+  if (stats) return {y, part};
+  return {y};
+}
+
+Tensor conv3x3s2(Tensor x, Tensor w, int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout) {
+  return conv3x3s2_impl(x, w, N, H, W, Cin, Cout, false)[0];
+}
+
+std::vector<Tensor> conv3x3s2_stats(Tensor x, Tensor w, int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout) {
+  return conv3x3s2_impl(x, w, N, H, W, Cin, Cout, true);
+}
+
+// Read-only plan query (tests): what a conv3x3s2 / conv3x3s2_stats launch would run under the
+// current plan CU count.  Workgroup j of an output-channel block owns output pixels
+// [M j / wpb, M (j + 1) / wpb) of M = N OH OW, in tiles of tm from its start, and writes part row j.
+// Returns (tm, wpb, vrows, pieces_per_thread, nx, fixed, OH, OW); fixed is 0: the one instance
+// takes its shape at run time, and stats changes the epilogue only
+std::vector<int64_t> conv3x3s2_plan(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout, bool stats) {
+  (void)stats;
+  TORCH_CHECK(conv3x3s2_args_ok(N, H, W, Cin, Cout), "conv3x3s2_plan: unsupported shape");
+  const rla::Conv3x3S2Geom g = conv3x3s2_full_geom(N, H, W, Cin, Cout);
+  TORCH_CHECK(rla::conv3x3s2_ok(g), "conv3x3s2_plan: unsupported shape");
+  return {rla::conv3x3s2_tm(), g.wpb, g.vrows, rla::conv3x3s2_pieces_per_thread(g), rla::conv3x3s2_nx(), 0,
+          g.OH, g.OW};
+}
+
 // ResNet stem forward: x [N, H, W, 3] NHWC bf16, w [64, 7, 7, 3] bf16 -> {y [N, OH, OW, 64]} or, with
 // stats, {y, part [rows, 2, 64]} (the next BatchNorm's partial sums of bf16(y))
 std::vector<Tensor> stem_fwd(Tensor x, Tensor w, bool stats) {
@@ -1026,6 +1112,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("w"), py::arg("N"), py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"),
         py::arg("pre_ss") = py::none(), py::arg("nbt_inc") = py::none());
   m.def("conv3x3_supported", &conv3x3_supported, "shapes the 3x3 MFMA convolution covers");
+  m.def("conv3x3s2", &conv3x3s2, "3x3 / stride 2 / pad 1 NHWC bf16 convolution on MFMA -> [N, OH, OW, Cout]",
+        py::arg("x"), py::arg("w"), py::arg("N"), py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"));
+  m.def("conv3x3s2_stats", &conv3x3s2_stats,
+        "3x3 / stride 2 / pad 1 forward + BatchNorm partial sums of its bf16 output -> (y, part [rows, 2, Cout])",
+        py::arg("x"), py::arg("w"), py::arg("N"), py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"));
+  m.def("conv3x3s2_supported", &conv3x3s2_supported, "shapes the 3x3 stride-2 MFMA convolution covers");
+  m.def("conv3x3s2_plan", &conv3x3s2_plan,
+        "the 3x3 stride-2 kernel's (tm, wpb, vrows, pieces_per_thread, nx, fixed, OH, OW)", py::arg("N"),
+        py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"), py::arg("stats") = false);
   m.def("stem_fwd", &stem_fwd, "ResNet stem 7x7/s2 conv (3 -> 64) on MFMA [+ BatchNorm partial sums]");
   m.def("stem_supported", &stem_supported, "input shapes the stem kernel covers");
   m.def("stem_wgrad", &stem_wgrad, "ResNet stem weight gradient on MFMA -> fp32 [64, 7, 7, 3] (channels_last order)");

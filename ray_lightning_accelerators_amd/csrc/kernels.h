@@ -346,6 +346,25 @@ bool launch_conv3x3(const uint16_t* x, const uint16_t* w, uint16_t* y, const Con
                     hipStream_t stream, float* part = nullptr, const float* pre_ss = nullptr,
                     int64_t* nbt_inc = nullptr);
 
+// 3x3 / stride 2 / pad 1 NHWC bf16 convolution forward on MFMA (csrc/conv3x3s2.hip):
+// y [N, OH, OW, Cout] = conv(x [N, H, W, Cin], w [Cout][3][3][Cin]), OH = (H - 1) / 2 + 1,
+// OW = (W - 1) / 2 + 1.  Cin % 16 == 0, Cout % 64 == 0.
+struct Conv3x3S2Geom {
+  int N, H, W, Cin, Cout, OH, OW;
+  int vrows;  // halo rows of the largest pixel tile (conv3x3s2_vrows)
+  int wpb;    // workgroups per 64-channel output block = contiguous output-pixel ranges
+};
+// (N .. OW, wpb = conv3x3_wpb over the OUTPUT pixels under the current plan_cus(); vrows left 0)
+Conv3x3S2Geom conv3x3s2_geom(int N, int H, int W, int Cin, int Cout);
+int conv3x3s2_vrows(const Conv3x3S2Geom& g);
+int conv3x3s2_pieces_per_thread(const Conv3x3S2Geom& g);  // 16-byte halo pieces per thread and chunk
+int conv3x3s2_tm();  // output pixels per workgroup tile
+int conv3x3s2_nx();  // halo pieces per thread the kernel is compiled for
+bool conv3x3s2_ok(const Conv3x3S2Geom& g);
+// part (or null): BatchNorm partial sums of bf16(y), [g.wpb][2][Cout] fp32
+bool launch_conv3x3s2(const uint16_t* x, const uint16_t* w, uint16_t* y, const Conv3x3S2Geom& g,
+                      hipStream_t stream, float* part = nullptr);
+
 // ResNet stem: 7x7 / stride 2 / pad 3 convolution, 3 -> 64 channels, NHWC bf16 (csrc/stem.hip);
 // part (or null): BatchNorm partial sums of bf16(y), [stem_grid(g)][2][64] fp32
 struct StemGeom {

@@ -72,8 +72,9 @@ class Bottleneck(nn.Module):
 
     @staticmethod
     def _conv_bn(conv, bn, x, **kw):
-        """bn(conv(x)): a stride-1 1x1 or 3x3 conv may compute bn's batch statistics in
-        its epilogue (ops.conv.BNStats; bn then skips its partial pass over the output)."""
+        """bn(conv(x)): a stride-1 1x1 conv or a 3x3 conv of stride 1 or 2 may compute bn's
+        batch statistics in its epilogue (ops.conv.BNStats; bn then skips its partial pass
+        over the output)."""
         fork = kw.pop("fork", None)
         if isinstance(conv, (Conv1x1NHWC, ConvBF16)) and bn.training:
             st = BNStats()

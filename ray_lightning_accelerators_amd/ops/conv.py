@@ -274,6 +274,54 @@ def conv3x3_dgrad_hip(dy: torch.Tensor, wb: torch.Tensor) -> torch.Tensor:
     return dx.permute(0, 3, 1, 2)
 
 
+def conv3x3s2_ok(x: torch.Tensor, wb: torch.Tensor, stride, padding) -> bool:
+    """3x3 / stride 2 / pad 1 forwards the MFMA kernel covers (csrc/conv3x3s2.hip): bf16
+    channels_last operands on the GPU, Cin % 16 == 0, Cout % 64 == 0 and a tile halo that
+    fits its LDS image.  ``RLA_CONV3X3=off`` turns this kernel off too."""
+    if tuple(wb.shape[2:]) != (3, 3) or tuple(stride) != (2, 2) or tuple(padding) != (1, 1):
+        return False
+    if not x.is_cuda or os.environ.get("RLA_CONV3X3", "auto") == "off":
+        return False
+    n, cin, h, w = x.shape
+    cout = wb.size(0)
+    return (cin % 16 == 0 and cout % 64 == 0 and x.dtype == torch.bfloat16 and wb.dtype == torch.bfloat16
+            and x.is_contiguous(memory_format=torch.channels_last)
+            and wb.is_contiguous(memory_format=torch.channels_last)
+            and x.data_ptr() % 16 == 0 and wb.data_ptr() % 16 == 0
+            and _conv3x3s2_shape_ok(n, h, w, cin, cout))
+
+
+def _conv3x3s2_shape_ok(n: int, h: int, w: int, cin: int, cout: int) -> bool:
+    # not cached here: the answer follows the work split, hence the planning CU count
+    # (set_plan_cus); the binding keeps the partition walk of the last shapes itself
+    from . import require
+
+    return bool(require().conv3x3s2_supported(n, h, w, cin, cout))
+
+
+def conv3x3s2_hip(x: torch.Tensor, wb: torch.Tensor) -> torch.Tensor:
+    """``conv2d(x, wb, stride=2, padding=1)`` on the MFMA kernel: ``x`` [N, Cin, H, W]
+    channels_last bf16, ``wb`` [Cout, Cin, 3, 3] channels_last bf16; returns
+    [N, Cout, (H - 1) // 2 + 1, (W - 1) // 2 + 1] channels_last."""
+    from . import require
+
+    n, cin, h, w = x.shape
+    cout = wb.size(0)
+    y = require().conv3x3s2(x.permute(0, 2, 3, 1), wb.permute(0, 2, 3, 1), n, h, w, cin, cout)
+    return y.permute(0, 3, 1, 2)
+
+
+def conv3x3s2_stats_hip(x: torch.Tensor, wb: torch.Tensor):
+    """:func:`conv3x3s2_hip` plus the per-channel partial sums of its bf16 output from the
+    epilogue (csrc/conv3x3s2.hip ST): returns (y channels_last, part [rows, 2, Cout])."""
+    from . import require
+
+    n, cin, h, w = x.shape
+    cout = wb.size(0)
+    y, part = require().conv3x3s2_stats(x.permute(0, 2, 3, 1), wb.permute(0, 2, 3, 1), n, h, w, cin, cout)
+    return y.permute(0, 3, 1, 2), part
+
+
 def _nhwc2d(t: torch.Tensor) -> torch.Tensor:
     n, c, h, w = t.shape
     return t.permute(0, 2, 3, 1).reshape(n * h * w, c)
@@ -529,7 +577,8 @@ class Conv1x1NHWC(nn.Conv2d):
 
 class _ConvNHWCFn(torch.autograd.Function):
     """KxK (or strided) bf16 NHWC convolution: MIOpen or, for 3x3 / stride 1 / pad 1, the
-    MFMA kernels for the forward and dgrad; the weight gradient from MIOpen or the MFMA
+    MFMA kernels for the forward and dgrad, for 3x3 / stride 2 / pad 1 the MFMA forward
+    (its dgrad is MIOpen's); the weight gradient from MIOpen or the MFMA
     kernel (``wgrad_hip``); each picked per shape on device time.  The weight gradient
     reaches the fp32 master weight in fp32."""
 
@@ -543,8 +592,21 @@ class _ConvNHWCFn(torch.autograd.Function):
             # forward stages the activation itself (conv_nhwc chose this path: 3x3 /
             # stride 1 / pad 1, no fork)
             y, bn_stats.part = conv3x3_stats_hip(x, wb, pre)
+        elif not ctx.c3 and conv3x3s2_ok(x, wb, stride, padding):
+            # 3x3 / stride 2 / pad 1 (ResNet's downsample conv2): the stride-2 MFMA forward
+            # against the library; the gradients below are those of any strided layer
+            key = (x.size(0) * x.size(2) * x.size(3), x.size(1), wb.size(0), 3, 3, 2, 1)
+            if (bn_stats is not None and conv3x3_stats_enabled()
+                    and not torch.are_deterministic_algorithms_enabled()):
+                cands["hip_st"] = lambda: conv3x3s2_stats_hip(x, wb)
+                y = _run_stats("fwd_kxk_st", key, cands, "hip_st", bn_stats)
+            else:
+                # deterministic mode too: _pick's fixed order lands on "hip" (bitwise
+                # reproducible) and the BatchNorm makes its own pass
+                cands["hip"] = lambda: conv3x3s2_hip(x, wb)
+                y = _run("fwd_kxk", key, cands)
         elif not ctx.c3:
-            y = cands["miopen"]()  # the only backend of a strided or non-3x3 forward
+            y = cands["miopen"]()  # the only backend of any other strided or non-3x3 forward
         else:
             key = (x.size(0) * x.size(2) * x.size(3), x.size(1), wb.size(0), 3, 3, 1, 1)
             if bn_stats is not None and conv3x3_stats_enabled():
@@ -710,7 +772,7 @@ def conv_nhwc(x: torch.Tensor, conv: nn.Conv2d, wb: torch.Tensor, fork: Optional
               bn_stats: Optional[BNStats] = None) -> torch.Tensor:
     """``conv(x)`` with the bf16 weight ``wb`` (the arena shadow), the weight gradient
     going to ``conv.weight`` in fp32 (``fork``: see :class:`GradFork`; ``bn_stats``:
-    see :class:`BNStats`, filled only by the 3x3 stride-1 MFMA forward)."""
+    see :class:`BNStats`, filled only by the 3x3 MFMA forwards, stride 1 or 2)."""
     pre = getattr(x, "_rla_pre", None)
     if pre is not None:
         # a deferred BatchNorm + ReLU output (ops/bn.py DeferredApply): the 3x3 statistics

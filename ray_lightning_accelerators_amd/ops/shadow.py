@@ -69,8 +69,8 @@ class ConvBF16(nn.Conv2d):
 
     def forward(self, x: torch.Tensor, fork=None, bn_stats=None) -> torch.Tensor:
         """``fork``: an ops.conv.GradFork shared with another consumer of ``x`` (fast path only).
-        ``bn_stats``: an ops.conv.BNStats the 3x3 MFMA forward may fill (the next
-        BatchNorm's batch statistics from its epilogue)."""
+        ``bn_stats``: an ops.conv.BNStats the 3x3 MFMA forward (stride 1 or 2) may fill
+        (the next BatchNorm's batch statistics from its epilogue)."""
         if getattr(x, "_rla_pre", None) is not None:
             # a deferred BatchNorm + ReLU output (ops/bn.py DeferredApply): only conv_nhwc
             # understands it -- every other path gets the materialised activation

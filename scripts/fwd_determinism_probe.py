@@ -1,7 +1,9 @@
 """Which layer of the fused ResNet-50 forward is not bitwise reproducible?  Runs the
 same training-mode forward (same weights, same batch, backends already picked) twice
 and reports, in forward order, every module whose output differs, with the backend
-choices of the convolutions -- one JSON line per differing module, then a summary."""
+choices of the convolutions -- one JSON line per differing module, then a summary.
+``BATCH=n`` sets the batch size (default 32), ``DETERMINISTIC=1`` runs under
+``torch.use_deterministic_algorithms(True, warn_only=True)``."""
 import json
 import os
 import sys
@@ -18,6 +20,9 @@ from ray_lightning_accelerators_amd.parallel.arena import ParamArena  # noqa: E4
 
 def main():
     B = int(os.environ.get("BATCH", "32"))
+    deterministic = os.environ.get("DETERMINISTIC", "0") == "1"
+    if deterministic:  # what Trainer(deterministic=True) sets: the fixed backend order of ops/conv.py _pick
+        torch.use_deterministic_algorithms(True, warn_only=True)
     dev = torch.device("cuda", 0)
     torch.backends.cudnn.benchmark = True
     torch.manual_seed(0)
@@ -63,7 +68,7 @@ def main():
                               "numel": a.numel()}), flush=True)
             if bad >= 12:
                 break
-    print(json.dumps({"modules": len(order), "differing": bad, "batch": B,
+    print(json.dumps({"modules": len(order), "differing": bad, "batch": B, "deterministic": deterministic,
                       "first": next((n for n in order if not torch.equal(outs[n][0], outs[n][1])), None),
                       "picks": {k: v["pick"] for k, v in C.choices().items() if k.startswith("fwd")}}), flush=True)
 
