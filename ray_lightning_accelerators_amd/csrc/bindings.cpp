@@ -843,6 +843,68 @@ std::vector<Tensor> conv3x3_stats(Tensor x, Tensor w, int64_t N, int64_t H, int6
   return conv3x3_impl(x, w, N, H, W, Cin, Cout, false, true, pre_ss, nbt_inc);
 }
 
+// The 3x3 / stride 1 / pad 1 input gradient with the PRECEDING BatchNorm + ReLU's backward
+// in its epilogue (csrc/conv3x3.hip BWD): dy [N, H, W, Cr], w the forward weight
+// [Cr, 3, 3, Co], xb [N, H, W, Co] that BatchNorm's input, ss its [4, Co] statistics.
+// Returns {d [N, H, W, Co] = (xb * scale + shift > 0 ? dx : 0), part [rows, 2, Co]}: the
+// sums of d and d * xb over each of the plan's pixel ranges (bn_bwd_finalize's input).
+rla::Conv3x3Geom conv3x3_dgrad_geom(int64_t N, int64_t H, int64_t W, int64_t Cr, int64_t Co) {
+  rla::Conv3x3Geom g{(int)N, (int)H, (int)W, (int)Cr, (int)Co, 0,
+                     rla::conv3x3_pick_tm((int)N, (int)H, (int)W, (int)Co),
+                     rla::conv3x3_wpb((int)N, (int)H, (int)W, (int)Co)};
+  // the partition walk once per (N, H, W, tm, wpb), as conv3x3_impl keeps it
+  static std::map<std::tuple<int64_t, int64_t, int64_t, int, int>, int> vrows_cache;
+  static std::mutex mu;
+  std::lock_guard<std::mutex> lk(mu);
+  auto key = std::make_tuple(N, H, W, g.tm, g.wpb);
+  auto it = vrows_cache.find(key);
+  if (it == vrows_cache.end()) it = vrows_cache.emplace(key, rla::conv3x3_vrows(g)).first;
+  g.vrows = it->second;
+  return g;
+}
+
+bool conv3x3_dgrad_bn_ok(int64_t N, int64_t H, int64_t W, int64_t Cr, int64_t Co) {
+  // conv3x3_supported's argument checks, then conv3x3_ok and the table limit on the cached geometry
+  if (N <= 0 || H <= 0 || W <= 0 || Cr <= 0 || Co <= 0 || N * (H + 2) * (W + 2) >= (int64_t(1) << 30)) return false;
+  return rla::conv3x3_bwd_ok(conv3x3_dgrad_geom(N, H, W, Cr, Co));
+}
+
+std::vector<Tensor> conv3x3_dgrad_bn(Tensor dy, Tensor w, int64_t N, int64_t H, int64_t W, int64_t Cr, int64_t Co,
+                                     Tensor xb, Tensor ss) {
+  TORCH_CHECK(dy.is_cuda() && w.is_cuda() && xb.is_cuda(), "conv3x3_dgrad_bn: GPU tensors");
+  TORCH_CHECK(dy.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16 &&
+                  xb.scalar_type() == at::kBFloat16,
+              "conv3x3_dgrad_bn: bf16 inputs");
+  TORCH_CHECK(dy.is_contiguous() && w.is_contiguous() && xb.is_contiguous(),
+              "conv3x3_dgrad_bn: contiguous NHWC / [Cr,3,3,Co] memory");
+  TORCH_CHECK(N > 0 && H > 0 && W > 0 && Cr > 0 && Co > 0, "conv3x3_dgrad_bn: bad geometry");
+  TORCH_CHECK(dy.numel() == N * H * W * Cr, "conv3x3_dgrad_bn: dy has ", dy.numel(), " elements");
+  TORCH_CHECK(w.numel() == Cr * 9 * Co, "conv3x3_dgrad_bn: w has ", w.numel(), " elements");
+  TORCH_CHECK(xb.numel() == N * H * W * Co, "conv3x3_dgrad_bn: xb has ", xb.numel(), " elements");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(dy.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(xb.data_ptr()) % 16 == 0,
+              "conv3x3_dgrad_bn: 16-byte aligned inputs");
+  TORCH_CHECK(dy.device() == w.device() && dy.device() == xb.device(), "conv3x3_dgrad_bn: one device");
+  check_dev(ss, "ss", at::kFloat);
+  TORCH_CHECK(ss.device() == dy.device() && ss.is_contiguous() && ss.dim() == 2 && ss.size(0) == 4 &&
+                  ss.size(1) == Co,
+              "conv3x3_dgrad_bn: ss must be [4, Co] fp32");
+  TORCH_CHECK(conv3x3_dgrad_bn_ok(N, H, W, Cr, Co),
+              "conv3x3_dgrad_bn: unsupported shape (Cr % 16, Co % 64, Co <= 512, halo tile size)");
+  const at::hip::HIPGuardMasqueradingAsCUDA guard(dy.device());
+  const rla::Conv3x3Geom g = conv3x3_dgrad_geom(N, H, W, Cr, Co);
+  Tensor d = at::empty({N, H, W, Co}, dy.options());
+  Tensor part = at::empty({g.wpb, 2, Co}, dy.options().dtype(at::kFloat));
+  TORCH_CHECK(rla::launch_conv3x3(reinterpret_cast<const uint16_t*>(dy.data_ptr()),
+                                  reinterpret_cast<const uint16_t*>(w.data_ptr()),
+                                  reinterpret_cast<uint16_t*>(d.data_ptr()), g, true, cur_stream(dy),
+                                  part.data_ptr<float>(), ss.data_ptr<float>(), nullptr,
+                                  reinterpret_cast<const uint16_t*>(xb.data_ptr())),
+              "conv3x3_dgrad_bn: launch refused");
+  return {d, part};
+}
+
 // 3x3 / stride 2 / pad 1 NHWC bf16 convolution forward (csrc/conv3x3s2.hip): x [N, H, W, Cin]
 // and w [Cout, 3, 3, Cin] as contiguous memory; returns y as contiguous [N, OH, OW, Cout].
 // stats: also the next BatchNorm's partial sums of bf16(y) -> {y, part [rows, 2, Cout]}
@@ -1004,6 +1066,14 @@ std::vector<int64_t> conv3x3_plan(int64_t N, int64_t H, int64_t W, int64_t Cin, 
   return {g.tm, g.wpb, g.vrows, rla::conv3x3_pieces_per_thread(g), ins.nx, ins.fixed ? 1 : 0};
 }
 
+// conv3x3_plan's tuple for a conv3x3_dgrad_bn launch (the plain input gradient's instance choice)
+std::vector<int64_t> conv3x3_dgrad_bn_plan(int64_t N, int64_t H, int64_t W, int64_t Cr, int64_t Co) {
+  TORCH_CHECK(conv3x3_dgrad_bn_ok(N, H, W, Cr, Co), "conv3x3_dgrad_bn_plan: unsupported shape");
+  const rla::Conv3x3Geom g = conv3x3_dgrad_geom(N, H, W, Cr, Co);
+  const rla::Conv3x3Instance ins = rla::conv3x3_instance(g, false);
+  return {g.tm, g.wpb, g.vrows, rla::conv3x3_pieces_per_thread(g), ins.nx, ins.fixed ? 1 : 0};
+}
+
 // (tnw, gy, gx, tiles_per_blk, variant) of conv1x1_stats (bwd: of conv1x1_bn_bwd); variant 0 / 1:
 // weights resident beside 6 / 4 x stages, 2: streamed
 std::vector<int64_t> conv1x1_plan(int64_t M, int64_t K, int64_t N, bool bwd) {
@@ -1112,6 +1182,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("w"), py::arg("N"), py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"),
         py::arg("pre_ss") = py::none(), py::arg("nbt_inc") = py::none());
   m.def("conv3x3_supported", &conv3x3_supported, "shapes the 3x3 MFMA convolution covers");
+  m.def("conv3x3_dgrad_bn", &conv3x3_dgrad_bn,
+        "3x3 / stride 1 / pad 1 input gradient + the preceding BatchNorm + ReLU's backward mask and partial sums "
+        "-> (d [N, H, W, Co], part [rows, 2, Co])",
+        py::arg("dy"), py::arg("w"), py::arg("N"), py::arg("H"), py::arg("W"), py::arg("Cr"), py::arg("Co"),
+        py::arg("xb"), py::arg("ss"));
+  m.def("conv3x3_dgrad_bn_ok", &conv3x3_dgrad_bn_ok, "shapes conv3x3_dgrad_bn covers", py::arg("N"), py::arg("H"),
+        py::arg("W"), py::arg("Cr"), py::arg("Co"));
+  m.def("conv3x3_dgrad_bn_plan", &conv3x3_dgrad_bn_plan,
+        "conv3x3_dgrad_bn's (tm, wpb, vrows, pieces_per_thread, nx, fixed)", py::arg("N"), py::arg("H"),
+        py::arg("W"), py::arg("Cr"), py::arg("Co"));
   m.def("conv3x3s2", &conv3x3s2, "3x3 / stride 2 / pad 1 NHWC bf16 convolution on MFMA -> [N, OH, OW, Cout]",
         py::arg("x"), py::arg("w"), py::arg("N"), py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"));
   m.def("conv3x3s2_stats", &conv3x3s2_stats,

@@ -128,21 +128,40 @@ struct CvSet {
 // registers to LDS; the zero padding stays zero (the conv pads the ACTIVATION).  A
 // thread's pieces all hold channel half (tid & 1) of the stage's 16-channel chunk, so
 // each store reads 8 scales and 8 shifts from a per-workgroup LDS table.
+//
+// BWD (round 9, input gradient only): the PRECEDING BatchNorm + ReLU's backward sums in
+// the epilogue (ResNet's bn1 <- conv2, ops/bn.py).  xb [N][H][W][Cout] is that
+// BatchNorm's input and pre_ss its forward statistics; after the v_permlane32_swap a lane
+// holds 8 consecutive channels of one pixel, so one 16-byte xb load matches one 16-byte
+// store: da = bf16(acc) is the plain input gradient, d = fma(xb, scale, shift) > 0 ? da : 0
+// (bn_affine's single fused multiply-add: bitwise what the RECOMP partial / apply kernels
+// mask) is stored in its place, and the lane keeps sum d and sum d * xb of its 32 channels
+// in fp32 over all its tiles.  At the end the workgroup reduces them through LDS in ST's
+// fixed order into row jr of part [wpb][2][Cout] (bn_partial_kernel<1>'s layout, read by
+// bn_bwd_finalize): no atomics, and d does not depend on the work split.  The workgroup's
+// 64 scales and shifts sit in an LDS table.  The compile-time-shape input-gradient
+// instances have the registers for it (256-pixel tiles: 106 AGPRs before, 184 with the
+// sums), the 56x56 one with a single register stage (launch_bwd).
 constexpr int kPreMaxC = 512;
-template <int NX, bool FLIP, int JB, int DEPTH, int WC = 0, int CC = 0, bool ST = false, bool PRE = false>
+template <int NX, bool FLIP, int JB, int DEPTH, int WC = 0, int CC = 0, bool ST = false, bool PRE = false,
+          bool BWD = false>
 __global__ __launch_bounds__(kCvThreads) void conv3x3_kernel(const uint16_t* __restrict__ x,
                                                              const uint16_t* __restrict__ w,
                                                              uint16_t* __restrict__ y, Conv3x3Geom g,
                                                              float* __restrict__ part,
                                                              const float* __restrict__ pre_ss = nullptr,
-                                                             int64_t* __restrict__ nbt_inc = nullptr) {
-  static_assert(!(ST && FLIP), "statistics are a forward epilogue");
+                                                             int64_t* __restrict__ nbt_inc = nullptr,
+                                                             const uint16_t* __restrict__ xb = nullptr) {
+  static_assert(!(ST && FLIP), "the forward statistics are a forward epilogue");
   static_assert(!(PRE && FLIP), "PRE is a forward variant");
+  static_assert(!BWD || FLIP, "BWD is an input-gradient epilogue");
   constexpr int XE = x_elems(NX, WC), BE = XE + kWElems;  // halo / whole buffer elements
   static_assert(2 * BE * 2 <= 160 * 1024, "two LDS buffers fit the CU's 160 KiB");
   __shared__ __attribute__((aligned(16))) __bf16 lds[2 * BE];
   // [channel][scale, shift] interleaved: one 16-byte read covers a word's two channels
   __shared__ __attribute__((aligned(16))) float pre_tab[PRE ? 2 * kPreMaxC : 4];
+  // BWD: this workgroup's 64 output channels, [scale | shift]
+  __shared__ __attribute__((aligned(16))) float bwd_tab[BWD ? 2 * kTN : 4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (WC) g.W = WC;
   if (CC) g.Cin = CC;
@@ -174,6 +193,14 @@ __global__ __launch_bounds__(kCvThreads) void conv3x3_kernel(const uint16_t* __r
   const int nblk = (int)blockIdx.x % tiles_n, jr = (int)blockIdx.x / tiles_n;
   const int64_t p_lo = M * jr / g.wpb, p_hi = M * (jr + 1) / g.wpb;  // this workgroup's pixels
   const int ntiles = (int)((p_hi - p_lo + TM - 1) / TM);
+  if constexpr (BWD) {
+    if (ntiles == 0) {  // an empty range sums to exactly zero (uniform)
+      if (tid < 2 * kTN) part[((int64_t)jr * 2 + (tid >> 6)) * g.Cout + nblk * kTN + (tid & 63)] = 0.f;
+      return;
+    }
+    // visible to every thread before the first epilogue (the prologue's barrier follows it)
+    if (tid < 2 * kTN) bwd_tab[tid] = pre_ss[(2 + (tid >> 6)) * g.Cout + nblk * kTN + (tid & 63)];
+  }
   if (ntiles == 0) return;
   const int nchunks = g.Cin / kKC;
   const int nst = ntiles * nchunks;
@@ -324,7 +351,8 @@ __global__ __launch_bounds__(kCvThreads) void conv3x3_kernel(const uint16_t* __r
   // the straight form waited lgkmcnt(0) before every tap's MFMAs).  Not in the 512-pixel
   // statistics instances: their second fragment set spilled (172 B of scratch per lane
   // at 56x56, forward + statistics 65.6 -> 94.4 us).
-  constexpr bool kPipe = !(ST && JB == 4);
+  // (nor in the 512-pixel BWD instances: 12-212 B of scratch per lane with it)
+  constexpr bool kPipe = !((ST || BWD) && JB == 4);
   auto fetch = [&](const __bf16* X, const __bf16* Wt, int tap, bf16x8 (&fa)[2], bf16x8 (&fb)[JB]) {
     const int r = tap / 3, s = tap - (tap / 3) * 3;
     const int toff = r * RS + s * kRow;
@@ -350,11 +378,15 @@ __global__ __launch_bounds__(kCvThreads) void conv3x3_kernel(const uint16_t* __r
         const int r = tap / 3, s = tap - (tap / 3) * 3;
         const int toff = r * RS + s * kRow;
         bf16x8 a[2], b[JB];
+        if constexpr (FLIP) {
+          fetch(X, Wt, tap, a, b);
+        } else {
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
-          a[i] = *reinterpret_cast<const bf16x8*>(Wt + (tap * kTN + i * 32 + (lane & 31)) * kRow + kg);
+          for (int i = 0; i < 2; ++i)
+            a[i] = *reinterpret_cast<const bf16x8*>(Wt + (tap * kTN + i * 32 + (lane & 31)) * kRow + kg);
 #pragma unroll
-        for (int j = 0; j < JB; ++j) b[j] = *reinterpret_cast<const bf16x8*>(X + bpos[j] + toff);
+          for (int j = 0; j < JB; ++j) b[j] = *reinterpret_cast<const bf16x8*>(X + bpos[j] + toff);
+        }
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -378,8 +410,9 @@ __global__ __launch_bounds__(kCvThreads) void conv3x3_kernel(const uint16_t* __r
   };
 
   // ST: this lane's channel sums [i][4 q + e] (channel i 32 + 8 q + 4 (lane >> 5) + e)
+  // BWD: [i][8 p + e] (channel i 32 + 16 p + 8 (lane >> 5) + e), bs = sum d, bq = sum d * xb
   float bs[2][16], bq[2][16];
-  if constexpr (ST) {
+  if constexpr (ST || BWD) {
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -400,6 +433,16 @@ __global__ __launch_bounds__(kCvThreads) void conv3x3_kernel(const uint16_t* __r
       // half (lane >> 5) channels 16 p + 8 (lane >> 5) .. + 8: 16-byte stores
       const bool ok = m < m_end;
       uint16_t* yo = y + (ok ? m : 0) * g.Cout + co0 + 8 * (lane >> 5);
+      // BWD: the BatchNorm input of this lane's 4 x 8 channels (unconditional: a lane past
+      // the tile reads pixel 0), in flight while the accumulators are rounded and swapped
+      u32x4 xv[BWD ? 2 : 1][BWD ? 2 : 1];
+      if constexpr (BWD) {
+        const uint16_t* xo = xb + (ok ? m : 0) * g.Cout + co0 + 8 * (lane >> 5);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int p = 0; p < 2; ++p) xv[i][p] = *reinterpret_cast<const u32x4*>(xo + 32 * i + 16 * p);
+      }
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         uint32_t v[4][2];
@@ -426,7 +469,37 @@ __global__ __launch_bounds__(kCvThreads) void conv3x3_kernel(const uint16_t* __r
         for (int p = 0; p < 2; ++p) {
           const auto s0 = __builtin_amdgcn_permlane32_swap(v[2 * p][0], v[2 * p + 1][0], false, false);
           const auto s1 = __builtin_amdgcn_permlane32_swap(v[2 * p][1], v[2 * p + 1][1], false, false);
-          const u32x4 o = {s0[0], s1[0], s0[1], s1[1]};
+          u32x4 o = {s0[0], s1[0], s0[1], s1[1]};
+          if constexpr (BWD) {
+            // word wd = channels 2 wd, 2 wd + 1 of the lane's 8; the coefficients read per
+            // word pair (few temporaries: every accumulator is still live)
+            const float* t = bwd_tab + 32 * i + 16 * p + 8 * (lane >> 5);
+            const u32x4 xw = xv[BWD ? i : 0][BWD ? p : 0];
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf) {
+              const float4 sc = *reinterpret_cast<const float4*>(t + 4 * hf);
+              const float4 sf = *reinterpret_cast<const float4*>(t + kTN + 4 * hf);
+              const float scv[4] = {sc.x, sc.y, sc.z, sc.w}, sfv[4] = {sf.x, sf.y, sf.z, sf.w};
+#pragma unroll
+              for (int u = 0; u < 2; ++u) {
+                const int wd = 2 * hf + u;
+                const uint32_t xwd = xw[wd], dwd = o[wd];
+                uint32_t keep = 0u;
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                  const float xf = __uint_as_float(h ? xwd & 0xFFFF0000u : xwd << 16);
+                  const bool on = __builtin_fmaf(xf, scv[2 * u + h], sfv[2 * u + h]) > 0.f;  // bn_affine
+                  const float df = on ? __uint_as_float(h ? dwd & 0xFFFF0000u : dwd << 16) : 0.f;
+                  keep |= on ? (h ? 0xFFFF0000u : 0x0000FFFFu) : 0u;
+                  if (ok) {  // the sums of what the BatchNorm backward reads
+                    bs[i][8 * p + 2 * wd + h] += df;
+                    bq[i][8 * p + 2 * wd + h] = __builtin_fmaf(df, xf, bq[i][8 * p + 2 * wd + h]);
+                  }
+                }
+                o[wd] = dwd & keep;
+              }
+            }
+          }
           if (ok) *reinterpret_cast<u32x4*>(yo + 32 * i + 16 * p) = o;
         }
       }
@@ -464,10 +537,11 @@ __global__ __launch_bounds__(kCvThreads) void conv3x3_kernel(const uint16_t* __r
 #pragma unroll
     for (int d = 0; d < DEPTH; ++d) {
       if (it + d >= nst) break;  // uniform
-      step(it + d, d & 1, sets[(d + 1) % DEPTH]);
+      // (DEPTH 1, the widest BWD instances: one register set, the buffer alternates with `it`)
+      step(it + d, DEPTH == 1 ? it & 1 : d & 1, sets[(d + 1) % DEPTH]);
     }
   }
-  if constexpr (ST) {
+  if constexpr (ST || BWD) {
     // [wave][pixel lane][stat][64 channels], rows padded to 65 floats (lanes of one
     // write land on distinct banks); the halo buffers are dead after the last stage
     constexpr int kSR = 65;
@@ -478,7 +552,8 @@ __global__ __launch_bounds__(kCvThreads) void conv3x3_kernel(const uint16_t* __r
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int k = 0; k < 16; ++k) {
-        const int co = i * 32 + 8 * (k >> 2) + 4 * (lane >> 5) + (k & 3);
+        const int co = BWD ? i * 32 + 16 * (k >> 3) + 8 * (lane >> 5) + (k & 7)
+                           : i * 32 + 8 * (k >> 2) + 4 * (lane >> 5) + (k & 3);
         red[row * kSR + co] = bs[i][k];
         red[(row + 1) * kSR + co] = bq[i][k];
       }
@@ -573,13 +648,14 @@ bool conv3x3_ok(const Conv3x3Geom& g) {
 struct C3Pre {
   const float* ss;
   int64_t* nbt;
+  const uint16_t* xb;  // BWD: the preceding BatchNorm's input
 };
 
-template <int NX, bool FLIP, int JB, int DEPTH, int WC, int CC, bool ST, bool PRE>
+template <int NX, bool FLIP, int JB, int DEPTH, int WC, int CC, bool ST, bool PRE, bool BWD = false>
 static void launch_one(const uint16_t* x, const uint16_t* w, uint16_t* y, const Conv3x3Geom& g, hipStream_t st,
                        dim3 grid, float* part, const C3Pre& pre) {
-  hipLaunchKernelGGL((conv3x3_kernel<NX, FLIP, JB, DEPTH, WC, CC, ST, PRE>), grid, dim3(kCvThreads), 0, st, x, w, y,
-                     g, part, pre.ss, pre.nbt);
+  hipLaunchKernelGGL((conv3x3_kernel<NX, FLIP, JB, DEPTH, WC, CC, ST, PRE, BWD>), grid, dim3(kCvThreads), 0, st, x,
+                     w, y, g, part, pre.ss, pre.nbt, pre.xb);
 }
 
 // The compile-time-shape instances (tile size, NX, WC, CC): ResNet-50's stride-1 3x3
@@ -639,15 +715,64 @@ static void launch_nx(const uint16_t* x, const uint16_t* w, uint16_t* y, const C
   }
 }
 
+// BWD: the same instance choice as the plain input gradient (conv3x3_instance(g, false)).
+// DEPTHW: register stages of the 6- and 7-piece instances -- at 512-pixel tiles the second
+// stage spilled beside the sums (run-time shape 56 / 104 B of scratch per lane, 56x56
+// compile-time shape 100 B), so those keep one: the loads of stage k + 2 are in flight
+// behind stage k + 1's 72 MFMAs per wave (~2.3K clocks)
+template <int JB, int DEPTH, int DEPTHW>
+static void launch_bwd(const uint16_t* x, const uint16_t* w, uint16_t* y, const Conv3x3Geom& g, hipStream_t st,
+                       dim3 grid, float* part, const C3Pre& pre) {
+  const Conv3x3Instance ins = conv3x3_instance(g, false);
+  if (ins.fixed) {  // (g.tm, g.W) names the kC3Fixed row, as in launch_nx
+    if constexpr (JB == 4) {
+      if (g.W == 56) launch_one<7, true, JB, DEPTHW, 56, 64, false, false, true>(x, w, y, g, st, grid, part, pre);
+      else launch_one<5, true, JB, DEPTH, 28, 128, false, false, true>(x, w, y, g, st, grid, part, pre);
+    } else {
+      if (g.W == 28) launch_one<4, true, JB, DEPTH, 28, 128, false, false, true>(x, w, y, g, st, grid, part, pre);
+      else if (g.W == 14) launch_one<4, true, JB, DEPTH, 14, 256, false, false, true>(x, w, y, g, st, grid, part, pre);
+      else launch_one<4, true, JB, DEPTH, 7, 512, false, false, true>(x, w, y, g, st, grid, part, pre);
+    }
+    return;
+  }
+  switch (ins.nx) {
+    case 4:
+      launch_one<4, true, JB, DEPTH, 0, 0, false, false, true>(x, w, y, g, st, grid, part, pre);
+      break;
+    case 5:
+      launch_one<5, true, JB, DEPTH, 0, 0, false, false, true>(x, w, y, g, st, grid, part, pre);
+      break;
+    case 6:
+      launch_one<6, true, JB, DEPTHW, 0, 0, false, false, true>(x, w, y, g, st, grid, part, pre);
+      break;
+    default:
+      launch_one<7, true, JB, DEPTHW, 0, 0, false, false, true>(x, w, y, g, st, grid, part, pre);
+      break;
+  }
+}
+
 bool conv3x3_pre_ok(const Conv3x3Geom& g) { return conv3x3_ok(g) && g.Cin <= kPreMaxC; }
 
+// the coefficient table holds the workgroup's own 64 channels, so the limit is PRE's by
+// convention only (every BatchNorm the fused layers cover is far below it)
+bool conv3x3_bwd_ok(const Conv3x3Geom& g) { return conv3x3_ok(g) && g.Cout <= kPreMaxC; }
+
 bool launch_conv3x3(const uint16_t* x, const uint16_t* w, uint16_t* y, const Conv3x3Geom& g, bool flip,
-                    hipStream_t st, float* part, const float* pre_ss, int64_t* nbt_inc) {
+                    hipStream_t st, float* part, const float* pre_ss, int64_t* nbt_inc, const uint16_t* bwd_x) {
+  if (bwd_x) {
+    // BatchNorm-backward epilogue: the input gradient only, with both the statistics and the sums' row buffer
+    if (!flip || !part || !pre_ss || !conv3x3_bwd_ok(g)) return false;
+    const dim3 grid((unsigned)(g.wpb * (g.Cout / kTN)));
+    const C3Pre pre{pre_ss, nullptr, bwd_x};
+    if (g.tm == 512) launch_bwd<4, 2, 1>(x, w, y, g, st, grid, part, pre);
+    else launch_bwd<2, 4, 4>(x, w, y, g, st, grid, part, pre);
+    return true;
+  }
   if (!conv3x3_ok(g) || (flip && part) || (flip && pre_ss) || (pre_ss && !part) || (pre_ss && g.Cin > kPreMaxC))
     return false;
   // persistent: one workgroup per (pixel range, output-channel block) -- one per CU
   const dim3 grid((unsigned)(g.wpb * (g.Cout / kTN)));
-  const C3Pre pre{pre_ss, nbt_inc};
+  const C3Pre pre{pre_ss, nbt_inc, nullptr};
   // 512-pixel tiles: twice the accumulators, so two register stages in flight.  A
   // deferred BatchNorm (pre_ss) comes with the statistics epilogue only (the ResNet path)
   if (g.tm == 512) {

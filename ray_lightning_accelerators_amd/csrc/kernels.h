@@ -330,7 +330,7 @@ int conv3x3_pick_tm(int N, int H, int W, int Cout);
 int conv3x3_vrows(const Conv3x3Geom& g);
 int conv3x3_pieces_per_thread(const Conv3x3Geom& g);  // 16-byte halo pieces per thread and chunk
 bool conv3x3_ok(const Conv3x3Geom& g);
-// the template instance launch_conv3x3 runs for g (pre: with pre_ss)
+// the template instance launch_conv3x3 runs for g (pre: with pre_ss; with bwd_x: that of pre = false)
 struct Conv3x3Instance {
   int nx;      // halo pieces per thread the instance is compiled for
   bool fixed;  // compile-time width and input channels
@@ -341,10 +341,15 @@ Conv3x3Instance conv3x3_instance(const Conv3x3Geom& g, bool pre);
 // part (forward only, or null): BatchNorm partial sums of bf16(y), [g.wpb][2][Cout] fp32
 // pre_ss (forward with part only; [4, Cin] BatchNorm stats, Cin <= 512): x is a deferred
 // BatchNorm + ReLU's input, staged as bf16(relu(x * scale + shift)); nbt_inc += 1
+// bwd_x (flip with part and pre_ss only; Cout <= 512): the PRECEDING BatchNorm + ReLU's
+// backward in the epilogue -- bwd_x [N, H, W, Cout] is that BatchNorm's input, pre_ss its
+// [4, Cout] statistics; y is d = fma(bwd_x, scale, shift) > 0 ? dx : 0 and part
+// [g.wpb][2][Cout] the sums of d and d * bwd_x over each range (bn_partial's backward layout)
 bool conv3x3_pre_ok(const Conv3x3Geom& g);
+bool conv3x3_bwd_ok(const Conv3x3Geom& g);
 bool launch_conv3x3(const uint16_t* x, const uint16_t* w, uint16_t* y, const Conv3x3Geom& g, bool flip,
                     hipStream_t stream, float* part = nullptr, const float* pre_ss = nullptr,
-                    int64_t* nbt_inc = nullptr);
+                    int64_t* nbt_inc = nullptr, const uint16_t* bwd_x = nullptr);
 
 // 3x3 / stride 2 / pad 1 NHWC bf16 convolution forward on MFMA (csrc/conv3x3s2.hip):
 // y [N, OH, OW, Cout] = conv(x [N, H, W, Cin], w [Cout][3][3][Cin]), OH = (H - 1) / 2 + 1,

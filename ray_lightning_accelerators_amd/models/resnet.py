@@ -69,6 +69,11 @@ class Bottleneck(nn.Module):
             # conv1 -- the shortcut's gradient is folded into bn3 -- so conv1's input
             # gradient may compute the previous bn3's backward partial (ops/conv.py)
             self.conv1.fuse_bn_dgrad = True
+        if fused_bn and isinstance(self.conv2, ConvBF16) and tuple(self.conv2.stride) == (1, 1):
+            # bn1's output feeds conv2 only: the 3x3 input gradient may compute bn1's backward
+            # mask and partial sums in its epilogue (ops/conv.py; stride-2 conv2 layers keep
+            # the library's input gradient)
+            self.conv2.fuse_bn_dgrad = True
 
     @staticmethod
     def _conv_bn(conv, bn, x, **kw):

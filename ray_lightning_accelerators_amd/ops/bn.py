@@ -69,12 +69,16 @@ def fused_ok(x: torch.Tensor, residual: Optional[torch.Tensor] = None) -> bool:
 class _FoldSlot:
     """Hand-off of a consumer layer's residual gradient to the producer of that residual."""
 
-    __slots__ = ("dres", "claimed", "x3", "bwd_part", "bwd_d")
+    __slots__ = ("dres", "claimed", "x3", "xin", "st", "bwd_part", "bwd_d")
 
     def __init__(self):
         self.dres = None
         self.claimed = False
         self.x3 = None        # this layer's input, for a consumer conv fusing our backward partial
+        # a ReLU layer WITHOUT residual: its input and forward statistics, for a consumer 3x3
+        # conv whose input-gradient epilogue recomputes our mask (ops.conv fuse_bn_dgrad, 3x3)
+        self.xin = None
+        self.st = None
         self.bwd_part = None  # that conv's partial sums of d (ops.conv fuse_bn_dgrad)
         self.bwd_d = None     # the d those sums are of (the tensor the conv returned as our dy)
 
@@ -176,6 +180,8 @@ class _BNActFn(torch.autograd.Function):
             defer.st, defer.nbt = st, (nbt if pending else None)
             ctx.relu, ctx.has_res, ctx.group, ctx.count = True, False, group, count
             ctx.slot, ctx.sink, ctx.recomp = slot, sink, True
+            if slot is not None and group is None:
+                slot.xin, slot.st = x, st  # a 3x3 conv reading the output may compute our backward partial
             ctx.save_for_backward(x, None, weight, st, None)
             return x
         y = torch.empty_like(x, memory_format=torch.channels_last)
@@ -185,6 +191,8 @@ class _BNActFn(torch.autograd.Function):
         ctx.slot, ctx.sink = slot, sink
         if slot is not None and relu and residual is not None and group is None:
             slot.x3 = x  # a 1x1 conv reading y may compute our backward partial (ops/conv.py)
+        if slot is not None and relu and residual is None and group is None:
+            slot.xin, slot.st = x, st  # likewise a 3x3 conv, whose epilogue recomputes the mask from x
         # ReLU without a residual: the backward recomputes the mask x*scale+shift > 0
         # from the stats (one stream less to read in both backward passes); with a
         # residual the mask needs the sum, so y is kept
@@ -239,8 +247,9 @@ class _BNActFn(torch.autograd.Function):
                 ctx.slot.bwd_part, fused = None, None
                 fold_stats["fused_rejected"] += 1
         if fused is not None:
-            # the consumer 1x1 conv's input-gradient kernel already produced d (= dy here)
-            # and its partial sums (ops/conv.py fuse_bn_dgrad)
+            # the consumer conv's input-gradient kernel already produced the masked d (= dy
+            # here) and its partial sums (ops/conv.py fuse_bn_dgrad: the 1x1 kernel for a
+            # residual layer, the 3x3 one for a layer without): the apply reads x and d
             ctx.slot.bwd_part, part, dres = None, fused, dy
         else:
             dres = torch.empty_like(x, memory_format=torch.channels_last) if ctx.has_res else None
@@ -263,6 +272,8 @@ class _BNActFn(torch.autograd.Function):
         # views of the coefficient tensor (no copy kernels): autograd hands them to .grad
         dgamma = wsrc[0] if weight is not None and ctx.needs_input_grad[1] else None
         dbeta = wsrc[1] if ctx.needs_input_grad[2] else None
+        if not ctx.has_res:
+            dres = None  # (the fused d of a layer without residual: there is no residual input)
         return dx, dgamma, dbeta, dres, None, None, None, None, None, None, None, None, None, None, None, None
 
 

@@ -48,7 +48,7 @@ from torch import nn
 # keyed by (op, M, Cin, Cout) for the 1x1 layers, (op, M, Cin, Cout, KH, KW, stride, pad) for KxK
 _choice: Dict[Tuple, str] = {}
 _timings: Dict[Tuple, Dict[str, float]] = {}
-stats = {"fast": 0, "fallback": 0, "bn_dgrad_fused": 0, "stem": 0, "pre_applied": 0}
+stats = {"fast": 0, "fallback": 0, "bn_dgrad_fused": 0, "bn_dgrad_fused_3x3": 0, "stem": 0, "pre_applied": 0}
 
 
 def _mode() -> str:
@@ -272,6 +272,74 @@ def conv3x3_dgrad_hip(dy: torch.Tensor, wb: torch.Tensor) -> torch.Tensor:
     cin = wb.size(1)
     dx = require().conv3x3(dy.permute(0, 2, 3, 1), wb.permute(0, 2, 3, 1), n, h, w, cout, cin, True)
     return dx.permute(0, 3, 1, 2)
+
+
+def conv3x3_dgrad_bn_hip(dy: torch.Tensor, wb: torch.Tensor, xb: torch.Tensor, ss: torch.Tensor):
+    """:func:`conv3x3_dgrad_hip` with the PRECEDING BatchNorm + ReLU's backward in the
+    epilogue (csrc/conv3x3.hip BWD): ``xb`` [N, Cin, H, W] channels_last bf16 is that
+    BatchNorm's input and ``ss`` its [4, Cin] forward statistics.  Returns (d channels_last,
+    part [rows, 2, Cin]): d = dx where xb * scale + shift > 0, else 0 -- bitwise what the
+    BatchNorm's own recomputed-mask passes see -- and the fixed-order partial sums of d and
+    d * xb that ``bn_bwd_finalize`` reads."""
+    from . import require
+
+    n, cout, h, w = dy.shape
+    cin = wb.size(1)
+    d, part = require().conv3x3_dgrad_bn(dy.permute(0, 2, 3, 1), wb.permute(0, 2, 3, 1), n, h, w, cout, cin,
+                                         xb.permute(0, 2, 3, 1), ss)
+    return d.permute(0, 3, 1, 2), part
+
+
+def fuse_bn_dgrad_3x3_mode() -> str:
+    """``RLA_FUSE_BN_DGRAD_3X3``: a 3x3 / stride-1 conv marked ``fuse_bn_dgrad`` (ResNet's
+    bottleneck conv2, the only reader of bn1's output) computes that BatchNorm's backward
+    mask and partial sums in its input-gradient epilogue.  ``0``: never; ``1``: wherever
+    the kernel covers the shape; ``auto`` (default): per shape, whichever of the fused
+    kernel and the plain input gradient + BatchNorm's own partial pass is faster
+    (``dgrad_kxk_bn`` in :func:`choices`)."""
+    m = os.environ.get("RLA_FUSE_BN_DGRAD_3X3", "auto")
+    return m if m in ("0", "1") else "auto"
+
+
+@functools.lru_cache(maxsize=256)
+def _dgrad_bn_shape_ok(n: int, h: int, w: int, cr: int, co: int) -> bool:
+    from . import require
+
+    return bool(require().conv3x3_dgrad_bn_ok(n, h, w, cr, co))
+
+
+def _fold_3x3_ok(fold, x: torch.Tensor, wb: torch.Tensor) -> bool:
+    """The producer BatchNorm left its input and statistics (ops/bn.py _FoldSlot.xin / st)
+    and the fused input-gradient kernel covers the layer."""
+    xin, st = getattr(fold, "xin", None), getattr(fold, "st", None)
+    if xin is None or st is None or fuse_bn_dgrad_3x3_mode() == "0":
+        return False
+    n, cin, h, w = x.shape
+    return (xin.shape == x.shape and xin.dtype == torch.bfloat16 and xin.is_cuda
+            and xin.is_contiguous(memory_format=torch.channels_last) and xin.data_ptr() % 16 == 0
+            and st.dtype == torch.float32 and tuple(st.shape) == (4, cin) and st.is_contiguous()
+            and _dgrad_bn_shape_ok(n, h, w, wb.size(0), cin))
+
+
+def _pick_dgrad_bn(key: Tuple[int, ...], dy: torch.Tensor, wb: torch.Tensor, fold) -> str:
+    """``fused`` or ``split`` for a 3x3 input gradient whose input is a fold-carrying
+    BatchNorm + ReLU output (both fixed-order, so deterministic mode takes ``fused``
+    untimed; a graph capture with no cached pick takes ``split``)."""
+    mode = fuse_bn_dgrad_3x3_mode()
+    if mode == "1" or torch.are_deterministic_algorithms_enabled():
+        return "fused"
+    from . import require
+
+    xin, st = fold.xin, fold.st
+
+    def split():
+        da = conv3x3_dgrad_hip(dy, wb)
+        return da, require().bn_partial(xin.permute(0, 2, 3, 1), None, da.permute(0, 2, 3, 1), xin.size(1), 1, True,
+                                        None, None, st, None)
+
+    cands = {"fused": lambda: conv3x3_dgrad_bn_hip(dy, wb, xin, st), "split": split}
+    be = _pick("dgrad_kxk_bn", key, cands)
+    return be if be in cands else "split"  # _pick's capture answer names no candidate here
 
 
 def conv3x3s2_ok(x: torch.Tensor, wb: torch.Tensor, stride, padding) -> bool:
@@ -583,9 +651,13 @@ class _ConvNHWCFn(torch.autograd.Function):
     reaches the fp32 master weight in fp32."""
 
     @staticmethod
-    def forward(ctx, x, weight, wb, stride, padding, fork=None, bn_stats=None, pre=None):
+    def forward(ctx, x, weight, wb, stride, padding, fork=None, bn_stats=None, pre=None, fold=None):
         ctx.pre_st = pre.st if pre is not None else None
         ctx.c3 = pre is not None or conv3x3_ok(x, wb, stride, padding)
+        # fold: the _FoldSlot of the BatchNorm + ReLU (no residual) whose output x is -- or,
+        # with pre, stands for -- and which no one else reads: the input gradient may
+        # absorb that BatchNorm's backward mask and partial sums (conv3x3_dgrad_bn_hip)
+        ctx.fold = fold if (ctx.c3 and fork is None and fold is not None and _fold_3x3_ok(fold, x, wb)) else None
         cands = {"miopen": lambda: _miopen_fwd(x, wb, stride, padding)}
         if pre is not None:
             # x is a deferred BatchNorm + ReLU's input (ops/bn.py DeferredApply): the
@@ -673,6 +745,16 @@ class _ConvNHWCFn(torch.autograd.Function):
             fork = None  # the input gradient is settled
         need_dx = bool(ctx.needs_input_grad[0]) and dx is None
         be_d = be_w = None
+        fold = ctx.fold
+        if (need_dx and fold is not None and ctx.fork is None and fold.xin is not None and not fold.claimed
+                and _pick_dgrad_bn((x.size(0) * x.size(2) * x.size(3), cin, cout, 3, 3, 1, 1), dy, wb, fold)
+                == "fused"):
+            # d = dgrad masked by the producer BatchNorm's recomputed ReLU mask, and that
+            # BatchNorm's backward partial sums, in one kernel; its backward takes d as its dy
+            dx, part = conv3x3_dgrad_bn_hip(dy, wb, fold.xin, fold.st)
+            fold.bwd_part, fold.bwd_d = part, dx  # bn backward checks it receives exactly this tensor
+            stats["bn_dgrad_fused_3x3"] += 1
+            need_dx = False
         if ctx.needs_input_grad[1]:
             key = (x.size(0) * dy.size(2) * dy.size(3), cin, cout, kh, kw, stride[0], padding[0])
             be_w = _pick("wgrad_kxk" if st is None else "wgrad_kxk_pre", key, wgrad)
@@ -688,7 +770,7 @@ class _ConvNHWCFn(torch.autograd.Function):
                 dx = _fork_dx(fork, dgrad[be_d], None)
             if be_w is not None:
                 dw = wgrad[be_w]()
-        return dx, dw, None, None, None, None, None, None
+        return dx, dw, None, None, None, None, None, None, None
 
 
 @functools.lru_cache(maxsize=64)
@@ -773,6 +855,8 @@ def conv_nhwc(x: torch.Tensor, conv: nn.Conv2d, wb: torch.Tensor, fork: Optional
     """``conv(x)`` with the bf16 weight ``wb`` (the arena shadow), the weight gradient
     going to ``conv.weight`` in fp32 (``fork``: see :class:`GradFork`; ``bn_stats``:
     see :class:`BNStats`, filled only by the 3x3 MFMA forwards, stride 1 or 2)."""
+    # before materialize(x), whose result no longer carries the tag
+    fold = getattr(x, "_rla_fold", None) if getattr(conv, "fuse_bn_dgrad", False) else None
     pre = getattr(x, "_rla_pre", None)
     if pre is not None:
         # a deferred BatchNorm + ReLU output (ops/bn.py DeferredApply): the 3x3 statistics
@@ -795,7 +879,7 @@ def conv_nhwc(x: torch.Tensor, conv: nn.Conv2d, wb: torch.Tensor, fork: Optional
                 pre.used = True
                 stats["fast"] += 1
                 stats["pre_applied"] += 1
-                return _ConvNHWCFn.apply(x, conv.weight, wb, conv.stride, conv.padding, None, bn_stats, pre)
+                return _ConvNHWCFn.apply(x, conv.weight, wb, conv.stride, conv.padding, None, bn_stats, pre, fold)
         x = materialize(x)
     stats["fast"] += 1
-    return _ConvNHWCFn.apply(x, conv.weight, wb, conv.stride, conv.padding, fork, bn_stats)
+    return _ConvNHWCFn.apply(x, conv.weight, wb, conv.stride, conv.padding, fork, bn_stats, None, fold)
