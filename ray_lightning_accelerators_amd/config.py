@@ -34,6 +34,7 @@ _CHOICES = {
     "precision": ("32", "bf16"),
     "pg_backend": ("auto", "nccl", "gloo"),
     "hip_graph_step": ("auto", "on", "off"),
+    "mlp_saturation": ("warn", "raise", "ignore"),
 }
 
 # legacy env names kept working (first release used these spellings)
@@ -67,6 +68,12 @@ class RLAConfig:
     fused_dp: bool = True
     # capture the resident MNIST step into hipGraphs
     use_hip_graph: bool = True
+    # MNIST fused step: what FusedMLPEngine.check() does when the kernel counted
+    # layer-1 tile partials that its 12.20 fixed point clamped (beyond +-32) or that
+    # were NaN / Inf.  warn = one log.warning per check that sees a count grow;
+    # raise = FusedStepNumericsError on the first non-zero count; ignore = counted
+    # (engine.health()) but never reported.  Hand-off time-outs raise under all three.
+    mlp_saturation: str = "warn"
     # Trainer: capture an autograd LightningModule's whole training step (forward,
     # backward, gradient all-reduce, fused optimizer) in one hipGraph and replay it
     # (lightning/graph_step.py).  auto = when the module sets hip_graph_step = True;

@@ -236,11 +236,12 @@ void mlp3(int64_t kind, Tensor x_u8, Tensor labels, Tensor order, Tensor counter
   a.stats_ring = a.stats ? (int)(stats->numel() / 4) : 0;
   a.head_part = ptr_or_null<float>(head_part, "head_part", at::kFloat, (Bp / 32) * 4);
   TORCH_CHECK(B <= 32 || a.head_part != nullptr, "mlp3: batches above 32 rows need head_part [ceil(B/32), 4]");
+  // every kind counts saturated / non-finite layer-1 partials into `hand` when it is given
+  a.hand = reinterpret_cast<unsigned long long*>(
+      ptr_or_null<int64_t>(hand, "hand", at::kLong, rla::mlp3_hand_words((int)L1, (int)L2)));
   if (kind == rla::kMLP3Step1 || kind == rla::kMLP3Step1DP) {
     TORCH_CHECK(B <= 32, "the one-launch step handles batches of up to 32 rows");
     TORCH_CHECK(counters.numel() >= 16, "the one-launch step needs counters of >= 16 int64 (launch sequence)");
-    a.hand = reinterpret_cast<unsigned long long*>(
-        ptr_or_null<int64_t>(hand, "hand", at::kLong, rla::mlp3_hand_words((int)L1, (int)L2)));
     TORCH_CHECK(a.hand != nullptr, "the one-launch step needs the hand-off buffer `hand`");
     a.hand_spin = 1 << 20;
   }
@@ -1118,6 +1119,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "3 tail-adam, 4 prime, 5 step with the in-kernel xGMI exchange, 6 one-launch step (B <= 32)");
   m.def("dp_pack_roundtrip", &dp_pack_roundtrip, "packed DP exchange wire form of fp32 pairs, encoded + decoded");
   m.def("mlp3_hand_words", [](int64_t l1, int64_t l2) { return rla::mlp3_hand_words((int)l1, (int)l2); });
+  m.def("mlp3_hand_layout", []() {
+    const rla::MLP3HandLayout h = rla::mlp3_hand_layout();
+    py::dict d;
+    d["ack"] = h.ack; d["err"] = h.err; d["sat"] = h.sat; d["nonfinite"] = h.nonfinite;
+    d["last_step"] = h.last_step; d["words"] = h.words;
+    return d;
+  });
   m.def("mlp3_h1_copies", [](int64_t l1) { return rla::mlp3_h1_copies((int)l1); },
         "H1pre copies per ring slot of the v3 step (the layer-1 partials' atomic fan-in is split over them)");
   m.def("mlp3_dp_area_floats", []() { return rla::comm::kDpUnitAreaFloats; },

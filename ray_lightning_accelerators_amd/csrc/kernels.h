@@ -262,13 +262,23 @@ struct MLP3Args {
   // loopback (diagnostic): one process plays all dp_world ranks through its own region
   // (every region pointer is this rank's; the block writes every source slot itself)
   int dp_loop;
-  // one-launch step (kMLP3Step1): in-launch hand-off words (mlp_step3.hip) and their poll bound
+  // one-launch step (kMLP3Step1): in-launch hand-off words (mlp_step3.hip) and their poll bound.
+  // Every kind that computes layer-1 partials (both step forms, the ADAM tail, PRIME) also
+  // counts the partials its 12.20 conversion clamped (finite, beyond +-32) or that were NaN /
+  // Inf into words sat / nonfinite of this buffer, and the latest affected optimizer step
+  // into last_step (mlp3_hand_layout); nullptr (two-launch kinds only): nothing is counted.
   unsigned long long* hand;
   int64_t hand_spin;
 };
 enum MLP3Kind { kMLP3Step = 0, kMLP3Head = 1, kMLP3TailGrad = 2, kMLP3TailAdam = 3, kMLP3Prime = 4,
                 kMLP3StepDP = 5, kMLP3Step1 = 6, kMLP3Step1DP = 7 };
 int64_t mlp3_hand_words(int L1, int L2);  // int64 words of the one-launch step's hand-off buffer
+// word indices of `hand`: ack / err (the one-launch hand-off), sat / nonfinite / last_step
+// (exact, monotonic u64 health counts of the layer-1 partial sums)
+struct MLP3HandLayout {
+  int ack, err, sat, nonfinite, last_step, words;
+};
+MLP3HandLayout mlp3_hand_layout();
 int launch_mlp3(const MLP3Args& a, int kind, hipStream_t stream);
 
 int mlp3_act_rows(int L1, int L2);

@@ -42,6 +42,8 @@
 // (((b/16 * L1/16 + m/16) * 4 + b%4) * 64 + (b%16/4) * 16 + m%16) so every atomic
 // wave-instruction covers 256 contiguous bytes.  The integer atomics are
 // associative, so H1pre (and the step) does not depend on arrival order.
+#include <cfloat>
+
 #include "common.h"
 #include "kernels.h"
 #include "mlp_common.h"
@@ -174,6 +176,58 @@ __device__ __forceinline__ void stamp_max(const MLP3Args& a, int k) {
 // is set when a bounded wait expires.
 constexpr int kSeq = 10;
 constexpr int kHandAck = 0, kHandErr = 16, kHandWords = 32;
+
+// Health of the layer-1 partial sums (both kinds of step and PRIME): f32_to_fixed
+// clamps silently and turns a NaN into -32, so the tile code classifies every MFMA
+// result of a real batch row and counts, exactly and monotonically (u64),
+//   hand[kHandSat]        finite partials beyond +-32 (replaced by the clamp),
+//   hand[kHandNonFinite]  NaN / Inf partials (never also counted as saturated),
+//   hand[kHandLastStep]   the latest optimizer step whose launch counted one
+//                         (the step the launch belongs to; PRIME: the current counter).
+// On the path every launch takes, a result costs one compare (not within +-32, true
+// for NaN) OR-ed into a lane mask, and an MFMA tile one wave-uniform branch on the
+// mask: a wave of a healthy run issues no memory operation.  A tile with trouble is
+// classified where it stands: per result two ballots (saturated / non-finite, real
+// rows only: 0 * NaN in a padded row raises the mask too) whose population counts add
+// into two wave-uniform tallies -- scalar work, no cross-lane traffic -- and at the end
+// one lane adds the tallies.  Both paths are kept this light on purpose: per-lane
+// counting with the full classification on the common path cost the two-launch step
+// 0.25 us, and a shuffle reduction on the reporting path showed in the benchmark, which
+// runs at lr 0.1 where the clamp does fire (profiles/r10_mlp_health).
+constexpr int kHandSat = 17, kHandNonFinite = 18, kHandLastStep = 19;
+static_assert(kHandLastStep < kHandWords, "health words inside the hand buffer");
+constexpr float kH1Sat = 32.0f;  // == kFixSat / kFix
+
+struct H1Health {
+  unsigned sat = 0u, bad = 0u;  // wave-uniform
+};
+
+// d[i] is batch row `row0 + i` of one 16x16 H1pre tile
+__device__ __forceinline__ void h1_check(H1Health& h, const f32x4& d, int row0, int B) {
+  const bool trouble = !(fabsf(d[0]) <= kH1Sat) | !(fabsf(d[1]) <= kH1Sat) | !(fabsf(d[2]) <= kH1Sat) |
+                       !(fabsf(d[3]) <= kH1Sat);
+  if (__builtin_amdgcn_ballot_w64(trouble) == 0ull) return;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float m = fabsf(d[i]);
+    const bool real = row0 + i < B, finite = m <= FLT_MAX;
+    h.bad += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(real && !finite));
+    h.sat += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(real && finite && m > kH1Sat));
+  }
+}
+
+__device__ __forceinline__ void h1_report(const MLP3Args& a, const H1Health& h, int64_t step) {
+  if ((h.sat | h.bad) == 0u || !a.hand) return;
+  if ((threadIdx.x & 63) == 0) {
+    if (h.sat)
+      __hip_atomic_fetch_add(a.hand + kHandSat, (unsigned long long)h.sat, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (h.bad)
+      __hip_atomic_fetch_add(a.hand + kHandNonFinite, (unsigned long long)h.bad, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_max(a.hand + kHandLastStep, (unsigned long long)step, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
 
 // ---------------------------------------------------------------------------
 // Head kernel (blocks [0, nchunks): one 8-wave workgroup per BC batch rows;
@@ -1641,13 +1695,16 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
     unsigned* h1 =
         reinterpret_cast<unsigned*>(a.h1pre + (slot * G + kt % G) * (int64_t)Bp * L1);
     const bf16x8 bfrag = (g < 2) ? ld8(sW + (ct * 16 + r16) * kXSS + 8 * g) : zero8();
+    H1Health health;
     for (int mt = 0; mt < Bp / 16; ++mt) {
       const bf16x8 afrag = (g < 2) ? ld8(sXn + (mt * 16 + r16) * kXSS + 8 * g) : zero8();
       const f32x4 d = mfma16(afrag, bfrag, f32x4{0.f, 0.f, 0.f, 0.f});
       unsigned* dst = h1 + (int64_t)((mt * TN1 + ct) * 4) * 64 + lane;
 #pragma unroll
       for (int i = 0; i < 4; ++i) atomicAdd(dst + i * 64, f32_to_fixed(d[i]));
+      h1_check(health, d, mt * 16 + 4 * g, B);
     }
+    h1_report(a, health, t_step);  // the head advanced it; PRIME: the current counter
   }
   if (a.stamps && kt == 0 && tid == 0) a.stamps[10] = __builtin_amdgcn_s_memrealtime();
   stamp_max(a, 11);
@@ -1904,6 +1961,7 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args a) {
       constexpr int G = H1Copies<L1>::G;
       unsigned* h1 = reinterpret_cast<unsigned*>(a.h1pre + ((slot ^ 1) * G + kt % G) * (int64_t)Bp * L1);
       const bf16x8 bfrag = (g < 2) ? ld8(sW + (w * 16 + r16) * kXSS + 8 * g) : zero8();
+      H1Health health;
 #pragma unroll
       for (int mt = 0; mt < Bp / 16; ++mt) {
         const bf16x8 afrag = (g < 2) ? ld8(sXn + (mt * 16 + r16) * kXSS + 8 * g) : zero8();
@@ -1911,7 +1969,9 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args a) {
         unsigned* dst = h1 + (int64_t)((mt * TN1 + w) * 4) * 64 + lane;
 #pragma unroll
         for (int i = 0; i < 4; ++i) atomicAdd(dst + i * 64, f32_to_fixed(d[i]));
+        h1_check(health, d, mt * 16 + 4 * g, B);
       }
+      h1_report(a, health, c0 + 1);
     }
     if (a.stamps && blk == 1 && tid == 0) a.stamps[10] = __builtin_amdgcn_s_memrealtime();
     stamp_max(a, 5);  // probe builds: the latest W1-tile block end
@@ -2064,6 +2124,9 @@ int dp_pack_roundtrip(const float* x, float* y, int64_t n, int tag, hipStream_t 
 int mlp3_act_rows(int L1, int L2) { return L1 + 2 * L2 + 16; }
 int mlp3_h1_copies(int L1) { return L1 <= 64 ? H1Copies<64>::G : H1Copies<128>::G; }
 int64_t mlp3_hand_words(int, int) { return kHandWords; }
+MLP3HandLayout mlp3_hand_layout() {
+  return {kHandAck, kHandErr, kHandSat, kHandNonFinite, kHandLastStep, kHandWords};
+}
 
 int launch_mlp3(const MLP3Args& a, int kind, hipStream_t stream) {
   if (a.B > kBMax || a.B < 1) return -2;

@@ -166,6 +166,8 @@ class Trainer:
         self.reload_dataloaders_every_epoch = reload_dataloaders_every_epoch
         self.weights_summary = weights_summary
         self.fused_step = fused_step
+        # set at the end of a fit that ran the fused MNIST step: FusedMLPEngine.health()
+        self.fused_step_health: Optional[Dict[str, Any]] = None
         self.steps_per_dispatch = steps_per_dispatch  # None: RLAConfig.steps_per_dispatch
         self._chunks_span_logs = False
         self.profiler = resolve_profiler(profiler)
@@ -464,6 +466,7 @@ class Trainer:
         self.accelerator_backend.configure_ddp(model)
         mark("ddp_configured", rank=self.global_rank)
         self._fused = self._maybe_fused(model)
+        self.fused_step_health = None
         mark("fused_step_ready", rank=self.global_rank)
         if self.resume_from_checkpoint and os.path.exists(self.resume_from_checkpoint):
             self.checkpoint_connector.restore(self.resume_from_checkpoint, on_gpu=self.on_gpu)
@@ -477,6 +480,10 @@ class Trainer:
         f = self._fused
         if f is not None and hasattr(f, "check"):
             f.check(blocking=True)  # the epoch-end checks trail by one epoch: the last one here
+            if hasattr(f, "health"):
+                # the fused MNIST step's saturation / non-finite counts of the whole fit
+                self.fused_step_health = f.health()
+                mark("fused_step_health", rank=self.global_rank, **self.fused_step_health)
         model.teardown("fit")
         return None
 

@@ -500,10 +500,17 @@ class FusedMNISTStep:
         return {"val_loss": tot[0], "val_accuracy": tot[1]}
 
     def check(self, blocking: bool = True) -> None:
-        """Raise if the engine's in-launch hand-off ever timed out (epoch end:
-        ``blocking=False`` checks the previous epoch's asynchronously copied flag)."""
+        """Raise if the engine's in-launch hand-off ever timed out, and report saturated /
+        non-finite layer-1 partial sums as ``RLAConfig.mlp_saturation`` says (epoch end:
+        ``blocking=False`` checks the previous epoch's asynchronously copied words)."""
         if self.eng is not None:
             self.eng.check(blocking)
+
+    def health(self, blocking: bool = True) -> Dict[str, Any]:
+        """``FusedMLPEngine.health()`` of the engine behind this step."""
+        if self.eng is not None:
+            return self.eng.health(blocking)
+        return {"saturated": 0, "nonfinite": 0, "last_step": 0, "timed_out": False}
 
     def sync_optimizer_state(self) -> None:
         """Owner protocol: consolidate the Adam state before it is read (collective)."""

@@ -186,7 +186,47 @@ def mlp3_dp_capacity(L1: int, L2: int) -> int:
 def mlp3_hand_words(L1: int, L2: int) -> int:
     """int64 words of the one-launch step's acknowledgement / error buffer (csrc/mlp_step3.hip)."""
     return 32
+
+
+# word indices of ``hand`` as csrc/mlp_step3.hip defines them (``_C.mlp3_hand_layout()``;
+# this copy serves the CPU engine and is checked against the extension when it loads)
+HAND_LAYOUT = {"ack": 0, "err": 16, "sat": 17, "nonfinite": 18, "last_step": 19, "words": 32}
+_hand_layout: Optional[Dict[str, int]] = None
+
+
+def mlp3_hand_layout(native: bool = True) -> Dict[str, int]:
+    """Where the kernels keep what in ``hand``: ``ack`` / ``err`` (the one-launch
+    hand-off), ``sat`` / ``nonfinite`` / ``last_step`` (health of the layer-1 partial
+    sums).  ``native``: read it from the extension (an engine on the GPU does)."""
+    global _hand_layout
+    if not native:
+        return dict(HAND_LAYOUT)
+    if _hand_layout is None:
+        lay = {k: int(v) for k, v in require().mlp3_hand_layout().items()}
+        if lay != HAND_LAYOUT:
+            raise RuntimeError(f"hand layout of the extension {lay} differs from ops.fused_mlp.HAND_LAYOUT")
+        _hand_layout = lay
+    return dict(_hand_layout)
+
+
 W1_TILES = IN_FEATURES // 16
+H1_SAT = 32.0  # |tile partial| beyond this is clamped by the 12.20 conversion
+
+
+def mlp3_h1_health(x_rows: torch.Tensor, w1_bf16: torch.Tensor) -> Tuple[int, int]:
+    """(saturated, nonfinite) over the 49 x B x L1 layer-1 tile partials of one batch,
+    as the kernels classify them (csrc/mlp_step3.hip ``h1_check``): fp32 partial
+    sums over 16 pixels of bf16 operands; non-finite = NaN or Inf, saturated =
+    finite and beyond +-32 (what the fixed-point conversion clamps).  Pure torch, on
+    the CPU: the oracle of the health counters.  ``x_rows``: [B, 784] pixels in
+    [0, 1] (real batch rows only), ``w1_bf16``: [L1, 784]."""
+    xt = x_rows.detach().cpu().to(torch.bfloat16).double().view(x_rows.size(0), W1_TILES, 16)
+    wt = w1_bf16.detach().cpu().to(torch.bfloat16).double().view(w1_bf16.size(0), W1_TILES, 16)
+    part = torch.einsum("bti,mti->tbm", xt, wt).float()  # fp32 MFMA partials
+    mag = part.abs()
+    bad = ~(mag <= torch.finfo(torch.float32).max)
+    sat = (mag > H1_SAT) & ~bad
+    return int(sat.sum()), int(bad.sum())
 
 
 def mlp3_h1_copies(L1: int) -> int:
@@ -210,7 +250,8 @@ def mlp3_buffers(L1: int, L2: int, B: int, device) -> Dict[str, torch.Tensor]:
         # [0, 5) current state, [5, 10) the head's advanced copy (published by the tail),
         # [10] the one-launch step's launch sequence number (its hand-off tag)
         "counters": torch.zeros(16, dtype=torch.int64, device=device),
-        # one-launch step: [0] per-block state acknowledgements (monotonic), [16] wait-timeout flag
+        # one-launch step: [0] per-block state acknowledgements (monotonic), [16] wait-timeout flag;
+        # every step kind: [17] saturated / [18] non-finite layer-1 partials, [19] last such step
         "hand": torch.zeros(mlp3_hand_words(L1, L2), dtype=torch.int64, device=device),
         # per-head-workgroup (sum NLL, #correct, #rows, -) when the batch spans several
         "head_part": torch.zeros(bp // 32 * 4, device=device),

@@ -29,6 +29,7 @@ oracle of the GPU tests) with identical batch order and optimizer semantics.
 """
 from __future__ import annotations
 
+import logging
 import math
 import os
 from typing import Callable, Dict, Optional, Sequence
@@ -36,8 +37,28 @@ from typing import Callable, Dict, Optional, Sequence
 import torch
 import torch.distributed as dist
 
+from ..config import get_config
 from ..ops import fused_mlp
 from ..ops.optim import fused_adam_
+
+log = logging.getLogger(__name__)
+
+
+class FusedStepNumericsError(RuntimeError):
+    """The fused MNIST step's layer-1 sum left its 12.20 fixed-point range or met a
+    NaN / Inf: the step is no longer the computation that was asked for."""
+
+    def __init__(self, saturated: int, nonfinite: int, last_step: int):
+        super().__init__(self.describe(saturated, nonfinite, last_step))
+        self.saturated, self.nonfinite, self.last_step = int(saturated), int(nonfinite), int(last_step)
+
+    @staticmethod
+    def describe(saturated: int, nonfinite: int, last_step: int) -> str:
+        return (f"fused MLP step: {int(saturated)} layer-1 tile partial(s) saturated the 12.20 fixed point "
+                f"(|partial| > 32, clamped) and {int(nonfinite)} were NaN / Inf (stored as +-32, so the "
+                f"reported loss stays finite); last affected optimizer step {int(last_step)}. "
+                "Remedies: Trainer(fused_step=False) (fp32 autograd path), a lower learning rate, or "
+                "RLA_MLP_SATURATION=warn to keep training with a warning.")
 
 
 def shard_indices(n: int, world: int, rank: int, epoch: int, seed: int, shuffle: bool,
@@ -136,6 +157,13 @@ class FusedMLPEngine:
         self.yring = bufs["yring"]
         self.head_part = bufs["head_part"]
         self.hand = bufs["hand"]
+        # word indices of `hand`; err, sat, nonfinite, last_step are adjacent (one copy reads them)
+        self._hl = fused_mlp.mlp3_hand_layout(native=self.native)
+        assert [self._hl[k] - self._hl["err"] for k in ("sat", "nonfinite", "last_step")] == [1, 2, 3]
+        self.saturation_policy: Optional[str] = None  # None: RLAConfig.mlp_saturation at each check
+        self._health_reported = (0, 0)  # counts the warn policy has already logged
+        self._health_last = {"saturated": 0, "nonfinite": 0, "last_step": 0, "timed_out": False}
+        self._hand_probe = None
         # world size 1, B <= 32: the whole step as ONE launch at every width
         # (RLA_MLP_ONE_LAUNCH=0: head + tail).  Round 5 gated widths > 64 off after
         # intermittent fidelity failures in long GPU sessions; round 6's post-mortem
@@ -228,31 +256,82 @@ class FusedMLPEngine:
 
     def check(self, blocking: bool = True) -> None:
         """Raise if a one-launch step's in-launch hand-off ever timed out (a block
-        polled past its bound: the step it belongs to is not trustworthy).
-        ``blocking=False`` (the Trainer's epoch ends): the flag is copied to pinned
+        polled past its bound: the step it belongs to is not trustworthy), then report
+        the kernels' saturation / non-finite counts as ``RLAConfig.mlp_saturation``
+        says (``warn`` / ``raise`` / ``ignore``; ``health`` has the counts).
+        ``blocking=False`` (the Trainer's epoch ends): the words are copied to pinned
         host memory asynchronously and the copy made at the PREVIOUS call is the one
         checked -- no device sync at an epoch boundary, detection one epoch late; a
-        blocking call at the end of the fit reads the current value."""
+        blocking call at the end of the fit reads the current values."""
         if not self.native:
             return
+        lo, hi = self._hl["err"], self._hl["last_step"] + 1
         prev = getattr(self, "_hand_probe", None)
         if prev is not None:
             buf, ev = prev
             ev.synchronize()  # enqueued one epoch ago: long complete
             self._hand_probe = None
-            if int(buf[0]) != 0:
-                raise RuntimeError("fused MLP one-launch step: an in-launch hand-off timed out")
+            self._apply_health(buf.tolist())
         if blocking:
-            if int(self.hand[16].item()) != 0:
-                raise RuntimeError("fused MLP one-launch step: an in-launch hand-off timed out")
+            self._apply_health(self.hand[lo:hi].tolist())
             return
         buf = getattr(self, "_hand_pin", None)
         if buf is None:
-            buf = self._hand_pin = torch.zeros(1, dtype=self.hand.dtype, pin_memory=True)
-        buf.copy_(self.hand[16:17], non_blocking=True)
+            buf = self._hand_pin = torch.zeros(hi - lo, dtype=self.hand.dtype, pin_memory=True)
+        buf.copy_(self.hand[lo:hi], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
         self._hand_probe = (buf, ev)
+
+    def _health_dict(self, words) -> Dict[str, object]:
+        """``hand[err : last_step + 1]`` as the dict ``health`` returns."""
+        o = self._hl["err"]
+        return {"saturated": int(words[self._hl["sat"] - o]), "nonfinite": int(words[self._hl["nonfinite"] - o]),
+                "last_step": int(words[self._hl["last_step"] - o]), "timed_out": int(words[0]) != 0}
+
+    def _apply_health(self, words) -> None:
+        """One reading of the error / health words: the time-out always raises, the
+        counts go through the saturation policy."""
+        h = self._health_last = self._health_dict(words)
+        if h["timed_out"]:
+            raise RuntimeError("fused MLP one-launch step: an in-launch hand-off timed out")
+        sat, bad = h["saturated"], h["nonfinite"]
+        policy = self.saturation_policy or get_config().mlp_saturation
+        if policy == "ignore" or (sat == 0 and bad == 0):
+            return
+        if policy == "raise":
+            raise FusedStepNumericsError(sat, bad, h["last_step"])
+        seen = self._health_reported
+        if sat > seen[0] or bad > seen[1]:  # one warning per check that sees a count grow
+            self._health_reported = (sat, bad)
+            log.warning(FusedStepNumericsError.describe(sat, bad, h["last_step"]))
+
+    def health(self, blocking: bool = True) -> Dict[str, object]:
+        """What the step kernels counted since the engine was built (or ``reset_health``):
+        ``saturated`` -- layer-1 tile partials beyond +-32 that the 12.20 fixed point
+        replaced by the clamp; ``nonfinite`` -- NaN / Inf partials (which the conversion
+        turns into a finite +-32, so the loss stays finite); ``last_step`` -- the latest
+        optimizer step whose launch counted one (0: none, or the priming before step 1);
+        ``timed_out`` -- the hand-off error word.  Exact device-side counts: they include
+        graph replays.  ``blocking=False``: the last reading a ``check`` made, no sync.
+        The CPU reference engine sums in fp32: all zeros."""
+        if not self.native:
+            return {"saturated": 0, "nonfinite": 0, "last_step": 0, "timed_out": False}
+        if not blocking:
+            return dict(self._health_last)
+        self._health_last = self._health_dict(self.hand[self._hl["err"]:self._hl["last_step"] + 1].tolist())
+        return dict(self._health_last)
+
+    def reset_health(self) -> None:
+        """Zero the saturation / non-finite counts and the last affected step
+        (stream-ordered; the time-out word stays).  A reading still in flight from
+        ``check(blocking=False)`` is dropped: it predates the reset."""
+        if self.native:
+            self.hand[self._hl["sat"]:self._hl["last_step"] + 1].zero_()
+        self._hand_probe = None
+        self._health_reported = (0, 0)
+        self._health_last = {"saturated": 0, "nonfinite": 0, "last_step": 0,
+                             "timed_out": bool(self._health_last["timed_out"])}
 
     def set_step(self, step: int) -> None:
         self.counters[0] = int(step)
