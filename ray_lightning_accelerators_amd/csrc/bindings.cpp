@@ -710,6 +710,10 @@ void bn_bwd_apply(Tensor x, optional<Tensor> y, Tensor dy, Tensor coef, bool rel
   bn_same(x, dx, "dx", C);
   const uint16_t* yp = nullptr;
   const float* ssp = relu ? bn_ss(ss, C) : nullptr;
+  // the recomputed mask has no dres variant: with one the launcher picks a y-masked
+  // kernel, and y is not taken when the stats are given
+  TORCH_CHECK(!(ssp && dres.has_value() && dres->defined()),
+              "bn_bwd_apply: ReLU recomputed from the forward stats cannot write dres; pass y instead of ss");
   if (relu && !ssp) {
     TORCH_CHECK(y.has_value(), "ReLU backward needs the saved output y (or the forward stats)");
     bn_same(x, *y, "y", C);

@@ -60,12 +60,15 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const uint16_t* __rest
   const int n = (int)(p / OH);
   f8 m;
   uint8_t a[8];
+  const int h0 = oh * s - pad, w0 = ow * s - pad;
+  // a window of -inf only keeps its first element INSIDE the image, as PyTorch does
+  // (2 * pad <= k: there is one); position 0 may be padding, which the backward never visits
+  const uint8_t first = (uint8_t)((h0 < 0 ? -h0 : 0) * k + (w0 < 0 ? -w0 : 0));
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
     m[c] = -INFINITY;
-    a[c] = 0;
+    a[c] = first;
   }
-  const int h0 = oh * s - pad, w0 = ow * s - pad;
   for (int kh = 0; kh < k; ++kh) {
     const int h = h0 + kh;
     if (h < 0 || h >= H) continue;
