@@ -37,6 +37,14 @@ T* ptr_or_null(const optional<Tensor>& t, const char* name, at::ScalarType dt, i
   return reinterpret_cast<T*>(t->data_ptr());
 }
 
+// The flat-arena kernels read and write float4 / packed bf16x4 (uint2) through
+// reinterpret_cast: an operand off that alignment must never reach a launch.
+void check_aligned(const Tensor& t, const char* name, size_t bytes) {
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % bytes == 0, name, " must be ", bytes,
+              "-byte aligned (storage offset ", t.storage_offset(), "): pass a view that starts at a multiple of ",
+              bytes / t.element_size(), " elements");
+}
+
 void adam_step(Tensor p, Tensor g, Tensor m, Tensor v, optional<Tensor> p_bf16, double lr,
                double beta1, double beta2, double eps, double weight_decay, double grad_scale,
                bool adamw, bool maximize, optional<Tensor> step, int64_t host_step,
@@ -45,6 +53,10 @@ void adam_step(Tensor p, Tensor g, Tensor m, Tensor v, optional<Tensor> p_bf16, 
   check_dev(g, "grad", at::kFloat);
   check_dev(m, "exp_avg", at::kFloat);
   check_dev(v, "exp_avg_sq", at::kFloat);
+  check_aligned(p, "param", 16);
+  check_aligned(g, "grad", 16);
+  check_aligned(m, "exp_avg", 16);
+  check_aligned(v, "exp_avg_sq", 16);
   const int64_t n = p.numel();
   TORCH_CHECK(g.numel() == n && m.numel() == n && v.numel() == n, "adam arena size mismatch");
   const at::hip::HIPGuardMasqueradingAsCUDA guard(p.device());
@@ -54,6 +66,7 @@ void adam_step(Tensor p, Tensor g, Tensor m, Tensor v, optional<Tensor> p_bf16, 
   a.m = m.data_ptr<float>();
   a.v = v.data_ptr<float>();
   a.p_bf16 = ptr_or_null<uint16_t>(p_bf16, "param_bf16", at::kBFloat16, n);
+  if (a.p_bf16) check_aligned(*p_bf16, "param_bf16", 8);
   a.n = n;
   a.lr = (float)lr; a.beta1 = (float)beta1; a.beta2 = (float)beta2; a.eps = (float)eps;
   a.weight_decay = (float)weight_decay; a.grad_scale = (float)grad_scale;
@@ -71,6 +84,8 @@ void sgd_step(Tensor p, Tensor g, optional<Tensor> buf, optional<Tensor> p_bf16,
               optional<Tensor> lr_t) {
   check_dev(p, "param", at::kFloat);
   check_dev(g, "grad", at::kFloat);
+  check_aligned(p, "param", 16);
+  check_aligned(g, "grad", 16);
   const int64_t n = p.numel();
   TORCH_CHECK(g.numel() == n, "sgd arena size mismatch");
   const at::hip::HIPGuardMasqueradingAsCUDA guard(p.device());
@@ -79,7 +94,9 @@ void sgd_step(Tensor p, Tensor g, optional<Tensor> buf, optional<Tensor> p_bf16,
   a.g = g.data_ptr<float>();
   a.buf = ptr_or_null<float>(buf, "momentum_buffer", at::kFloat, n);
   TORCH_CHECK(momentum == 0.0 || a.buf != nullptr, "sgd: momentum needs a buffer");
+  if (a.buf) check_aligned(*buf, "momentum_buffer", 16);
   a.p_bf16 = ptr_or_null<uint16_t>(p_bf16, "param_bf16", at::kBFloat16, n);
+  if (a.p_bf16) check_aligned(*p_bf16, "param_bf16", 8);
   a.n = n;
   a.lr = (float)lr; a.momentum = (float)momentum; a.dampening = (float)dampening;
   a.weight_decay = (float)weight_decay; a.grad_scale = (float)grad_scale;
@@ -100,12 +117,14 @@ void multi_copy(Tensor table, double scale, bool accumulate) {
 
 void scale_(Tensor x, double s) {
   check_dev(x, "x", at::kFloat);
+  check_aligned(x, "x", 16);
   const at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   rla::launch_scale(x.data_ptr<float>(), x.numel(), (float)s, cur_stream(x));
 }
 
 Tensor sumsq(Tensor x) {
   check_dev(x, "x", at::kFloat);
+  check_aligned(x, "x", 16);
   const at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   Tensor out = at::empty({1}, x.options());
   rla::launch_sumsq(x.data_ptr<float>(), x.numel(), out.data_ptr<float>(), cur_stream(x));

@@ -110,6 +110,8 @@ class _FusionState:
             return None
         srt = sorted(gs, key=lambda g: g.data_ptr())
         base = srt[0]
+        if base.data_ptr() % 16:
+            return None  # ops.scale_ needs a float4-aligned arena: pack into a fresh buffer instead
         end = base.data_ptr()
         for g in srt:
             if g.data_ptr() != end:

@@ -42,6 +42,13 @@ def fused_adam_(
 
     ``step`` is the 1-based step number AFTER this update (torch semantics), a
     Python int or a device int64 tensor (graph-replay friendly).
+
+    Alignment contract (GPU): the kernel reads and writes float4s and stores the
+    shadow as packed bf16x4, so ``p``, ``g``, ``m`` and ``v`` must start on a 16-byte
+    boundary and ``p_bf16`` on an 8-byte one -- a view into an arena must start at a
+    multiple of 4 elements, which ``ParamArena(align=4)`` guarantees.  Anything else
+    raises ``RuntimeError`` naming the operand before a launch is issued.  ``n`` itself
+    is free: the last ``n % 4`` elements take a scalar tail.
     """
     if use_native(p):
         step_t, host_step = _step_args(step)
@@ -89,7 +96,12 @@ def fused_sgd_(
     lr_tensor: Optional[torch.Tensor] = None,
     p_bf16: Optional[torch.Tensor] = None,
 ) -> None:
-    """One SGD step (torch.optim.SGD semantics) over flat fp32 arenas."""
+    """One SGD step (torch.optim.SGD semantics) over flat fp32 arenas.
+
+    ``step <= 1`` overwrites the momentum buffer with the gradient, later steps blend
+    it.  Alignment contract (GPU) as :func:`fused_adam_`: ``p``, ``g`` and ``buf`` on a
+    16-byte boundary, ``p_bf16`` on an 8-byte one, else ``RuntimeError``.
+    """
     if use_native(p):
         step_t, host_step = _step_args(step)
         require().sgd_step(
@@ -166,7 +178,11 @@ def multi_copy(
     accumulate: bool = False,
     table: Optional[torch.Tensor] = None,
 ) -> None:
-    """dst (+)= src * scale for every pair, casting fp32<->bf16, in ONE launch on GPU."""
+    """dst (+)= src * scale for every pair, casting fp32<->bf16, in ONE launch on GPU.
+
+    No alignment requirement: each chunk takes the float4 path only when both of its
+    addresses are 16-byte aligned fp32, and an element-wise path otherwise.
+    """
     if not pairs:
         return
     if use_native(pairs[0][0]):
@@ -183,6 +199,8 @@ def multi_copy(
 
 
 def scale_(x: torch.Tensor, s: float) -> None:
+    """x *= s in place.  GPU: ``x`` must start on a 16-byte boundary (float4 accesses; a view
+    at a multiple of 4 elements of an arena does), else ``RuntimeError``."""
     if use_native(x):
         require().scale_(x, float(s))
     else:
@@ -190,6 +208,7 @@ def scale_(x: torch.Tensor, s: float) -> None:
 
 
 def sumsq(x: torch.Tensor) -> torch.Tensor:
+    """sum(x^2) as a one-element tensor.  GPU: the same 16-byte contract as :func:`scale_`."""
     if use_native(x):
         return require().sumsq(x)
     return (x.float() * x.float()).sum().reshape(1)
