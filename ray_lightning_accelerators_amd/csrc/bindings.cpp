@@ -1149,6 +1149,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     d["last_step"] = h.last_step; d["words"] = h.words;
     return d;
   });
+  m.def("mlp3_adam_cache_layout", []() {
+    const rla::MLP3AdamCacheLayout c = rla::mlp3_adam_cache_layout();
+    py::dict d;
+    d["step"] = c.step; d["betas"] = c.betas; d["bc1"] = c.bc1; d["bc2_sqrt"] = c.bc2_sqrt;
+    return d;
+  });
   m.def("mlp3_h1_copies", [](int64_t l1) { return rla::mlp3_h1_copies((int)l1); },
         "H1pre copies per ring slot of the v3 step (the layer-1 partials' atomic fan-in is split over them)");
   m.def("mlp3_dp_area_floats", []() { return rla::comm::kDpUnitAreaFloats; },

@@ -279,6 +279,13 @@ struct MLP3HandLayout {
   int ack, err, sat, nonfinite, last_step, words;
 };
 MLP3HandLayout mlp3_hand_layout();
+// further words of `hand`: the one-launch step's cache of Adam's bias corrections for the
+// next step -- key (step, bits(beta1) | bits(beta2) << 32), 1 - beta1^step and
+// sqrt(1 - beta2^step) as f64 bits (mlp_step3.hip)
+struct MLP3AdamCacheLayout {
+  int step, betas, bc1, bc2_sqrt;
+};
+MLP3AdamCacheLayout mlp3_adam_cache_layout();
 int launch_mlp3(const MLP3Args& a, int kind, hipStream_t stream);
 
 int mlp3_act_rows(int L1, int L2);

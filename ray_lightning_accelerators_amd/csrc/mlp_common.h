@@ -36,6 +36,37 @@ __device__ __forceinline__ void adam_scalars(AdamScal& o, int64_t t, float lr, f
   o.beta1 = b1; o.beta2 = b2; o.eps = eps; o.wd = wd; o.adamw = adamw;
 }
 
+// The part of adam_scalars that depends on (t, beta1, beta2) only -- the two pow() --
+// as the one-launch step caches it from one step to the next (mlp_step3.hip, "Adam
+// bias-correction cache"): bc1 = 1 - beta1^t and sqrt(1 - beta2^t), both in double.
+struct AdamBias {
+  double bc1, bc2_sqrt;
+};
+
+// Both powers in ONE instruction stream: lane 0 of the wave evaluates pow(beta1, t),
+// lane 1 pow(beta2, t) (one pow()'s dependent chain where adam_scalars has two),
+// and every calling lane receives both through readlane (no LDS round trip).  Each
+// lane runs the same pow() on the same arguments as adam_scalars, so the bits are
+// adam_scalars' bits.  Call with (at least) lanes 0 and 1 of the wave active.
+__device__ __forceinline__ AdamBias adam_bias2(int64_t t, float b1, float b2) {
+  const bool first = (threadIdx.x & 63) == 0;
+  const double p = pow((double)(first ? b1 : b2), (double)t);
+  const int lo = __double2loint(p), hi = __double2hiint(p);
+  const double p1 = __hiloint2double(__builtin_amdgcn_readlane(hi, 0), __builtin_amdgcn_readlane(lo, 0));
+  const double p2 = __hiloint2double(__builtin_amdgcn_readlane(hi, 1), __builtin_amdgcn_readlane(lo, 1));
+  return AdamBias{1.0 - p1, sqrt(1.0 - p2)};
+}
+
+// adam_scalars with the bias corrections given: the learning rate is applied here
+// (it may change between any two steps), the same operations on the same doubles.
+__device__ __forceinline__ void adam_scalars_bias(AdamScal& o, const AdamBias& c, float lr, float b1, float b2,
+                                                  float eps, float wd, int adamw) {
+  o.lr = lr;
+  o.step_size = (float)((double)lr / c.bc1);
+  o.bc2_sqrt = (float)c.bc2_sqrt;
+  o.beta1 = b1; o.beta2 = b2; o.eps = eps; o.wd = wd; o.adamw = adamw;
+}
+
 // Explicit FMAs and no compiler contraction: every kernel that inlines this (tail
 // epilogues, the one-launch step's tiles, the arena Adam) computes the same bits.
 __device__ __forceinline__ float adam1(float p, float g, float& m, float& v, const AdamScal& o) {

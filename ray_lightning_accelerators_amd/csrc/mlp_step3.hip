@@ -198,6 +198,27 @@ constexpr int kHandSat = 17, kHandNonFinite = 18, kHandLastStep = 19;
 static_assert(kHandLastStep < kHandWords, "health words inside the hand buffer");
 constexpr float kH1Sat = 32.0f;  // == kFixSat / kFix
 
+// Adam bias-correction cache of the one-launch step (mlp3_adam_cache_layout).  The two
+// double-precision pow() of adam_scalars depend on (t, beta1, beta2) only, and step
+// t + 1's are known during step t: block 0 computes them once per launch, off every
+// chain, and parks them here for the next launch's other blocks, which evaluated them
+// on thread 0 ahead of their head-pass loads before (profiles/r11_adam_cache).
+//   hand[kHandAdamStep]   key: the optimizer step the entry is for (0: no entry),
+//   hand[kHandAdamBetas]  key: bits(beta1) | bits(beta2) << 32,
+//   hand[kHandAdamBc1]    1 - beta1^t as f64 bits,
+//   hand[kHandAdamBc2]    sqrt(1 - beta2^t) as f64 bits.
+// The learning rate is not part of it: it may change between any two steps.  A reader
+// whose (step, betas) differ from the key computes the values itself, so nothing on
+// the host invalidates the entry: a fresh buffer, set_step, a checkpoint load, a
+// two-launch step or other betas just miss once.  Same ordering rule as the counters:
+// read through the scalar path before the block's acknowledgement, written by block 0
+// after every block's acknowledgement.
+constexpr int kHandAdamStep = 20, kHandAdamBetas = 21, kHandAdamBc1 = 22, kHandAdamBc2 = 23;
+static_assert(kHandAdamStep > kHandLastStep && kHandAdamBc2 < kHandWords, "cache words are spare words of hand");
+__device__ __forceinline__ unsigned long long adam_betas_key(float b1, float b2) {
+  return (unsigned long long)__float_as_uint(b1) | ((unsigned long long)__float_as_uint(b2) << 32);
+}
+
 struct H1Health {
   unsigned sat = 0u, bad = 0u;  // wave-uniform
 };
@@ -985,9 +1006,19 @@ __device__ __forceinline__ void small_finalize(const MLP3Args& a, bool adam, con
   if (adam && r.kind == 1) *reinterpret_cast<bf16x4*>(SHW + O::W3T + (int64_t)r.colv * 16 + r.rowv) = sh4;
 }
 
-// Owner protocol: r.v[] already holds the new fp32 weights (from the owner's Adam or
-// its all-gather); store them and the bf16 shadows, and m / v where this rank owns
-// the task (r.mv / r.vv advanced by the owner's Adam).
+// small_finalize's Adam without its stores (the one-launch step: ahead of the
+// acknowledgement wait): r.v[] gradient -> new fp32 weight, r.mv / r.vv advanced.
+// Same adam1 per element, so small_adam + small_store writes small_finalize's bits.
+__device__ __forceinline__ void small_adam(SmallRes& r, const AdamScal& o) {
+  if (r.kind < 0) return;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    if (r.valid[i]) r.v[i] = adam1(r.pv[i], r.v[i], r.mv[i], r.vv[i], o);
+}
+
+// r.v[] already holds the new fp32 weights (from small_adam, the owner's Adam or its
+// all-gather); store them and the bf16 shadows, and m / v where this rank owns the
+// task (r.mv / r.vv advanced by that Adam).
 template <int L1, int L2>
 __device__ __forceinline__ void small_store(const MLP3Args& a, const SmallRes& r, bool store_mv) {
   using O = Off<L1, L2>;
@@ -1732,6 +1763,18 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
 // never wait.  Invariant kept by every step kind: the H1pre slot the tiles add
 // into (slot ^ 1) is zero when a step starts (block 0 / the two-launch tail
 // zero the consumed slot; prime zeroes both).
+//
+// Adam's scalars: every block but block 0 needs them for its tail role.  Their two
+// f64 pow() (~500 dependent instructions on one lane) used to run on thread 0 of each
+// of those blocks ahead of its head-pass loads; they depend on (t, betas) only, so
+// block 0 now evaluates step t + 1's once per launch (two lanes of an idle wave, while
+// wave 0 polls for the acknowledgements) and leaves them in `hand` under a (step,
+// betas) key -- see kHandAdamStep.  The other blocks read the entry with the counters
+// and, behind their last prologue load (end of the hook), only divide the learning rate
+// (never cached) by the bias correction; on a key mismatch they compute the pow()
+// themselves, there.  Bits as adam_scalars() in either case.
+// The small-parameter blocks run their Adam in registers before the acknowledgement
+// wait and only store after it.
 // ---------------------------------------------------------------------------
 template <int L1, int L2>
 struct One {
@@ -1812,6 +1855,11 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args a) {
   const int64_t c0 = ld_state(a.counters, 0), cursor = ld_state(a.counters, 1);
   const int64_t slot = ld_state(a.counters, 3), ob = ld_state(a.counters, 4);
   const int64_t seq = ld_state(a.counters, kSeq);
+  // the cached bias corrections and their key, written by the previous launch's block 0
+  const int64_t* hand_s = reinterpret_cast<const int64_t*>(a.hand);
+  const int64_t ck_step = ld_state(hand_s, kHandAdamStep), ck_betas = ld_state(hand_s, kHandAdamBetas);
+  const int64_t ck_bc1 = ld_state(hand_s, kHandAdamBc1), ck_bc2 = ld_state(hand_s, kHandAdamBc2);
+  const int64_t t_adam = a.advance_step ? c0 + 1 : c0;  // the step this launch's Adam belongs to
   const uint32_t dgen = DP ? dp_gen_now(a) : 0u;
   const int B = a.B;
 
@@ -1855,10 +1903,24 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args a) {
     p4 = *reinterpret_cast<const F4*>(a.params + gidx);
     m4 = *reinterpret_cast<const F4*>(a.exp_avg + gidx);
     v4 = *reinterpret_cast<const F4*>(a.exp_avg_sq + gidx);
+    // Adam's scalars, behind the wave's last load (they are needed after the head pass
+    // only): the bias corrections from the cache block 0 of the previous launch filled
+    // -- a wave-uniform branch on scalar loads, consumed before the block's
+    // acknowledgement -- and one f64 division for the learning rate, a few dozen
+    // instructions under the loads' round trip.  A miss (first step, set_step, another
+    // kind of step in between, other betas) evaluates the two pow() here, on two lanes:
+    // that one launch's first barrier waits for them (profiles/r7_softmax_lanes, variant A).
+    if (w == 0 && blk > 0) {
+      if (t_adam > 0 && ck_step == t_adam && ck_betas == (int64_t)adam_betas_key(a.beta1, a.beta2)) {
+        if (lane == 0)
+          adam_scalars_bias(*sh_o, AdamBias{__longlong_as_double(ck_bc1), __longlong_as_double(ck_bc2)}, lr_now,
+                            a.beta1, a.beta2, a.eps, a.weight_decay, a.adamw);
+      } else if (lane < 2) {
+        const AdamBias bc = adam_bias2(t_adam, a.beta1, a.beta2);
+        if (lane == 0) adam_scalars_bias(*sh_o, bc, lr_now, a.beta1, a.beta2, a.eps, a.weight_decay, a.adamw);
+      }
+    }
   };
-  if (tid == 0 && blk > 0)
-    adam_scalars(*sh_o, a.advance_step ? c0 + 1 : c0, lr_now, a.beta1, a.beta2, a.eps, a.weight_decay, a.adamw);
-
   // ---- the serial chain, on this CU (tile wave 0 also issues the next batch's loads) ----
   head_body<32, L1, L2, false, true>(a, smem, &pre, hook);
 
@@ -2012,16 +2074,32 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args a) {
       }
       dp_end_nosync(a, gen, fail);
     }
+    // every protocol: Adam in registers BEFORE the acknowledgement wait (it needs only
+    // this wave's gradient and its prefetched state), the stores after it
+    if (!adam_done) small_adam(r, *sh_o);
+    // (asking for the acknowledgement count ahead of small_compute, to hide the poll's
+    // round trip, cost the step 0.35 us: profiles/r11_adam_cache)
     one_wait_acks(a, seq, &sh_fail);  // every block has read the weights / biases this overwrites
-    if (adam_done) small_store<L1, L2>(a, r, store_mv);  // r.v: the new weights
-    else small_finalize<L1, L2>(a, true, r, *sh_o);
+    small_store<L1, L2>(a, r, store_mv);  // r.v: the new weights
     stamp_max(a, 6);  // probe builds: the latest small-parameter block end
   } else {
     // block 0: stats, the consumed H1pre slot zeroed (the invariant), then the advanced state
     // the rows' parked loss stats, summed by wave 0 before it polls for the acks
     HeadStats hs{0.f, 0.f, 0.f};
     if (w == 0) hs = head_stats((const float*)(smem + C::oZ));
+    // the NEXT step's bias corrections, once for all its blocks: wave 1 (two lanes)
+    // evaluates the pow() while wave 0 polls -- after this block's head pass and its
+    // acknowledgement, inside the ~1 us block 0 waits for the other blocks' anyway
+    const int64_t t_next = a.advance_step ? t_adam + 1 : t_adam;
+    AdamBias nbc{0.0, 0.0};
+    if (w == 1 && lane < 2) nbc = adam_bias2(t_next, a.beta1, a.beta2);
     one_wait_acks(a, seq, &sh_fail);
+    if (tid == 64) {  // every block has consumed the previous entry
+      a.hand[kHandAdamStep] = (unsigned long long)t_next;
+      a.hand[kHandAdamBetas] = adam_betas_key(a.beta1, a.beta2);
+      a.hand[kHandAdamBc1] = (unsigned long long)__double_as_longlong(nbc.bc1);
+      a.hand[kHandAdamBc2] = (unsigned long long)__double_as_longlong(nbc.bc2_sqrt);
+    }
     uint4* z = reinterpret_cast<uint4*>(a.h1pre + slot * H1Copies<L1>::G * (int64_t)Bp * L1);
     for (int i = tid; i < H1Copies<L1>::G * Bp * L1 / 4; i += kThreads) z[i] = make_uint4(0u, 0u, 0u, 0u);
     if (tid == 0) {
@@ -2127,6 +2205,7 @@ int64_t mlp3_hand_words(int, int) { return kHandWords; }
 MLP3HandLayout mlp3_hand_layout() {
   return {kHandAck, kHandErr, kHandSat, kHandNonFinite, kHandLastStep, kHandWords};
 }
+MLP3AdamCacheLayout mlp3_adam_cache_layout() { return {kHandAdamStep, kHandAdamBetas, kHandAdamBc1, kHandAdamBc2}; }
 
 int launch_mlp3(const MLP3Args& a, int kind, hipStream_t stream) {
   if (a.B > kBMax || a.B < 1) return -2;

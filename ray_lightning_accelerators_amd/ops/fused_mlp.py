@@ -209,6 +209,24 @@ def mlp3_hand_layout(native: bool = True) -> Dict[str, int]:
     return dict(_hand_layout)
 
 
+# further words of ``hand``: the one-launch step's cache of Adam's bias corrections for
+# the NEXT step (csrc/mlp_step3.hip, ``_C.mlp3_adam_cache_layout()``).  ``step`` and
+# ``betas`` (bits(beta1) | bits(beta2) << 32) are the key; ``bc1`` holds 1 - beta1^step and
+# ``bc2_sqrt`` sqrt(1 - beta2^step), both as f64 bits.  A launch whose step or betas
+# differ from the key ignores the entry and computes the values itself.
+ADAM_CACHE_LAYOUT = {"step": 20, "betas": 21, "bc1": 22, "bc2_sqrt": 23}
+
+
+def mlp3_adam_cache_layout(native: bool = True) -> Dict[str, int]:
+    """Word indices of the bias-correction cache in ``hand`` (kept apart from
+    ``mlp3_hand_layout``, which describes the hand-off and health words)."""
+    if native:
+        lay = {k: int(v) for k, v in require().mlp3_adam_cache_layout().items()}
+        if lay != ADAM_CACHE_LAYOUT:
+            raise RuntimeError(f"Adam cache layout of the extension {lay} differs from ops.fused_mlp.ADAM_CACHE_LAYOUT")
+    return dict(ADAM_CACHE_LAYOUT)
+
+
 W1_TILES = IN_FEATURES // 16
 H1_SAT = 32.0  # |tile partial| beyond this is clamped by the 12.20 conversion
 
