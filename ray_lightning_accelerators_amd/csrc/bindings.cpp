@@ -775,7 +775,7 @@ Tensor conv_wgrad(Tensor dy, Tensor x, int64_t N, int64_t H, int64_t W, int64_t 
   const rla::WgradPlan plan = rla::wgrad_plan(g, (int)splits, (int)algo);
   const float* pre = nullptr;
   if (pre_ss.has_value() && pre_ss->defined()) {
-    // x is a deferred BatchNorm + ReLU's input: the generic kernel stages the activation
+    // x is a deferred BatchNorm + ReLU's input: the kernel of the plan (generic or halo) stages the activation
     check_dev(*pre_ss, "pre_ss", at::kFloat);
     TORCH_CHECK(pre_ss->is_contiguous() && pre_ss->dim() == 2 && pre_ss->size(0) == 4 && pre_ss->size(1) == Cin,
                 "conv_wgrad: pre_ss must be [4, Cin] contiguous fp32");

@@ -321,8 +321,9 @@ struct WgradPlan {
 // splits <= 0: automatic; algo 0: the halo kernel when the geometry allows, 1: generic
 WgradPlan wgrad_plan(const WgradGeom& g, int splits, int algo = 0);
 // part: splits * Cout * KH * KW * Cin floats when plan.splits > 1 (else unused)
-// pre_ss ([4, Cin] BatchNorm stats; generic 1x1 / stride-1 plans only): x is a deferred
-// BatchNorm + ReLU's input, staged as bf16(relu(x * scale + shift))
+// pre_ss ([4, Cin] BatchNorm stats; every plan: the generic kernel at any filter, stride and
+// padding, and the halo kernel): x is a deferred BatchNorm + ReLU's input, staged as
+// bf16(relu(x * scale + shift)) inside the image; zero-padding taps stay zero
 void launch_wgrad(const uint16_t* dy, const uint16_t* x, float* out, float* part, const WgradGeom& g,
                   const WgradPlan& p, hipStream_t stream, const float* pre_ss = nullptr);
 

@@ -171,8 +171,9 @@ def wgrad_hip(dy: torch.Tensor, x: torch.Tensor, kernel_size, stride, padding, s
     gradient [Cout, Cin, KH, KW] with channels_last strides (the kernel writes the
     [Cout, KH, KW, Cin] memory order directly).  ``algo`` 0: the 3x3 / stride-1 /
     pad-1 halo kernel where it applies, else the generic one; 1: always generic.
-    ``pre_ss`` (1x1 / stride 1): ``x`` is a deferred BatchNorm + ReLU's input and the
-    kernel stages relu(x * scale + shift) (ops/bn.py DeferredApply)."""
+    ``pre_ss`` (either kernel, any geometry): ``x`` is a deferred BatchNorm + ReLU's input
+    and the kernel stages relu(x * scale + shift) inside the image, zero in the padding
+    (ops/bn.py DeferredApply)."""
     from . import require
 
     n, cin, h, w = x.shape
