@@ -4,10 +4,8 @@
 // before launching: a hand-written kernel must never see a shape it was not
 // built for (an out-of-bounds access can reset every GPU of the host).
 #include <torch/extension.h>
+#include <algorithm>
 #include <cstdlib>
-#include <map>
-#include <mutex>
-#include <tuple>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
@@ -43,6 +41,17 @@ void check_aligned(const Tensor& t, const char* name, size_t bytes) {
   TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % bytes == 0, name, " must be ", bytes,
               "-byte aligned (storage offset ", t.storage_offset(), "): pass a view that starts at a multiple of ",
               bytes / t.element_size(), " elements");
+}
+
+// A required bf16 operand of the NHWC convolution / pooling bindings: contiguous, exactly
+// `numel` elements, on the GPU of `like` (the binding's first operand) and aligned for the
+// kernels' 16-byte fragment reads (`align`: a kernel that reads narrower words)
+uint16_t* bf16_operand(const Tensor& t, const char* name, int64_t numel, const Tensor& like, size_t align = 16) {
+  check_dev(t, name, at::kBFloat16);
+  TORCH_CHECK(t.device() == like.device(), name, " must be on ", like.device(), ", not ", t.device());
+  TORCH_CHECK(t.numel() == numel, name, " has ", t.numel(), " elements, expected ", numel);
+  check_aligned(t, name, align);
+  return reinterpret_cast<uint16_t*>(t.data_ptr());
 }
 
 void adam_step(Tensor p, Tensor g, Tensor m, Tensor v, optional<Tensor> p_bf16, double lr,
@@ -390,7 +399,7 @@ int64_t bn_rows(const Tensor& x, const char* name, int64_t C) {
   TORCH_CHECK(C > 0 && C % 8 == 0 && C <= rla::kBnMaxC, "fused BN: C must be a multiple of 8 and <= ",
               rla::kBnMaxC, ", got ", C);
   TORCH_CHECK(x.dim() >= 1 && x.size(-1) == C, name, " must have C=", C, " as its innermost dimension");
-  TORCH_CHECK((reinterpret_cast<uintptr_t>(x.data_ptr()) & 15) == 0, name, " must be 16-byte aligned");
+  check_aligned(x, name, 16);
   return x.numel() / C;
 }
 
@@ -409,13 +418,14 @@ const uint16_t* bn_dy2(const Tensor& x, const optional<Tensor>& dy2, int64_t C) 
   return reinterpret_cast<const uint16_t*>(dy2->data_ptr());
 }
 
-// optional forward statistics [4, C] (mean, invstd, scale, shift): the backward's
-// ReLU mask is recomputed from x instead of read from the saved output y
-const float* bn_ss(const optional<Tensor>& ss, int64_t C) {
+// optional forward statistics [4, C] (mean, invstd, scale, shift) of a BatchNorm, on the GPU
+// of `like`: the backward's ReLU mask recomputed from x instead of read from the saved
+// output y, or a deferred BatchNorm + ReLU a conv / pool kernel applies to its input
+const float* stats4(const optional<Tensor>& ss, int64_t C, const Tensor& like, const char* name = "stats") {
   if (!ss.has_value() || !ss->defined()) return nullptr;
-  check_dev(*ss, "stats", at::kFloat);
-  TORCH_CHECK(ss->dim() == 2 && ss->size(0) == 4 && ss->size(1) == C && ss->is_contiguous(),
-              "stats must be a contiguous [4, C] fp32 tensor");
+  check_dev(*ss, name, at::kFloat);
+  TORCH_CHECK(ss->dim() == 2 && ss->size(0) == 4 && ss->size(1) == C && ss->device() == like.device(), name,
+              " must be a contiguous [4, C] fp32 tensor on ", like.device(), ", C = ", C);
   return ss->data_ptr<float>();
 }
 
@@ -503,7 +513,7 @@ Tensor bn_partial(Tensor x, optional<Tensor> y, optional<Tensor> dy, int64_t C, 
   }
   rla::launch_bn_partial(reinterpret_cast<const uint16_t*>(x.data_ptr()), yp, dyp, M, (int)C, (int)mode, relu,
                          plan, part.data_ptr<float>(), nbtp, cur_stream(x), mode == 1 ? bn_dy2(x, dy2, C) : nullptr,
-                         mode == 1 && relu ? bn_ss(ss, C) : nullptr, lv, doutp, pooled ? &pg : nullptr);
+                         mode == 1 && relu ? stats4(ss, C, x) : nullptr, lv, doutp, pooled ? &pg : nullptr);
   return tickets ? rows : part;
 }
 
@@ -558,30 +568,20 @@ Tensor bn_bwd_finalize(Tensor part, double count, optional<Tensor> weight, Tenso
 // x: [N, H, W, C] bf16 (NHWC view of a channels_last tensor); returns (y, argmax bytes)
 std::vector<Tensor> maxpool_fwd(Tensor x, int64_t k, int64_t s, int64_t pad, c10::optional<Tensor> bn_ss,
                                 c10::optional<Tensor> nbt_inc) {
-  check_dev(x, "x", at::kBFloat16);
-  const float* ss = nullptr;
-  int64_t* nbt = nullptr;
-  if (bn_ss.has_value() && bn_ss->defined()) {
-    check_dev(*bn_ss, "bn_ss", at::kFloat);
-    TORCH_CHECK(bn_ss->is_contiguous() && bn_ss->numel() == 4 * x.size(3), "maxpool: bn_ss must be [4, C]");
-    ss = bn_ss->data_ptr<float>();
-  }
-  if (nbt_inc.has_value() && nbt_inc->defined()) {
-    TORCH_CHECK(nbt_inc->is_cuda() && nbt_inc->scalar_type() == at::kLong, "maxpool: nbt_inc int64 on the GPU");
-    nbt = nbt_inc->data_ptr<int64_t>();
-  }
-  TORCH_CHECK(x.dim() == 4 && x.is_contiguous(), "maxpool: x must be a contiguous NHWC [N, H, W, C] view");
+  TORCH_CHECK(x.dim() == 4, "maxpool: x must be a contiguous NHWC [N, H, W, C] view");
+  const uint16_t* xp = bf16_operand(x, "maxpool: x", x.numel(), x);
   const int64_t N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
+  const float* ss = stats4(bn_ss, C, x, "maxpool: bn_ss");
+  int64_t* nbt = ptr_or_null<int64_t>(nbt_inc, "maxpool: nbt_inc", at::kLong, 1);
   TORCH_CHECK(C % 8 == 0 && k >= 1 && s >= 1 && pad >= 0 && 2 * pad <= k, "maxpool: unsupported geometry");
   const int64_t OH = (H + 2 * pad - k) / s + 1, OW = (W + 2 * pad - k) / s + 1;
   TORCH_CHECK(OH > 0 && OW > 0, "maxpool: empty output");
   const at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   Tensor y = at::empty({N, OH, OW, C}, x.options());
   Tensor arg = at::empty({N, OH, OW, C}, x.options().dtype(at::kByte));
-  TORCH_CHECK(rla::launch_maxpool_fwd(reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                                      reinterpret_cast<uint16_t*>(y.data_ptr()), arg.data_ptr<uint8_t>(), (int)N, (int)H,
-                                      (int)W, (int)C, (int)OH, (int)OW, (int)k, (int)s, (int)pad, cur_stream(x), ss,
-                                      nbt) == 0,
+  TORCH_CHECK(rla::launch_maxpool_fwd(xp, reinterpret_cast<uint16_t*>(y.data_ptr()), arg.data_ptr<uint8_t>(), (int)N,
+                                      (int)H, (int)W, (int)C, (int)OH, (int)OW, (int)k, (int)s, (int)pad,
+                                      cur_stream(x), ss, nbt) == 0,
               "maxpool forward launch failed");
   return {y, arg};
 }
@@ -655,15 +655,16 @@ void bn_apply(Tensor x, Tensor scale, Tensor shift, optional<Tensor> res, bool r
 // BWD): dy1 [M, K], wt [N, K] (the weight transposed), dy2 / yb / xb [M, N]; returns
 // (d [M, N] bf16, part [rows, 2, N] fp32 for bn_bwd_finalize)
 std::vector<Tensor> conv1x1_bn_bwd(Tensor dy1, Tensor wt, Tensor dy2, Tensor yb, Tensor xb) {
-  for (const Tensor* t : {&dy1, &wt, &dy2, &yb, &xb}) {
-    check_dev(*t, "conv1x1_bn_bwd operand", at::kBFloat16);
-    TORCH_CHECK(t->dim() == 2 && t->is_contiguous() && reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
-                "conv1x1_bn_bwd: contiguous 16-byte aligned 2-D operands");
-  }
+  TORCH_CHECK(dy1.dim() == 2 && wt.dim() == 2 && wt.size(1) == dy1.size(1),
+              "conv1x1_bn_bwd: dy1 must be [M, K] and wt [N, K]");
   const int64_t M = dy1.size(0), K = dy1.size(1), N = wt.size(0);
-  TORCH_CHECK(wt.size(1) == K, "conv1x1_bn_bwd: wt must be [N, K]");
   for (const Tensor* t : {&dy2, &yb, &xb})
-    TORCH_CHECK(t->size(0) == M && t->size(1) == N, "conv1x1_bn_bwd: dy2 / yb / xb must be [M, N]");
+    TORCH_CHECK(t->dim() == 2 && t->size(0) == M && t->size(1) == N, "conv1x1_bn_bwd: dy2 / yb / xb must be [M, N]");
+  const uint16_t* dy1p = bf16_operand(dy1, "conv1x1_bn_bwd: dy1", M * K, dy1);
+  const uint16_t* wtp = bf16_operand(wt, "conv1x1_bn_bwd: wt", N * K, dy1);
+  const uint16_t* dy2p = bf16_operand(dy2, "conv1x1_bn_bwd: dy2", M * N, dy1);
+  const uint16_t* ybp = bf16_operand(yb, "conv1x1_bn_bwd: yb", M * N, dy1);
+  const uint16_t* xbp = bf16_operand(xb, "conv1x1_bn_bwd: xb", M * N, dy1);
   TORCH_CHECK(rla::conv1x1_bn_bwd_ok(M, (int)K, (int)N), "conv1x1_bn_bwd: unsupported shape (K <= 128)");
   const at::hip::HIPGuardMasqueradingAsCUDA guard(dy1.device());
   int rows = 0;
@@ -671,45 +672,29 @@ std::vector<Tensor> conv1x1_bn_bwd(Tensor dy1, Tensor wt, Tensor dy2, Tensor yb,
                              cur_stream(dy1));
   Tensor d = at::empty({M, N}, dy1.options());
   Tensor part = at::empty({rows, 2, N}, dy1.options().dtype(at::kFloat));
-  auto u = [](const Tensor& t) { return reinterpret_cast<const uint16_t*>(t.data_ptr()); };
-  rla::launch_conv1x1_bn_bwd(u(dy1), u(wt), reinterpret_cast<uint16_t*>(d.data_ptr()), M, (int)K, (int)N, u(dy2),
-                             u(yb), u(xb), part.data_ptr<float>(), &rows, cur_stream(dy1));
+  rla::launch_conv1x1_bn_bwd(dy1p, wtp, reinterpret_cast<uint16_t*>(d.data_ptr()), M, (int)K, (int)N, dy2p, ybp, xbp,
+                             part.data_ptr<float>(), &rows, cur_stream(dy1));
   return {d, part};
 }
 
 // 1x1 conv forward with BatchNorm partial sums: x [M, K] (NHWC rows), w [N, K], both
 // bf16 contiguous; returns (y [M, N] bf16, part [gx, 2, N] fp32 for bn_finalize)
 std::vector<Tensor> conv1x1_stats(Tensor x, Tensor w, optional<Tensor> pre_ss, optional<Tensor> nbt_inc) {
-  check_dev(x, "x", at::kBFloat16);
-  check_dev(w, "w", at::kBFloat16);
-  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.is_contiguous() && w.is_contiguous(),
-              "conv1x1_stats: x [M, K] and w [N, K] must be contiguous 2-D");
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && w.size(1) == x.size(1), "conv1x1_stats: x must be [M, K] and w [N, K]");
   const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
-  TORCH_CHECK(w.size(1) == K, "conv1x1_stats: w must be [N, K]");
+  const uint16_t* xp = bf16_operand(x, "conv1x1_stats: x", M * K, x);
+  const uint16_t* wp = bf16_operand(w, "conv1x1_stats: w", N * K, x);
   TORCH_CHECK(rla::conv1x1_stats_ok(M, (int)K, (int)N), "conv1x1_stats: unsupported shape (K % 32, N % 64)");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
-              "conv1x1_stats: 16-byte aligned operands");
-  const float* pre = nullptr;
-  int64_t* nbt = nullptr;
-  if (pre_ss.has_value() && pre_ss->defined()) {
-    // a deferred BatchNorm + ReLU on x: bn_finalize's [4, K] stats (rows 2 / 3 = scale / shift)
-    check_dev(*pre_ss, "pre_ss", at::kFloat);
-    TORCH_CHECK(pre_ss->is_contiguous() && pre_ss->dim() == 2 && pre_ss->size(0) == 4 && pre_ss->size(1) == K,
-                "conv1x1_stats: pre_ss must be [4, K] contiguous fp32");
-    TORCH_CHECK(rla::conv1x1_pre_ok(M, (int)K, (int)N), "conv1x1_stats: pre_ss needs K <= 512");
-    pre = pre_ss->data_ptr<float>();
-    if (nbt_inc.has_value() && nbt_inc->defined()) {
-      check_dev(*nbt_inc, "nbt_inc", at::kLong);
-      nbt = nbt_inc->data_ptr<int64_t>();
-    }
-  }
+  // a deferred BatchNorm + ReLU on x: bn_finalize's [4, K] stats (rows 2 / 3 = scale / shift)
+  const float* pre = stats4(pre_ss, K, x, "conv1x1_stats: pre_ss");
+  TORCH_CHECK(!pre || rla::conv1x1_pre_ok(M, (int)K, (int)N), "conv1x1_stats: pre_ss needs K <= 512");
+  int64_t* nbt = ptr_or_null<int64_t>(nbt_inc, "conv1x1_stats: nbt_inc", at::kLong, 1);
   const at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   const rla::Conv1x1Plan p = rla::conv1x1_stats_plan(M, (int)N);
   Tensor y = at::empty({M, N}, x.options());
   Tensor part = at::empty({p.gx, 2, N}, x.options().dtype(at::kFloat));
-  rla::launch_conv1x1_stats(reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                            reinterpret_cast<const uint16_t*>(w.data_ptr()), reinterpret_cast<uint16_t*>(y.data_ptr()),
-                            M, (int)K, (int)N, p, part.data_ptr<float>(), cur_stream(x), pre, nbt);
+  rla::launch_conv1x1_stats(xp, wp, reinterpret_cast<uint16_t*>(y.data_ptr()), M, (int)K, (int)N, p,
+                            part.data_ptr<float>(), cur_stream(x), pre, pre ? nbt : nullptr);
   return {y, part};
 }
 
@@ -728,7 +713,7 @@ void bn_bwd_apply(Tensor x, optional<Tensor> y, Tensor dy, Tensor coef, bool rel
   if (!pooled) bn_same(x, dy, "dy", C);
   bn_same(x, dx, "dx", C);
   const uint16_t* yp = nullptr;
-  const float* ssp = relu ? bn_ss(ss, C) : nullptr;
+  const float* ssp = relu ? stats4(ss, C, x) : nullptr;
   // the recomputed mask has no dres variant: with one the launcher picks a y-masked
   // kernel, and y is not taken when the stats are given
   TORCH_CHECK(!(ssp && dres.has_value() && dres->defined()),
@@ -750,53 +735,54 @@ void bn_bwd_apply(Tensor x, optional<Tensor> y, Tensor dy, Tensor coef, bool rel
                            ssp, pooled ? &pg : nullptr);
 }
 
+// ---- NHWC bf16 convolutions -----------------------------------------------------------
+// Every Python-visible function of a kernel family -- launch, *_supported / *_ok and
+// *_plan -- builds its geometry with the family's one builder (rla::conv3x3_geom,
+// rla::conv3x3s2_geom, rla::stem_geom, wgrad_geom below) and its operands with
+// bf16_operand / stats4 / ptr_or_null, so the three cannot disagree.
+
+// conv_wgrad's geometry from the binding's arguments, range-checked before the int casts
+rla::WgradGeom wgrad_geom(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t OH, int64_t OW, int64_t Cout,
+                          int64_t KH, int64_t KW, int64_t sh, int64_t sw, int64_t ph, int64_t pw) {
+  TORCH_CHECK(Cout % 64 == 0 && Cin % 64 == 0 && Cout > 0 && Cin > 0, "conv_wgrad: channels must be multiples of 64");
+  TORCH_CHECK(N > 0 && H > 0 && W > 0 && OH > 0 && OW > 0 && KH > 0 && KW > 0 && sh > 0 && sw > 0 && ph >= 0 &&
+                  pw >= 0 && std::max({N, H, W, Cin, OH, OW, Cout, KH, KW, sh, sw, ph, pw}) < (int64_t(1) << 30),
+              "conv_wgrad: bad geometry");
+  TORCH_CHECK((H + 2 * ph - KH) / sh + 1 == OH && (W + 2 * pw - KW) / sw + 1 == OW, "conv_wgrad: output size mismatch");
+  const int64_t px = std::max(OH * OW, H * W), lim = (int64_t(1) << 31) / 4;
+  TORCH_CHECK(px < lim && N * px < lim, "conv_wgrad: too many rows");
+  return rla::WgradGeom{(int)N, (int)H, (int)W, (int)Cin, (int)OH, (int)OW, (int)Cout, (int)KH, (int)KW,
+                        (int)sh, (int)sw, (int)ph, (int)pw};
+}
+
 // dW of an NHWC bf16 convolution (csrc/conv_wgrad.hip): dy [N, OH, OW, Cout] and
 // x [N, H, W, Cin] as contiguous NHWC memory; returns fp32 [Cout, KH, KW, Cin]
 // (the channels_last weight's memory order).
 Tensor conv_wgrad(Tensor dy, Tensor x, int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t OH, int64_t OW,
                   int64_t Cout, int64_t KH, int64_t KW, int64_t sh, int64_t sw, int64_t ph, int64_t pw,
                   int64_t splits, int64_t algo, optional<Tensor> pre_ss) {
-  TORCH_CHECK(dy.is_cuda() && x.is_cuda(), "conv_wgrad: GPU tensors");
   TORCH_CHECK(algo == 0 || algo == 1, "conv_wgrad: algo 0 (auto) or 1 (generic)");
-  TORCH_CHECK(dy.scalar_type() == at::kBFloat16 && x.scalar_type() == at::kBFloat16, "conv_wgrad: bf16 inputs");
-  TORCH_CHECK(dy.is_contiguous() && x.is_contiguous(), "conv_wgrad: contiguous NHWC memory");
-  TORCH_CHECK(Cout % 64 == 0 && Cin % 64 == 0 && Cout > 0 && Cin > 0, "conv_wgrad: channels must be multiples of 64");
-  TORCH_CHECK(N > 0 && H > 0 && W > 0 && OH > 0 && OW > 0 && KH > 0 && KW > 0 && sh > 0 && sw > 0 && ph >= 0 &&
-                  pw >= 0, "conv_wgrad: bad geometry");
-  TORCH_CHECK((H + 2 * ph - KH) / sh + 1 == OH && (W + 2 * pw - KW) / sw + 1 == OW, "conv_wgrad: output size mismatch");
-  TORCH_CHECK(dy.numel() == N * OH * OW * Cout, "conv_wgrad: dy has ", dy.numel(), " elements");
-  TORCH_CHECK(x.numel() == N * H * W * Cin, "conv_wgrad: x has ", x.numel(), " elements");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(dy.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
-              "conv_wgrad: 16-byte aligned inputs");
-  TORCH_CHECK(N * std::max(OH * OW, H * W) < (int64_t(1) << 31) / 4, "conv_wgrad: too many rows");
+  const rla::WgradGeom g = wgrad_geom(N, H, W, Cin, OH, OW, Cout, KH, KW, sh, sw, ph, pw);
+  const uint16_t* dyp = bf16_operand(dy, "conv_wgrad: dy", N * OH * OW * Cout, dy);
+  const uint16_t* xp = bf16_operand(x, "conv_wgrad: x", N * H * W * Cin, dy);
+  // x is a deferred BatchNorm + ReLU's input: the kernel of the plan (generic or halo) stages the activation
+  const float* pre = stats4(pre_ss, Cin, dy, "conv_wgrad: pre_ss");
+  TORCH_CHECK(!pre || Cin <= 4096, "conv_wgrad: pre_ss with Cin <= 4096");
   const at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
-  rla::WgradGeom g{(int)N, (int)H, (int)W, (int)Cin, (int)OH, (int)OW, (int)Cout, (int)KH, (int)KW,
-                   (int)sh, (int)sw, (int)ph, (int)pw};
   const rla::WgradPlan plan = rla::wgrad_plan(g, (int)splits, (int)algo);
-  const float* pre = nullptr;
-  if (pre_ss.has_value() && pre_ss->defined()) {
-    // x is a deferred BatchNorm + ReLU's input: the kernel of the plan (generic or halo) stages the activation
-    check_dev(*pre_ss, "pre_ss", at::kFloat);
-    TORCH_CHECK(pre_ss->is_contiguous() && pre_ss->dim() == 2 && pre_ss->size(0) == 4 && pre_ss->size(1) == Cin,
-                "conv_wgrad: pre_ss must be [4, Cin] contiguous fp32");
-    TORCH_CHECK(Cin <= 4096, "conv_wgrad: pre_ss with Cin <= 4096");
-    pre = pre_ss->data_ptr<float>();
-  }
   Tensor out = at::empty({Cout, KH, KW, Cin}, x.options().dtype(at::kFloat));
   Tensor part;
   if (plan.splits > 1) part = at::empty({(int64_t)plan.splits * Cout * KH * KW * Cin}, out.options());
-  rla::launch_wgrad(reinterpret_cast<const uint16_t*>(dy.data_ptr()), reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                    out.data_ptr<float>(), plan.splits > 1 ? part.data_ptr<float>() : nullptr, g, plan, cur_stream(x),
-                    pre);
+  rla::launch_wgrad(dyp, xp, out.data_ptr<float>(), plan.splits > 1 ? part.data_ptr<float>() : nullptr, g, plan,
+                    cur_stream(x), pre);
   return out;
 }
 
 std::vector<int64_t> conv_wgrad_plan(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t OH, int64_t OW,
                                      int64_t Cout, int64_t KH, int64_t KW, int64_t sh, int64_t sw, int64_t ph,
                                      int64_t pw, int64_t splits, int64_t algo) {
-  rla::WgradGeom g{(int)N, (int)H, (int)W, (int)Cin, (int)OH, (int)OW, (int)Cout, (int)KH, (int)KW,
-                   (int)sh, (int)sw, (int)ph, (int)pw};
-  const rla::WgradPlan p = rla::wgrad_plan(g, (int)splits, (int)algo);
+  const rla::WgradPlan p =
+      rla::wgrad_plan(wgrad_geom(N, H, W, Cin, OH, OW, Cout, KH, KW, sh, sw, ph, pw), (int)splits, (int)algo);
   return {p.kind, p.wa, p.wb, p.splits, p.rows_per_split};
 }
 
@@ -807,52 +793,21 @@ std::vector<int64_t> conv_wgrad_plan(int64_t N, int64_t H, int64_t W, int64_t Ci
 std::vector<Tensor> conv3x3_impl(Tensor x, Tensor w, int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout,
                                  bool flip, bool stats, optional<Tensor> pre_ss = {},
                                  optional<Tensor> nbt_inc = {}) {
-  TORCH_CHECK(x.is_cuda() && w.is_cuda(), "conv3x3: GPU tensors");
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16, "conv3x3: bf16 inputs");
-  TORCH_CHECK(x.is_contiguous() && w.is_contiguous(), "conv3x3: contiguous NHWC / [Cout,3,3,Cin] memory");
-  TORCH_CHECK(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv3x3: bad geometry");
-  TORCH_CHECK(x.numel() == N * H * W * Cin, "conv3x3: x has ", x.numel(), " elements");
-  TORCH_CHECK(w.numel() == Cout * 9 * Cin, "conv3x3: w has ", w.numel(), " elements");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
-              "conv3x3: 16-byte aligned inputs");
-  TORCH_CHECK(N * (H + 2) * (W + 2) < (int64_t(1) << 30), "conv3x3: too many pixels");
-  const at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
-  rla::Conv3x3Geom g{(int)N, (int)H, (int)W, (int)Cin, (int)Cout, 0,
-                     rla::conv3x3_pick_tm((int)N, (int)H, (int)W, (int)Cout),
-                     rla::conv3x3_wpb((int)N, (int)H, (int)W, (int)Cout)};
-  // vrows is a function of (N, H, W, tm, wpb) alone: a pinned plan CU count changes wpb, hence the key
-  static std::map<std::tuple<int64_t, int64_t, int64_t, int, int>, int> vrows_cache;
-  static std::mutex mu;
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    auto key = std::make_tuple(N, H, W, g.tm, g.wpb);
-    auto it = vrows_cache.find(key);
-    if (it == vrows_cache.end()) it = vrows_cache.emplace(key, rla::conv3x3_vrows(g)).first;
-    g.vrows = it->second;
-  }
+  const rla::Conv3x3Geom g = rla::conv3x3_geom(N, H, W, Cin, Cout);
   TORCH_CHECK(rla::conv3x3_ok(g), "conv3x3: unsupported shape (Cin % 16, Cout % 64, halo tile size)");
   TORCH_CHECK(!(flip && stats), "conv3x3: statistics are a forward epilogue");
-  const float* pre = nullptr;
-  int64_t* nbt = nullptr;
-  if (pre_ss.has_value() && pre_ss->defined()) {
-    // a deferred BatchNorm + ReLU on x (the statistics forward only)
-    check_dev(*pre_ss, "pre_ss", at::kFloat);
-    TORCH_CHECK(stats && pre_ss->is_contiguous() && pre_ss->dim() == 2 && pre_ss->size(0) == 4 &&
-                    pre_ss->size(1) == Cin && rla::conv3x3_pre_ok(g),
-                "conv3x3: pre_ss must be [4, Cin] fp32 (Cin <= 512) on the statistics forward");
-    pre = pre_ss->data_ptr<float>();
-    if (nbt_inc.has_value() && nbt_inc->defined()) {
-      check_dev(*nbt_inc, "nbt_inc", at::kLong);
-      nbt = nbt_inc->data_ptr<int64_t>();
-    }
-  }
+  const uint16_t* xp = bf16_operand(x, "conv3x3: x", N * H * W * Cin, x);
+  const uint16_t* wp = bf16_operand(w, "conv3x3: w", Cout * 9 * Cin, x);
+  // a deferred BatchNorm + ReLU on x (the statistics forward only)
+  const float* pre = stats4(pre_ss, Cin, x, "conv3x3: pre_ss");
+  TORCH_CHECK(!pre || (stats && rla::conv3x3_pre_ok(g)), "conv3x3: pre_ss (Cin <= 512) on the statistics forward only");
+  int64_t* nbt = ptr_or_null<int64_t>(nbt_inc, "conv3x3: nbt_inc", at::kLong, 1);
+  const at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   Tensor y = at::empty({N, H, W, Cout}, x.options());
   Tensor part;
   if (stats) part = at::empty({g.wpb, 2, Cout}, x.options().dtype(at::kFloat));
-  TORCH_CHECK(rla::launch_conv3x3(reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                                  reinterpret_cast<const uint16_t*>(w.data_ptr()),
-                                  reinterpret_cast<uint16_t*>(y.data_ptr()), g, flip, cur_stream(x),
-                                  stats ? part.data_ptr<float>() : nullptr, pre, nbt),
+  TORCH_CHECK(rla::launch_conv3x3(xp, wp, reinterpret_cast<uint16_t*>(y.data_ptr()), g, flip, cur_stream(x),
+                                  stats ? part.data_ptr<float>() : nullptr, pre, pre ? nbt : nullptr),
               "conv3x3: launch refused");
   if (stats) return {y, part};
   return {y};
@@ -867,126 +822,77 @@ std::vector<Tensor> conv3x3_stats(Tensor x, Tensor w, int64_t N, int64_t H, int6
   return conv3x3_impl(x, w, N, H, W, Cin, Cout, false, true, pre_ss, nbt_inc);
 }
 
+bool conv3x3_supported(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout) {
+  return rla::conv3x3_ok(rla::conv3x3_geom(N, H, W, Cin, Cout));
+}
+
 // The 3x3 / stride 1 / pad 1 input gradient with the PRECEDING BatchNorm + ReLU's backward
 // in its epilogue (csrc/conv3x3.hip BWD): dy [N, H, W, Cr], w the forward weight
 // [Cr, 3, 3, Co], xb [N, H, W, Co] that BatchNorm's input, ss its [4, Co] statistics.
 // Returns {d [N, H, W, Co] = (xb * scale + shift > 0 ? dx : 0), part [rows, 2, Co]}: the
 // sums of d and d * xb over each of the plan's pixel ranges (bn_bwd_finalize's input).
-rla::Conv3x3Geom conv3x3_dgrad_geom(int64_t N, int64_t H, int64_t W, int64_t Cr, int64_t Co) {
-  rla::Conv3x3Geom g{(int)N, (int)H, (int)W, (int)Cr, (int)Co, 0,
-                     rla::conv3x3_pick_tm((int)N, (int)H, (int)W, (int)Co),
-                     rla::conv3x3_wpb((int)N, (int)H, (int)W, (int)Co)};
-  // the partition walk once per (N, H, W, tm, wpb), as conv3x3_impl keeps it
-  static std::map<std::tuple<int64_t, int64_t, int64_t, int, int>, int> vrows_cache;
-  static std::mutex mu;
-  std::lock_guard<std::mutex> lk(mu);
-  auto key = std::make_tuple(N, H, W, g.tm, g.wpb);
-  auto it = vrows_cache.find(key);
-  if (it == vrows_cache.end()) it = vrows_cache.emplace(key, rla::conv3x3_vrows(g)).first;
-  g.vrows = it->second;
-  return g;
-}
-
 bool conv3x3_dgrad_bn_ok(int64_t N, int64_t H, int64_t W, int64_t Cr, int64_t Co) {
-  // conv3x3_supported's argument checks, then conv3x3_ok and the table limit on the cached geometry
-  if (N <= 0 || H <= 0 || W <= 0 || Cr <= 0 || Co <= 0 || N * (H + 2) * (W + 2) >= (int64_t(1) << 30)) return false;
-  return rla::conv3x3_bwd_ok(conv3x3_dgrad_geom(N, H, W, Cr, Co));
+  return rla::conv3x3_bwd_ok(rla::conv3x3_geom(N, H, W, Cr, Co));
 }
 
 std::vector<Tensor> conv3x3_dgrad_bn(Tensor dy, Tensor w, int64_t N, int64_t H, int64_t W, int64_t Cr, int64_t Co,
                                      Tensor xb, Tensor ss) {
-  TORCH_CHECK(dy.is_cuda() && w.is_cuda() && xb.is_cuda(), "conv3x3_dgrad_bn: GPU tensors");
-  TORCH_CHECK(dy.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16 &&
-                  xb.scalar_type() == at::kBFloat16,
-              "conv3x3_dgrad_bn: bf16 inputs");
-  TORCH_CHECK(dy.is_contiguous() && w.is_contiguous() && xb.is_contiguous(),
-              "conv3x3_dgrad_bn: contiguous NHWC / [Cr,3,3,Co] memory");
-  TORCH_CHECK(N > 0 && H > 0 && W > 0 && Cr > 0 && Co > 0, "conv3x3_dgrad_bn: bad geometry");
-  TORCH_CHECK(dy.numel() == N * H * W * Cr, "conv3x3_dgrad_bn: dy has ", dy.numel(), " elements");
-  TORCH_CHECK(w.numel() == Cr * 9 * Co, "conv3x3_dgrad_bn: w has ", w.numel(), " elements");
-  TORCH_CHECK(xb.numel() == N * H * W * Co, "conv3x3_dgrad_bn: xb has ", xb.numel(), " elements");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(dy.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(xb.data_ptr()) % 16 == 0,
-              "conv3x3_dgrad_bn: 16-byte aligned inputs");
-  TORCH_CHECK(dy.device() == w.device() && dy.device() == xb.device(), "conv3x3_dgrad_bn: one device");
-  check_dev(ss, "ss", at::kFloat);
-  TORCH_CHECK(ss.device() == dy.device() && ss.is_contiguous() && ss.dim() == 2 && ss.size(0) == 4 &&
-                  ss.size(1) == Co,
-              "conv3x3_dgrad_bn: ss must be [4, Co] fp32");
-  TORCH_CHECK(conv3x3_dgrad_bn_ok(N, H, W, Cr, Co),
+  const rla::Conv3x3Geom g = rla::conv3x3_geom(N, H, W, Cr, Co);
+  TORCH_CHECK(rla::conv3x3_bwd_ok(g),
               "conv3x3_dgrad_bn: unsupported shape (Cr % 16, Co % 64, Co <= 512, halo tile size)");
+  const uint16_t* dyp = bf16_operand(dy, "conv3x3_dgrad_bn: dy", N * H * W * Cr, dy);
+  const uint16_t* wp = bf16_operand(w, "conv3x3_dgrad_bn: w", Cr * 9 * Co, dy);
+  const uint16_t* xbp = bf16_operand(xb, "conv3x3_dgrad_bn: xb", N * H * W * Co, dy);
+  const float* ssp = stats4(ss, Co, dy, "conv3x3_dgrad_bn: ss");
+  TORCH_CHECK(ssp, "conv3x3_dgrad_bn: ss must be a [4, Co] fp32 tensor");
   const at::hip::HIPGuardMasqueradingAsCUDA guard(dy.device());
-  const rla::Conv3x3Geom g = conv3x3_dgrad_geom(N, H, W, Cr, Co);
   Tensor d = at::empty({N, H, W, Co}, dy.options());
   Tensor part = at::empty({g.wpb, 2, Co}, dy.options().dtype(at::kFloat));
-  TORCH_CHECK(rla::launch_conv3x3(reinterpret_cast<const uint16_t*>(dy.data_ptr()),
-                                  reinterpret_cast<const uint16_t*>(w.data_ptr()),
-                                  reinterpret_cast<uint16_t*>(d.data_ptr()), g, true, cur_stream(dy),
-                                  part.data_ptr<float>(), ss.data_ptr<float>(), nullptr,
-                                  reinterpret_cast<const uint16_t*>(xb.data_ptr())),
+  TORCH_CHECK(rla::launch_conv3x3(dyp, wp, reinterpret_cast<uint16_t*>(d.data_ptr()), g, true, cur_stream(dy),
+                                  part.data_ptr<float>(), ssp, nullptr, xbp),
               "conv3x3_dgrad_bn: launch refused");
   return {d, part};
+}
+
+// Read-only plan queries (tests): what the launches above run for a shape, under the
+// current plan CU count (set_plan_cus) and the RLA_CONV3X3_TM / RLA_CONV3X3_GENERIC switches:
+// (tm, wpb, vrows, pieces_per_thread, nx, fixed)
+std::vector<int64_t> conv3x3_plan_of(const rla::Conv3x3Geom& g, bool pre) {
+  const rla::Conv3x3Instance ins = rla::conv3x3_instance(g, pre);
+  return {g.tm, g.wpb, g.vrows, rla::conv3x3_pieces_per_thread(g), ins.nx, ins.fixed ? 1 : 0};
+}
+
+// the arguments are the conv3x3 / conv3x3_stats binding's own (flip: Cin = dy's channels)
+std::vector<int64_t> conv3x3_plan(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout, bool flip, bool stats,
+                                  bool pre) {
+  const rla::Conv3x3Geom g = rla::conv3x3_geom(N, H, W, Cin, Cout);
+  TORCH_CHECK(rla::conv3x3_ok(g), "conv3x3_plan: unsupported shape");
+  TORCH_CHECK(!(flip && stats) && (!pre || stats), "conv3x3_plan: statistics are a forward epilogue, pre needs them");
+  TORCH_CHECK(!pre || rla::conv3x3_pre_ok(g), "conv3x3_plan: pre needs Cin <= 512");
+  return conv3x3_plan_of(g, pre);
+}
+
+// a conv3x3_dgrad_bn launch: the plain input gradient's instance choice
+std::vector<int64_t> conv3x3_dgrad_bn_plan(int64_t N, int64_t H, int64_t W, int64_t Cr, int64_t Co) {
+  const rla::Conv3x3Geom g = rla::conv3x3_geom(N, H, W, Cr, Co);
+  TORCH_CHECK(rla::conv3x3_bwd_ok(g), "conv3x3_dgrad_bn_plan: unsupported shape");
+  return conv3x3_plan_of(g, false);
 }
 
 // 3x3 / stride 2 / pad 1 NHWC bf16 convolution forward (csrc/conv3x3s2.hip): x [N, H, W, Cin]
 // and w [Cout, 3, 3, Cin] as contiguous memory; returns y as contiguous [N, OH, OW, Cout].
 // stats: also the next BatchNorm's partial sums of bf16(y) -> {y, part [rows, 2, Cout]}
-rla::Conv3x3S2Geom conv3x3s2_full_geom(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout) {
-  rla::Conv3x3S2Geom g = rla::conv3x3s2_geom((int)N, (int)H, (int)W, (int)Cin, (int)Cout);
-  // vrows walks every tile of the partition and is a function of (N, H, W, wpb) alone (a
-  // pinned plan CU count changes wpb, hence the key): the last few answers are kept, a
-  // model has a handful of such layers
-  struct Slot {
-    int64_t n, h, w;
-    int wpb, vrows;
-  };
-  static Slot slots[16];
-  static int used = 0, next = 0;
-  static std::mutex mu;
-  std::lock_guard<std::mutex> lk(mu);
-  for (int i = 0; i < used; ++i)
-    if (slots[i].n == N && slots[i].h == H && slots[i].w == W && slots[i].wpb == g.wpb) {
-      g.vrows = slots[i].vrows;
-      return g;
-    }
-  g.vrows = rla::conv3x3s2_vrows(g);
-  slots[next] = Slot{N, H, W, g.wpb, g.vrows};
-  next = (next + 1) % 16;
-  if (used < 16) ++used;
-  return g;
-}
-
-// the arguments a geometry can be built from (int ranges; Cout % 64 before conv3x3_wpb divides by Cout / 64)
-bool conv3x3s2_args_ok(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout) {
-  return N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cout % 64 == 0 && Cin < (int64_t(1) << 30) &&
-         Cout < (int64_t(1) << 30) && N * (H + 2) * (W + 2) < (int64_t(1) << 30);
-}
-
-bool conv3x3s2_supported(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout) {
-  return conv3x3s2_args_ok(N, H, W, Cin, Cout) && rla::conv3x3s2_ok(conv3x3s2_full_geom(N, H, W, Cin, Cout));
-}
-
 std::vector<Tensor> conv3x3s2_impl(Tensor x, Tensor w, int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout,
                                    bool stats) {
-  TORCH_CHECK(x.is_cuda() && w.is_cuda(), "conv3x3s2: GPU tensors");
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16, "conv3x3s2: bf16 inputs");
-  TORCH_CHECK(x.is_contiguous() && w.is_contiguous(), "conv3x3s2: contiguous NHWC / [Cout,3,3,Cin] memory");
-  TORCH_CHECK(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv3x3s2: bad geometry");
-  TORCH_CHECK(x.numel() == N * H * W * Cin, "conv3x3s2: x has ", x.numel(), " elements");
-  TORCH_CHECK(w.numel() == Cout * 9 * Cin, "conv3x3s2: w has ", w.numel(), " elements");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
-              "conv3x3s2: 16-byte aligned inputs");
-  TORCH_CHECK(conv3x3s2_args_ok(N, H, W, Cin, Cout), "conv3x3s2: unsupported shape (Cout % 64, size)");
-  const at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
-  const rla::Conv3x3S2Geom g = conv3x3s2_full_geom(N, H, W, Cin, Cout);  // once per launch
+  const rla::Conv3x3S2Geom g = rla::conv3x3s2_geom(N, H, W, Cin, Cout);
   TORCH_CHECK(rla::conv3x3s2_ok(g), "conv3x3s2: unsupported shape (Cin % 16, Cout % 64, halo tile size)");
+  const uint16_t* xp = bf16_operand(x, "conv3x3s2: x", N * H * W * Cin, x);
+  const uint16_t* wp = bf16_operand(w, "conv3x3s2: w", Cout * 9 * Cin, x);
+  const at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   Tensor y = at::empty({N, g.OH, g.OW, Cout}, x.options());
   Tensor part;
   if (stats) part = at::empty({g.wpb, 2, Cout}, x.options().dtype(at::kFloat));
-  TORCH_CHECK(rla::launch_conv3x3s2(reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                                    reinterpret_cast<const uint16_t*>(w.data_ptr()),
-                                    reinterpret_cast<uint16_t*>(y.data_ptr()), g, cur_stream(x),
+  TORCH_CHECK(rla::launch_conv3x3s2(xp, wp, reinterpret_cast<uint16_t*>(y.data_ptr()), g, cur_stream(x),
                                     stats ? part.data_ptr<float>() : nullptr),
               "conv3x3s2: launch refused");
   if (stats) return {y, part};
@@ -1001,6 +907,10 @@ std::vector<Tensor> conv3x3s2_stats(Tensor x, Tensor w, int64_t N, int64_t H, in
   return conv3x3s2_impl(x, w, N, H, W, Cin, Cout, true);
 }
 
+bool conv3x3s2_supported(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout) {
+  return rla::conv3x3s2_ok(rla::conv3x3s2_geom(N, H, W, Cin, Cout));
+}
+
 // Read-only plan query (tests): what a conv3x3s2 / conv3x3s2_stats launch would run under the
 // current plan CU count.  Workgroup j of an output-channel block owns output pixels
 // [M j / wpb, M (j + 1) / wpb) of M = N OH OW, in tiles of tm from its start, and writes part row j.
@@ -1008,31 +918,27 @@ std::vector<Tensor> conv3x3s2_stats(Tensor x, Tensor w, int64_t N, int64_t H, in
 // takes its shape at run time, and stats changes the epilogue only
 std::vector<int64_t> conv3x3s2_plan(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout, bool stats) {
   (void)stats;
-  TORCH_CHECK(conv3x3s2_args_ok(N, H, W, Cin, Cout), "conv3x3s2_plan: unsupported shape");
-  const rla::Conv3x3S2Geom g = conv3x3s2_full_geom(N, H, W, Cin, Cout);
+  const rla::Conv3x3S2Geom g = rla::conv3x3s2_geom(N, H, W, Cin, Cout);
   TORCH_CHECK(rla::conv3x3s2_ok(g), "conv3x3s2_plan: unsupported shape");
   return {rla::conv3x3s2_tm(), g.wpb, g.vrows, rla::conv3x3s2_pieces_per_thread(g), rla::conv3x3s2_nx(), 0,
           g.OH, g.OW};
 }
 
 // ResNet stem forward: x [N, H, W, 3] NHWC bf16, w [64, 7, 7, 3] bf16 -> {y [N, OH, OW, 64]} or, with
-// stats, {y, part [rows, 2, 64]} (the next BatchNorm's partial sums of bf16(y))
+// stats, {y, part [rows, 2, 64]} (the next BatchNorm's partial sums of bf16(y)).  The kernels read x
+// as 32-bit words and w element by element (an arena's bf16 shadow is 8-byte aligned): 4-byte alignment
 std::vector<Tensor> stem_fwd(Tensor x, Tensor w, bool stats) {
-  TORCH_CHECK(x.is_cuda() && w.is_cuda(), "stem: GPU tensors");
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16, "stem: bf16 inputs");
-  TORCH_CHECK(x.dim() == 4 && x.size(3) == 3 && x.is_contiguous(), "stem: x must be contiguous [N, H, W, 3]");
-  TORCH_CHECK(w.numel() == 64 * 147 && w.is_contiguous(), "stem: w must be contiguous [64, 7, 7, 3]");
-  const rla::StemGeom g{(int)x.size(0), (int)x.size(1), (int)x.size(2), (int)((x.size(1) - 1) / 2 + 1),
-                        (int)((x.size(2) - 1) / 2 + 1)};
+  TORCH_CHECK(x.dim() == 4 && x.size(3) == 3, "stem: x must be contiguous [N, H, W, 3]");
+  const rla::StemGeom g = rla::stem_geom(x.size(0), x.size(1), x.size(2));
   TORCH_CHECK(rla::stem_ok(g), "stem: unsupported shape (W even, W <= 256)");
+  const uint16_t* xp = bf16_operand(x, "stem: x", x.numel(), x, 4);
+  const uint16_t* wp = bf16_operand(w, "stem: w [64, 7, 7, 3]", 64 * 147, x, 4);
   const at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   Tensor y = at::empty({g.N, g.OH, g.OW, 64}, x.options());
   Tensor part;
   if (stats) part = at::empty({rla::stem_grid(g), 2, 64}, x.options().dtype(at::kFloat));
-  TORCH_CHECK(rla::launch_stem_fwd(reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                                   reinterpret_cast<const uint16_t*>(w.data_ptr()),
-                                   reinterpret_cast<uint16_t*>(y.data_ptr()), stats ? part.data_ptr<float>() : nullptr,
-                                   g, cur_stream(x)),
+  TORCH_CHECK(rla::launch_stem_fwd(xp, wp, reinterpret_cast<uint16_t*>(y.data_ptr()),
+                                   stats ? part.data_ptr<float>() : nullptr, g, cur_stream(x)),
               "stem: launch refused");
   if (stats) return {y, part};
   return {y};
@@ -1040,62 +946,27 @@ std::vector<Tensor> stem_fwd(Tensor x, Tensor w, bool stats) {
 
 // ResNet stem weight gradient: x [N, H, W, 3], dy [N, OH, OW, 64] (NHWC bf16) -> fp32 [64, 7, 7, 3]
 Tensor stem_wgrad(Tensor x, Tensor dy) {
-  TORCH_CHECK(x.is_cuda() && dy.is_cuda(), "stem_wgrad: GPU tensors");
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && dy.scalar_type() == at::kBFloat16, "stem_wgrad: bf16 inputs");
-  TORCH_CHECK(x.dim() == 4 && x.size(3) == 3 && x.is_contiguous(), "stem_wgrad: x must be contiguous [N, H, W, 3]");
-  const rla::StemGeom g{(int)x.size(0), (int)x.size(1), (int)x.size(2), (int)((x.size(1) - 1) / 2 + 1),
-                        (int)((x.size(2) - 1) / 2 + 1)};
+  TORCH_CHECK(x.dim() == 4 && x.size(3) == 3, "stem_wgrad: x must be contiguous [N, H, W, 3]");
+  const rla::StemGeom g = rla::stem_geom(x.size(0), x.size(1), x.size(2));
   TORCH_CHECK(rla::stem_ok(g), "stem_wgrad: unsupported shape");
-  TORCH_CHECK(dy.dim() == 4 && dy.size(0) == g.N && dy.size(1) == g.OH && dy.size(2) == g.OW && dy.size(3) == 64 &&
-                  dy.is_contiguous(),
+  TORCH_CHECK(dy.dim() == 4 && dy.size(0) == g.N && dy.size(1) == g.OH && dy.size(2) == g.OW && dy.size(3) == 64,
               "stem_wgrad: dy must be contiguous [N, OH, OW, 64]");
+  const uint16_t* xp = bf16_operand(x, "stem_wgrad: x", x.numel(), x, 4);
+  const uint16_t* dyp = bf16_operand(dy, "stem_wgrad: dy", dy.numel(), x);
   const at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   Tensor part = at::empty({rla::stem_grid(g), 64, 224}, x.options().dtype(at::kFloat));
   Tensor dw = at::empty({64, 7, 7, 3}, x.options().dtype(at::kFloat));
-  TORCH_CHECK(rla::launch_stem_wgrad(reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                                     reinterpret_cast<const uint16_t*>(dy.data_ptr()), part.data_ptr<float>(),
-                                     dw.data_ptr<float>(), g, cur_stream(x)),
+  TORCH_CHECK(rla::launch_stem_wgrad(xp, dyp, part.data_ptr<float>(), dw.data_ptr<float>(), g, cur_stream(x)),
               "stem_wgrad: launch refused");
   return dw;
 }
 
-bool stem_supported(int64_t N, int64_t H, int64_t W) {
-  const rla::StemGeom g{(int)N, (int)H, (int)W, (int)((H - 1) / 2 + 1), (int)((W - 1) / 2 + 1)};
-  return rla::stem_ok(g);
-}
+bool stem_supported(int64_t N, int64_t H, int64_t W) { return rla::stem_ok(rla::stem_geom(N, H, W)); }
 
-bool conv3x3_supported(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout) {
-  if (N <= 0 || H <= 0 || W <= 0 || Cout <= 0 || N * (H + 2) * (W + 2) >= (int64_t(1) << 30)) return false;
-  rla::Conv3x3Geom g{(int)N, (int)H, (int)W, (int)Cin, (int)Cout, 0,
-                     rla::conv3x3_pick_tm((int)N, (int)H, (int)W, (int)Cout),
-                     rla::conv3x3_wpb((int)N, (int)H, (int)W, (int)Cout)};
-  g.vrows = rla::conv3x3_vrows(g);
-  return rla::conv3x3_ok(g);
-}
-
-// Read-only plan queries (tests): what the launches above would run for a shape, under the
-// current plan CU count (set_plan_cus) and the RLA_CONV3X3_TM / RLA_CONV3X3_GENERIC switches.
-// The arguments are the conv3x3 / conv3x3_stats binding's own (flip: Cin = dy's channels);
-// returns (tm, wpb, vrows, pieces_per_thread, nx, fixed)
-std::vector<int64_t> conv3x3_plan(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout, bool flip, bool stats,
-                                  bool pre) {
-  TORCH_CHECK(conv3x3_supported(N, H, W, Cin, Cout), "conv3x3_plan: unsupported shape");
-  TORCH_CHECK(!(flip && stats) && (!pre || stats), "conv3x3_plan: statistics are a forward epilogue, pre needs them");
-  rla::Conv3x3Geom g{(int)N, (int)H, (int)W, (int)Cin, (int)Cout, 0,
-                     rla::conv3x3_pick_tm((int)N, (int)H, (int)W, (int)Cout),
-                     rla::conv3x3_wpb((int)N, (int)H, (int)W, (int)Cout)};
-  g.vrows = rla::conv3x3_vrows(g);
-  TORCH_CHECK(!pre || rla::conv3x3_pre_ok(g), "conv3x3_plan: pre needs Cin <= 512");
-  const rla::Conv3x3Instance ins = rla::conv3x3_instance(g, pre);
-  return {g.tm, g.wpb, g.vrows, rla::conv3x3_pieces_per_thread(g), ins.nx, ins.fixed ? 1 : 0};
-}
-
-// conv3x3_plan's tuple for a conv3x3_dgrad_bn launch (the plain input gradient's instance choice)
-std::vector<int64_t> conv3x3_dgrad_bn_plan(int64_t N, int64_t H, int64_t W, int64_t Cr, int64_t Co) {
-  TORCH_CHECK(conv3x3_dgrad_bn_ok(N, H, W, Cr, Co), "conv3x3_dgrad_bn_plan: unsupported shape");
-  const rla::Conv3x3Geom g = conv3x3_dgrad_geom(N, H, W, Cr, Co);
-  const rla::Conv3x3Instance ins = rla::conv3x3_instance(g, false);
-  return {g.tm, g.wpb, g.vrows, rla::conv3x3_pieces_per_thread(g), ins.nx, ins.fixed ? 1 : 0};
+int64_t stem_grid(int64_t N, int64_t H, int64_t W) {
+  const rla::StemGeom g = rla::stem_geom(N, H, W);
+  TORCH_CHECK(rla::stem_ok(g), "stem_grid: unsupported shape");
+  return rla::stem_grid(g);
 }
 
 // (tnw, gy, gx, tiles_per_blk, variant) of conv1x1_stats (bwd: of conv1x1_bn_bwd); variant 0 / 1:
@@ -1105,12 +976,6 @@ std::vector<int64_t> conv1x1_plan(int64_t M, int64_t K, int64_t N, bool bwd) {
               "conv1x1_plan: unsupported shape");
   const rla::Conv1x1Plan p = rla::conv1x1_stats_plan(M, (int)N, bwd);
   return {p.tnw, p.gy, p.gx, p.tiles_per_blk, rla::conv1x1_variant((int)K, p)};
-}
-
-int64_t stem_grid(int64_t N, int64_t H, int64_t W) {
-  const rla::StemGeom g{(int)N, (int)H, (int)W, (int)((H - 1) / 2 + 1), (int)((W - 1) / 2 + 1)};
-  TORCH_CHECK(rla::stem_ok(g), "stem_grid: unsupported shape");
-  return rla::stem_grid(g);
 }
 
 Tensor dp_pack_roundtrip(Tensor x, int64_t tag) {

@@ -39,7 +39,10 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <array>
 #include <atomic>
+#include <map>
+#include <mutex>
 
 #include "common.h"
 #include "kernels.h"
@@ -634,6 +637,30 @@ int conv3x3_pick_tm(int N, int H, int W, int Cout) {
   const int64_t M = (int64_t)N * H * W;
   const int64_t per = M / conv3x3_wpb(N, H, W, Cout);
   return per >= 768 ? 512 : 256;
+}
+
+bool conv3x3_args_ok(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout) {
+  const int64_t lim = int64_t(1) << 30;  // each factor first: the products below cannot overflow
+  return N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && N < lim && H < lim && W < lim && Cin < lim &&
+         Cout < lim && Cout % kTN == 0 && N * (H + 2) < lim && N * (H + 2) * (W + 2) < lim;
+}
+
+int conv3x3_cached_vrows(int stride, int N, int H, int W, int tm, int wpb, const std::function<int()>& walk) {
+  static std::mutex mu;
+  static std::map<std::array<int, 6>, int> cache;
+  const std::array<int, 6> key{stride, N, H, W, tm, wpb};
+  std::lock_guard<std::mutex> lk(mu);
+  auto it = cache.find(key);
+  if (it == cache.end()) it = cache.emplace(key, walk()).first;
+  return it->second;
+}
+
+Conv3x3Geom conv3x3_geom(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout) {
+  if (!conv3x3_args_ok(N, H, W, Cin, Cout)) return Conv3x3Geom{};
+  Conv3x3Geom g{(int)N, (int)H, (int)W, (int)Cin, (int)Cout, 0, conv3x3_pick_tm((int)N, (int)H, (int)W, (int)Cout),
+                conv3x3_wpb((int)N, (int)H, (int)W, (int)Cout)};
+  g.vrows = conv3x3_cached_vrows(1, g.N, g.H, g.W, g.tm, g.wpb, [&g] { return conv3x3_vrows(g); });
+  return g;
 }
 
 bool conv3x3_ok(const Conv3x3Geom& g) {

@@ -368,9 +368,11 @@ __global__ __launch_bounds__(kS2Threads) void conv3x3s2_kernel(const uint16_t* _
 
 }  // namespace
 
-Conv3x3S2Geom conv3x3s2_geom(int N, int H, int W, int Cin, int Cout) {
-  Conv3x3S2Geom g{N, H, W, Cin, Cout, (H - 1) / 2 + 1, (W - 1) / 2 + 1, 0, 0};
-  g.wpb = conv3x3_wpb(N, g.OH, g.OW, Cout);
+Conv3x3S2Geom conv3x3s2_geom(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout) {
+  if (!conv3x3_args_ok(N, H, W, Cin, Cout)) return Conv3x3S2Geom{};
+  Conv3x3S2Geom g{(int)N, (int)H, (int)W, (int)Cin, (int)Cout, (int)((H - 1) / 2 + 1), (int)((W - 1) / 2 + 1), 0, 0};
+  g.wpb = conv3x3_wpb(g.N, g.OH, g.OW, g.Cout);
+  g.vrows = conv3x3_cached_vrows(2, g.N, g.H, g.W, kS2TM, g.wpb, [&g] { return conv3x3s2_vrows(g); });
   return g;
 }
 

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <functional>
+
 namespace rla {
 
 struct AdamArgs {
@@ -346,6 +348,19 @@ void set_plan_cus(int n);
 int conv3x3_wpb(int N, int H, int W, int Cout);
 int conv3x3_pick_tm(int N, int H, int W, int Cout);
 int conv3x3_vrows(const Conv3x3Geom& g);
+// The arguments a 3x3 geometry of either stride can be built from: all positive, the pixel
+// and channel counts in int range (N (H + 2) (W + 2), Cin, Cout < 2^30) and Cout % 64 == 0,
+// which conv3x3_wpb divides by.
+bool conv3x3_args_ok(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout);
+// The one cache of the partition walks (conv3x3_vrows, conv3x3s2_vrows), keyed on all a
+// walk's answer is a function of; a pinned plan CU count or RLA_CONV3X3_TM changes tm / wpb,
+// hence the key.  walk() runs on a key's first use.
+int conv3x3_cached_vrows(int stride, int N, int H, int W, int tm, int wpb, const std::function<int()>& walk);
+// The geometry of every stride-1 launch, predicate and plan query, under the current
+// plan_cus() and RLA_CONV3X3_TM.  Guards conv3x3_args_ok (what makes the int casts and the
+// planning arithmetic safe): arguments that fail it give the all-zero geometry, which
+// conv3x3_ok refuses.  Cin % 16, the halo limit and the 32-bit offset limits are conv3x3_ok's.
+Conv3x3Geom conv3x3_geom(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout);
 int conv3x3_pieces_per_thread(const Conv3x3Geom& g);  // 16-byte halo pieces per thread and chunk
 bool conv3x3_ok(const Conv3x3Geom& g);
 // the template instance launch_conv3x3 runs for g (pre: with pre_ss; with bwd_x: that of pre = false)
@@ -377,8 +392,9 @@ struct Conv3x3S2Geom {
   int vrows;  // halo rows of the largest pixel tile (conv3x3s2_vrows)
   int wpb;    // workgroups per 64-channel output block = contiguous output-pixel ranges
 };
-// (N .. OW, wpb = conv3x3_wpb over the OUTPUT pixels under the current plan_cus(); vrows left 0)
-Conv3x3S2Geom conv3x3s2_geom(int N, int H, int W, int Cin, int Cout);
+// conv3x3_geom's stride-2 counterpart, with the same guard and the same all-zero answer
+// (wpb = conv3x3_wpb over the OUTPUT pixels); Cin % 16 and the halo limit are conv3x3s2_ok's
+Conv3x3S2Geom conv3x3s2_geom(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout);
 int conv3x3s2_vrows(const Conv3x3S2Geom& g);
 int conv3x3s2_pieces_per_thread(const Conv3x3S2Geom& g);  // 16-byte halo pieces per thread and chunk
 int conv3x3s2_tm();  // output pixels per workgroup tile
@@ -393,6 +409,9 @@ bool launch_conv3x3s2(const uint16_t* x, const uint16_t* w, uint16_t* y, const C
 struct StemGeom {
   int N, H, W, OH, OW;
 };
+// guards the int casts only (out-of-range sizes give the all-zero geometry); the shapes the
+// kernels cover are stem_ok's
+StemGeom stem_geom(int64_t N, int64_t H, int64_t W);
 bool stem_ok(const StemGeom& g);
 int stem_grid(const StemGeom& g);
 bool launch_stem_fwd(const uint16_t* x, const uint16_t* w, uint16_t* y, float* part, const StemGeom& g,

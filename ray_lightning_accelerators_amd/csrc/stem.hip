@@ -447,6 +447,12 @@ __global__ __launch_bounds__(256) void stem_wgrad_reduce_kernel(const float* __r
 
 }  // namespace
 
+StemGeom stem_geom(int64_t N, int64_t H, int64_t W) {
+  const int64_t lim = int64_t(1) << 31;
+  if (N <= 0 || H <= 0 || W <= 0 || N >= lim || H >= lim || W >= lim) return StemGeom{};
+  return StemGeom{(int)N, (int)H, (int)W, (int)((H - 1) / 2 + 1), (int)((W - 1) / 2 + 1)};
+}
+
 bool stem_ok(const StemGeom& g) {
   return g.N > 0 && g.H > 0 && g.W > 0 && g.W % 2 == 0 && g.W <= kMaxW && g.OH == (g.H - 1) / 2 + 1 &&
          g.OW == (g.W - 1) / 2 + 1 && g.OW <= 128 && (g.W >> 1) * kRowsIn <= kNP * kStThreads &&

@@ -203,8 +203,8 @@ def _bn_bwd_shape_ok(m: int, k: int, n: int) -> bool:
     return bool(require().conv1x1_bn_bwd_ok(m, k, n))
 
 
-@functools.lru_cache(maxsize=256)
 def _conv3x3_shape_ok(n: int, h: int, w: int, cin: int, cout: int) -> bool:
+    # not cached here, see _conv3x3s2_shape_ok
     from . import require
 
     return bool(require().conv3x3_supported(n, h, w, cin, cout))
@@ -302,8 +302,8 @@ def fuse_bn_dgrad_3x3_mode() -> str:
     return m if m in ("0", "1") else "auto"
 
 
-@functools.lru_cache(maxsize=256)
 def _dgrad_bn_shape_ok(n: int, h: int, w: int, cr: int, co: int) -> bool:
+    # not cached here, see _conv3x3s2_shape_ok
     from . import require
 
     return bool(require().conv3x3_dgrad_bn_ok(n, h, w, cr, co))
@@ -361,8 +361,10 @@ def conv3x3s2_ok(x: torch.Tensor, wb: torch.Tensor, stride, padding) -> bool:
 
 
 def _conv3x3s2_shape_ok(n: int, h: int, w: int, cin: int, cout: int) -> bool:
-    # not cached here: the answer follows the work split, hence the planning CU count
-    # (set_plan_cus); the binding keeps the partition walk of the last shapes itself
+    # The three 3x3 predicates (this one, _conv3x3_shape_ok, _dgrad_bn_shape_ok) are not
+    # cached here: the answer follows the work split, hence the planning CU count
+    # (set_plan_cus) and RLA_CONV3X3_TM, and must be the one the launch will give.  The
+    # binding builds the launch's own geometry and keeps every partition walk it has made.
     from . import require
 
     return bool(require().conv3x3s2_supported(n, h, w, cin, cout))
@@ -456,7 +458,14 @@ class BNStats:
 
 def conv1x1_stats_ok(m: int, cin: int, cout: int) -> bool:
     """Shapes of the 1x1 MFMA forward with BatchNorm statistics (csrc/conv1x1.hip)."""
-    return cin % 32 == 0 and cout % 64 == 0 and cout <= 4096 and os.environ.get("RLA_CONV1X1_STATS", "auto") != "off"
+    return os.environ.get("RLA_CONV1X1_STATS", "auto") != "off" and _conv1x1_stats_shape_ok(m, cin, cout)
+
+
+@functools.lru_cache(maxsize=256)
+def _conv1x1_stats_shape_ok(m: int, k: int, n: int) -> bool:
+    from . import require
+
+    return bool(require().conv1x1_stats_ok(m, k, n))
 
 
 def conv1x1_stats_hip(x: torch.Tensor, wb: torch.Tensor, pre=None):

@@ -4,7 +4,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import test_conv_partition as P
+
 gpu = pytest.mark.gpu
+plan_cus = P.plan_cus  # the fixture that pins the planning CU count, shared with that file
 
 # (N, H, W, Cin, Cout): ResNet-50's stride-1 conv2 shapes at small batch, plus tiles
 # that cross image boundaries (H*W not a multiple of 256, tiny images) and a tail
@@ -388,3 +391,38 @@ def test_resnet_block_bn1_deferred_into_conv2(monkeypatch):
     for nm, a, b in zip([n for n, _ in blk.named_parameters()], p0, p1):
         assert torch.equal(a, b), nm
     assert torch.equal(m0, m1) and torch.equal(v0, v1) and n0 == n1 == 1
+
+
+@gpu
+def test_predicates_answer_for_the_plan_in_force(plan_cus, monkeypatch):
+    """The stride-1 twin of test_conv3x3s2.py's test_resnet_shapes_supported_at_every_batch:
+    ``conv3x3_ok`` and ``_dgrad_bn_shape_ok`` follow a re-pinned planning CU count, as the
+    bindings they ask do.  x [1, 64, 8, 200], Cout 64: at 8 plan CUs 8 ranges of 200 pixels,
+    256-pixel tiles, 3 halo rows of 202 entries = 5 pieces per thread (taken, and the output
+    within test_conv_partition.py's fp64 bound); at 1 CU one range of 1600 pixels,
+    512-pixel tiles, 6 halo rows = 10 pieces against the kernel's 7 (refused)."""
+    from ray_lightning_accelerators_amd import ops
+    from ray_lightning_accelerators_amd.ops import conv as C
+
+    monkeypatch.delenv("RLA_CONV3X3_TM", raising=False)
+    monkeypatch.delenv("RLA_CONV3X3", raising=False)
+    m = ops.require()
+    n, h, w, cin, cout = 1, 8, 200, 64, 64
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device="cpu").manual_seed(14)
+    x = torch.randn(n, cin, h, w, generator=g).to(dev).to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+    wb = (torch.randn(cout, cin, 3, 3, generator=g) / (3 * cin ** 0.5)).to(dev).to(torch.bfloat16)
+    wb = wb.contiguous(memory_format=torch.channels_last)
+    for cus, taken in ((8, True), (1, False), (8, True)):
+        plan_cus(cus)
+        assert C.conv3x3_ok(x, wb, (1, 1), (1, 1)) == taken, cus
+        assert m.conv3x3_supported(n, h, w, cin, cout) == taken, cus
+        assert C._dgrad_bn_shape_ok(n, h, w, cout, cin) == taken, cus
+        assert m.conv3x3_dgrad_bn_ok(n, h, w, cout, cin) == taken, cus
+    assert tuple(m.conv3x3_plan(n, h, w, cin, cout)[:4]) == (256, 8, 3, 5)
+    assert tuple(m.conv3x3_dgrad_bn_plan(n, h, w, cout, cin)[:4]) == (256, 8, 3, 5)
+    y = C.conv3x3_hip(x, wb)
+    xn, wn = x.permute(0, 2, 3, 1), wb.permute(0, 2, 3, 1)
+    ref, amp = P.conv3x3_ref(xn, wn), P.conv3x3_ref(xn.abs(), wn.abs())
+    P._check_elementwise("conv3x3 1x8x200x64x64-cu8", y.permute(0, 2, 3, 1).reshape(-1, cout), ref.reshape(-1, cout),
+                         amp.reshape(-1, cout), 9 * cin)
