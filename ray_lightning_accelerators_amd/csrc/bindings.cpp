@@ -738,7 +738,7 @@ void bn_bwd_apply(Tensor x, optional<Tensor> y, Tensor dy, Tensor coef, bool rel
 // ---- NHWC bf16 convolutions -----------------------------------------------------------
 // Every Python-visible function of a kernel family -- launch, *_supported / *_ok and
 // *_plan -- builds its geometry with the family's one builder (rla::conv3x3_geom,
-// rla::conv3x3s2_geom, rla::stem_geom, wgrad_geom below) and its operands with
+// rla::conv3x3s2_geom, rla::conv3x3s2_dgrad_geom, rla::stem_geom, wgrad_geom below) and its operands with
 // bf16_operand / stats4 / ptr_or_null, so the three cannot disagree.
 
 // conv_wgrad's geometry from the binding's arguments, range-checked before the int casts
@@ -924,6 +924,36 @@ std::vector<int64_t> conv3x3s2_plan(int64_t N, int64_t H, int64_t W, int64_t Cin
           g.OH, g.OW};
 }
 
+// Input gradient of the 3x3 / stride 2 / pad 1 convolution (csrc/conv3x3s2_dgrad.hip):
+// dy [N, OH, OW, Cr] and the forward weight w [Cr, 3, 3, Co] as contiguous memory; returns dx as
+// contiguous [N, H, W, Co], every element written by the kernel.
+Tensor conv3x3s2_dgrad(Tensor dy, Tensor w, int64_t N, int64_t H, int64_t W, int64_t Cr, int64_t Co) {
+  const rla::Conv3x3S2DgradGeom g = rla::conv3x3s2_dgrad_geom(N, H, W, Cr, Co);
+  TORCH_CHECK(rla::conv3x3s2_dgrad_ok(g), "conv3x3s2_dgrad: unsupported shape (Cr % 16, Co % 64, halo tile size)");
+  const uint16_t* dyp = bf16_operand(dy, "conv3x3s2_dgrad: dy", N * g.OH * g.OW * Cr, dy);
+  const uint16_t* wp = bf16_operand(w, "conv3x3s2_dgrad: w", Cr * 9 * Co, dy);
+  const at::hip::HIPGuardMasqueradingAsCUDA guard(dy.device());
+  Tensor dx = at::empty({N, H, W, Co}, dy.options());
+  TORCH_CHECK(rla::launch_conv3x3s2_dgrad(dyp, wp, reinterpret_cast<uint16_t*>(dx.data_ptr()), g, cur_stream(dy)),
+              "conv3x3s2_dgrad: launch refused");
+  return dx;
+}
+
+bool conv3x3s2_dgrad_supported(int64_t N, int64_t H, int64_t W, int64_t Cr, int64_t Co) {
+  return rla::conv3x3s2_dgrad_ok(rla::conv3x3s2_dgrad_geom(N, H, W, Cr, Co));
+}
+
+// Read-only plan query (tests): what a conv3x3s2_dgrad launch would run under the current plan
+// CU count.  Workgroup j of a dx-channel block owns quads [Q j / wpb, Q (j + 1) / wpb) of
+// Q = N OH OW, in tiles of tq from its start.  Returns (tq, wpb, vrows, pieces_per_thread, nx,
+// fixed, OH, OW); fixed is 0: the one instance takes its shape at run time
+std::vector<int64_t> conv3x3s2_dgrad_plan(int64_t N, int64_t H, int64_t W, int64_t Cr, int64_t Co) {
+  const rla::Conv3x3S2DgradGeom g = rla::conv3x3s2_dgrad_geom(N, H, W, Cr, Co);
+  TORCH_CHECK(rla::conv3x3s2_dgrad_ok(g), "conv3x3s2_dgrad_plan: unsupported shape");
+  return {rla::conv3x3s2_dgrad_tq(), g.wpb, g.vrows, rla::conv3x3s2_dgrad_pieces_per_thread(g),
+          rla::conv3x3s2_dgrad_nx(g), 0, g.OH, g.OW};
+}
+
 // ResNet stem forward: x [N, H, W, 3] NHWC bf16, w [64, 7, 7, 3] bf16 -> {y [N, OH, OW, 64]} or, with
 // stats, {y, part [rows, 2, 64]} (the next BatchNorm's partial sums of bf16(y)).  The kernels read x
 // as 32-bit words and w element by element (an arena's bf16 shadow is 8-byte aligned): 4-byte alignment
@@ -1103,6 +1133,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv3x3s2_plan", &conv3x3s2_plan,
         "the 3x3 stride-2 kernel's (tm, wpb, vrows, pieces_per_thread, nx, fixed, OH, OW)", py::arg("N"),
         py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"), py::arg("stats") = false);
+  m.def("conv3x3s2_dgrad", &conv3x3s2_dgrad,
+        "3x3 / stride 2 / pad 1 input gradient on MFMA: dy [N, OH, OW, Cr], forward weight [Cr, 3, 3, Co] "
+        "-> dx [N, H, W, Co]",
+        py::arg("dy"), py::arg("w"), py::arg("N"), py::arg("H"), py::arg("W"), py::arg("Cr"), py::arg("Co"));
+  m.def("conv3x3s2_dgrad_supported", &conv3x3s2_dgrad_supported, "shapes conv3x3s2_dgrad covers", py::arg("N"),
+        py::arg("H"), py::arg("W"), py::arg("Cr"), py::arg("Co"));
+  m.def("conv3x3s2_dgrad_plan", &conv3x3s2_dgrad_plan,
+        "conv3x3s2_dgrad's (tq, wpb, vrows, pieces_per_thread, nx, fixed, OH, OW)", py::arg("N"), py::arg("H"),
+        py::arg("W"), py::arg("Cr"), py::arg("Co"));
   m.def("stem_fwd", &stem_fwd, "ResNet stem 7x7/s2 conv (3 -> 64) on MFMA [+ BatchNorm partial sums]");
   m.def("stem_supported", &stem_supported, "input shapes the stem kernel covers");
   m.def("stem_wgrad", &stem_wgrad, "ResNet stem weight gradient on MFMA -> fp32 [64, 7, 7, 3] (channels_last order)");

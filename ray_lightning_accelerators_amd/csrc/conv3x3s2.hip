@@ -4,8 +4,9 @@
 //
 // with OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1.  ResNet-50's three downsample conv2
 // layers (layer2/3/4.0.conv2: 56/128, 28/256, 14/512 as input width / Cin), each the
-// same 29.6 GFLOP at batch 128 as a stride-1 conv2.  Forward only: the input gradient
-// of these layers stays on the library, the weight gradient is conv_wgrad.hip's.
+// same 29.6 GFLOP at batch 128 as a stride-1 conv2.  This file is the forward; the input
+// gradient of these layers is conv3x3s2_dgrad.hip's (tiled over quads of input pixels), the
+// weight gradient conv_wgrad.hip's.
 //
 // The structure is conv3x3.hip's (read that header first): implicit GEMM
 // D[co][m] = W[co][(tap, ci)] . X[(tap, ci)][m] over m = output pixel with

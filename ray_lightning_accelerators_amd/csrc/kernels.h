@@ -352,7 +352,8 @@ int conv3x3_vrows(const Conv3x3Geom& g);
 // and channel counts in int range (N (H + 2) (W + 2), Cin, Cout < 2^30) and Cout % 64 == 0,
 // which conv3x3_wpb divides by.
 bool conv3x3_args_ok(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout);
-// The one cache of the partition walks (conv3x3_vrows, conv3x3s2_vrows), keyed on all a
+// The one cache of the partition walks (conv3x3_vrows, conv3x3s2_vrows and, under stride key
+// 3, conv3x3s2_dgrad_vrows), keyed on all a
 // walk's answer is a function of; a pinned plan CU count or RLA_CONV3X3_TM changes tm / wpb,
 // hence the key.  walk() runs on a key's first use.
 int conv3x3_cached_vrows(int stride, int N, int H, int W, int tm, int wpb, const std::function<int()>& walk);
@@ -403,6 +404,27 @@ bool conv3x3s2_ok(const Conv3x3S2Geom& g);
 // part (or null): BatchNorm partial sums of bf16(y), [g.wpb][2][Cout] fp32
 bool launch_conv3x3s2(const uint16_t* x, const uint16_t* w, uint16_t* y, const Conv3x3S2Geom& g,
                       hipStream_t stream, float* part = nullptr);
+
+// Input gradient of the 3x3 / stride 2 / pad 1 convolution on MFMA (csrc/conv3x3s2_dgrad.hip):
+// dx [N, H, W, Co] from dy [N, OH, OW, Cr] and the FORWARD weight w [Cr][3][3][Co] (Cr the
+// layer's output channels, Co its input channels, as conv3x3_dgrad_bn names them).  The work
+// is tiled over quads (n, a, b), a < OH, b < OW: the input pixels (2 a + {0, 1}, 2 b + {0, 1}).
+// Cr % 16 == 0, Co % 64 == 0.
+struct Conv3x3S2DgradGeom {
+  int N, H, W, Cr, Co, OH, OW;
+  int vrows;  // dy halo rows of the largest quad tile (conv3x3s2_dgrad_vrows)
+  int wpb;    // workgroups per 64-channel dx block = contiguous quad ranges
+};
+// conv3x3s2_geom's counterpart, with the same guard and the same all-zero answer
+// (wpb = conv3x3_wpb over the quads); Cr % 16 and the halo limit are conv3x3s2_dgrad_ok's
+Conv3x3S2DgradGeom conv3x3s2_dgrad_geom(int64_t N, int64_t H, int64_t W, int64_t Cr, int64_t Co);
+int conv3x3s2_dgrad_vrows(const Conv3x3S2DgradGeom& g);
+int conv3x3s2_dgrad_pieces_per_thread(const Conv3x3S2DgradGeom& g);  // 16-byte halo pieces per thread and chunk
+int conv3x3s2_dgrad_tq();  // quads per workgroup tile
+int conv3x3s2_dgrad_nx(const Conv3x3S2DgradGeom& g);  // halo pieces per thread of the instance g runs (2, 3 or 4)
+bool conv3x3s2_dgrad_ok(const Conv3x3S2DgradGeom& g);
+bool launch_conv3x3s2_dgrad(const uint16_t* dy, const uint16_t* w, uint16_t* dx, const Conv3x3S2DgradGeom& g,
+                            hipStream_t stream);
 
 // ResNet stem: 7x7 / stride 2 / pad 3 convolution, 3 -> 64 channels, NHWC bf16 (csrc/stem.hip);
 // part (or null): BatchNorm partial sums of bf16(y), [stem_grid(g)][2][64] fp32

@@ -20,7 +20,8 @@ cast, profiles/r3_rn50/kernel_stats_rn50_steady.csv) and its forward of the
 So every (operation, shape) picks its backend once, timed on the device at first
 use (like cudnn.benchmark): each operation builds ONE table ``{name: callable}``,
 ``_pick`` names the winner and that table's callable runs.  ``RLA_CONV1X1`` and
-``RLA_CONV_WGRAD`` pin a backend by its name in the table (``miopen|gemm|hip|...``).
+``RLA_CONV_WGRAD`` pin a backend by its name in the table (``miopen|gemm|hip|...``),
+``RLA_CONV3X3S2_DGRAD`` that of the stride-2 3x3 input gradient (``_pick_dgrad_s2``).
 
 Around the convolutions themselves:
 
@@ -95,7 +96,11 @@ def _pick(op: str, key: Tuple[int, ...], cands) -> str:
         for name in _DETERMINISTIC_ORDER:
             if name in cands:
                 return name
-    k = (op,) + key
+    return _timed_pick((op,) + key, cands)
+
+
+def _timed_pick(k: Tuple, cands) -> str:
+    """The cached pick of ``k`` = (op, *key), timing ``cands`` on the device at first use."""
     c = _choice.get(k)
     if c is None and torch.cuda.is_current_stream_capturing():
         return "miopen"  # no timing inside a graph capture (it synchronises)
@@ -393,6 +398,65 @@ def conv3x3s2_stats_hip(x: torch.Tensor, wb: torch.Tensor):
     return y.permute(0, 3, 1, 2), part
 
 
+def conv3x3s2_dgrad_ok(dy: torch.Tensor, wb: torch.Tensor, h: int, w: int) -> bool:
+    """Input gradients of a 3x3 / stride 2 / pad 1 layer with an [h, w] input the MFMA kernel
+    covers (csrc/conv3x3s2_dgrad.hip): ``dy`` [N, Cout, OH, OW] and the forward weight ``wb``
+    [Cout, Cin, 3, 3], both bf16 channels_last on the GPU and 16-byte aligned, Cout % 16 == 0,
+    Cin % 64 == 0 and a tile halo that fits its LDS image.  ``RLA_CONV3X3=off`` turns this
+    kernel off too."""
+    if dy.dim() != 4 or wb.dim() != 4 or tuple(wb.shape[2:]) != (3, 3):
+        return False
+    if not dy.is_cuda or not wb.is_cuda or os.environ.get("RLA_CONV3X3", "auto") == "off":
+        return False
+    n, cout, oh, ow = dy.shape
+    cin = wb.size(1)
+    return (wb.size(0) == cout and (oh, ow) == ((h - 1) // 2 + 1, (w - 1) // 2 + 1)
+            and cout % 16 == 0 and cin % 64 == 0 and dy.dtype == torch.bfloat16 and wb.dtype == torch.bfloat16
+            and dy.is_contiguous(memory_format=torch.channels_last)
+            and wb.is_contiguous(memory_format=torch.channels_last)
+            and dy.data_ptr() % 16 == 0 and wb.data_ptr() % 16 == 0
+            and _conv3x3s2_dgrad_shape_ok(n, h, w, cout, cin))
+
+
+def _conv3x3s2_dgrad_shape_ok(n: int, h: int, w: int, cr: int, co: int) -> bool:
+    # not cached here, see _conv3x3s2_shape_ok
+    from . import require
+
+    return bool(require().conv3x3s2_dgrad_supported(n, h, w, cr, co))
+
+
+def conv3x3s2_dgrad_hip(dy: torch.Tensor, wb: torch.Tensor, h: int, w: int) -> torch.Tensor:
+    """Input gradient of ``conv2d(x, wb, stride=2, padding=1)`` for an [h, w] input on the MFMA
+    kernel: ``dy`` [N, Cout, OH, OW] channels_last bf16, ``wb`` the forward weight [Cout, Cin,
+    3, 3] channels_last bf16, read as it lies in memory; returns [N, Cin, h, w] channels_last,
+    every element written once (fixed order: bitwise reproducible)."""
+    from . import require
+
+    n, cout = dy.size(0), dy.size(1)
+    cin = wb.size(1)
+    dx = require().conv3x3s2_dgrad(dy.permute(0, 2, 3, 1), wb.permute(0, 2, 3, 1), n, h, w, cout, cin)
+    return dx.permute(0, 3, 1, 2)
+
+
+def _s2_dgrad_mode() -> str:
+    """``RLA_CONV3X3S2_DGRAD=auto|hip|miopen``: backend of the stride-2 3x3 input gradient
+    (auto: timed per shape; deterministic mode: the in-tree kernel)."""
+    m = os.environ.get("RLA_CONV3X3S2_DGRAD", "auto")
+    return m if m in ("hip", "miopen") else "auto"
+
+
+def _pick_dgrad_s2(key: Tuple[int, ...], cands) -> str:
+    """``hip`` or ``miopen`` for a 3x3 / stride-2 input gradient (``dgrad_s2`` in
+    :func:`choices`).  The in-tree kernel runs in a fixed order, so deterministic mode takes
+    it untimed; a graph capture with no cached pick takes ``miopen``."""
+    mode = _s2_dgrad_mode()
+    if mode in cands:
+        return mode
+    if torch.are_deterministic_algorithms_enabled():
+        return "hip"
+    return _timed_pick(("dgrad_s2",) + key, cands)
+
+
 def _nhwc2d(t: torch.Tensor) -> torch.Tensor:
     n, c, h, w = t.shape
     return t.permute(0, 2, 3, 1).reshape(n * h * w, c)
@@ -656,14 +720,16 @@ class Conv1x1NHWC(nn.Conv2d):
 class _ConvNHWCFn(torch.autograd.Function):
     """KxK (or strided) bf16 NHWC convolution: MIOpen or, for 3x3 / stride 1 / pad 1, the
     MFMA kernels for the forward and dgrad, for 3x3 / stride 2 / pad 1 the MFMA forward
-    (its dgrad is MIOpen's); the weight gradient from MIOpen or the MFMA
-    kernel (``wgrad_hip``); each picked per shape on device time.  The weight gradient
-    reaches the fp32 master weight in fp32."""
+    and the MFMA quad-tiled dgrad (``conv3x3s2_dgrad_hip``; ``dgrad_s2``, picked by
+    ``_pick_dgrad_s2``: the in-tree kernel untimed in deterministic mode); the weight
+    gradient from MIOpen or the MFMA kernel (``wgrad_hip``); each picked per shape on device
+    time.  The weight gradient reaches the fp32 master weight in fp32."""
 
     @staticmethod
     def forward(ctx, x, weight, wb, stride, padding, fork=None, bn_stats=None, pre=None, fold=None):
         ctx.pre_st = pre.st if pre is not None else None
         ctx.c3 = pre is not None or conv3x3_ok(x, wb, stride, padding)
+        ctx.s2 = False  # the stride-2 forward predicate held (gates the in-tree input gradient)
         # fold: the _FoldSlot of the BatchNorm + ReLU (no residual) whose output x is -- or,
         # with pre, stands for -- and which no one else reads: the input gradient may
         # absorb that BatchNorm's backward mask and partial sums (conv3x3_dgrad_bn_hip)
@@ -676,7 +742,9 @@ class _ConvNHWCFn(torch.autograd.Function):
             y, bn_stats.part = conv3x3_stats_hip(x, wb, pre)
         elif not ctx.c3 and conv3x3s2_ok(x, wb, stride, padding):
             # 3x3 / stride 2 / pad 1 (ResNet's downsample conv2): the stride-2 MFMA forward
-            # against the library; the gradients below are those of any strided layer
+            # against the library; backward adds the in-tree input gradient to the strided
+            # layer's candidates
+            ctx.s2 = True
             key = (x.size(0) * x.size(2) * x.size(3), x.size(1), wb.size(0), 3, 3, 2, 1)
             if (bn_stats is not None and conv3x3_stats_enabled()
                     and not torch.are_deterministic_algorithms_enabled()):
@@ -768,9 +836,16 @@ class _ConvNHWCFn(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             key = (x.size(0) * dy.size(2) * dy.size(3), cin, cout, kh, kw, stride[0], padding[0])
             be_w = _pick("wgrad_kxk" if st is None else "wgrad_kxk_pre", key, wgrad)
-        if need_dx:  # MIOpen is the only backend of a strided or non-3x3 input gradient
+        if need_dx and ctx.c3:
             key = (x.size(0) * x.size(2) * x.size(3), cin, cout, 3, 3, 1, 1)
-            be_d = _pick("dgrad_kxk", key, dgrad) if ctx.c3 else "miopen"
+            be_d = _pick("dgrad_kxk", key, dgrad)
+        elif need_dx and ctx.s2 and conv3x3s2_dgrad_ok(dy, wb, x.size(2), x.size(3)):
+            # 3x3 / stride 2 / pad 1 whose forward predicate held: the quad-tiled MFMA kernel
+            # against the library (in deterministic mode the kernel, untimed)
+            dgrad["hip"] = lambda: conv3x3s2_dgrad_hip(dy, wb, x.size(2), x.size(3))
+            be_d = _pick_dgrad_s2((x.size(0) * x.size(2) * x.size(3), cin, cout, 3, 3, 2, 1), dgrad)
+        elif need_dx:  # MIOpen is the only backend of any other strided or non-3x3 input gradient
+            be_d = "miopen"
         if be_d == "miopen" and be_w == "miopen":
             # MIOpen for both gradients: one call, as F.conv2d's autograd makes it
             dxm, dw = _miopen_bwd(dy, x, wb, stride, padding, True, True)
