@@ -131,6 +131,27 @@ void scale_(Tensor x, double s) {
   rla::launch_scale(x.data_ptr<float>(), x.numel(), (float)s, cur_stream(x));
 }
 
+// per-block sums of squares in a fixed order (csrc/optim_kernels.hip clip_partials_kernel)
+Tensor clip_partials(Tensor x, int64_t nblk, optional<Tensor> out) {
+  check_dev(x, "x", at::kFloat);
+  check_aligned(x, "x", 16);
+  TORCH_CHECK(nblk >= 1 && nblk <= rla::kClipMaxBlocks, "clip_partials: nblk must be in [1, ", rla::kClipMaxBlocks,
+              "], got ", nblk);
+  const at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor part;
+  if (out.has_value() && out->defined()) {
+    check_dev(*out, "out", at::kFloat);
+    TORCH_CHECK(out->device() == x.device(), "out must be on ", x.device(), ", not ", out->device());
+    TORCH_CHECK(out->numel() == nblk, "out has ", out->numel(), " elements, expected ", nblk);
+    part = *out;
+  } else {
+    part = at::empty({nblk}, x.options());
+  }
+  TORCH_CHECK(rla::launch_clip_partials(x.data_ptr<float>(), x.numel(), part.data_ptr<float>(), (int)nblk,
+                                        cur_stream(x)) == 0, "clip_partials launch failed");
+  return part;
+}
+
 Tensor sumsq(Tensor x) {
   check_dev(x, "x", at::kFloat);
   check_aligned(x, "x", 16);
@@ -206,7 +227,8 @@ void mlp3(int64_t kind, Tensor x_u8, Tensor labels, Tensor order, Tensor counter
           bool advance_step, double lr,
           double beta1, double beta2, double eps, double weight_decay, double grad_scale, optional<Tensor> lr_t,
           bool adamw, optional<Tensor> stamps, std::vector<int64_t> dp_ctx, optional<Tensor> head_part,
-          optional<Tensor> hand, int64_t dp_proto, bool dp_loop, int64_t repeat) {
+          optional<Tensor> hand, int64_t dp_proto, bool dp_loop, int64_t repeat, optional<Tensor> clip_part,
+          double clip_max_norm, optional<Tensor> clip_out, int64_t clip_nblk) {
   TORCH_CHECK(kind >= 0 && kind <= 7, "mlp3: bad kind ", kind);
   TORCH_CHECK(repeat >= 1, "mlp3: repeat must be >= 1");
   TORCH_CHECK(rla::mlp_supported((int)L1, (int)L2), "no fused MLP kernel for layer sizes ", L1, "/", L2);
@@ -316,12 +338,40 @@ void mlp3(int64_t kind, Tensor x_u8, Tensor labels, Tensor order, Tensor counter
     }
     TORCH_CHECK(!dp_loop || kind == rla::kMLP3Step1DP, "loopback is a one-launch-step diagnostic");
   }
+  // gradient clipping of the ADAM tail: the norm partials (clip_partials over `grads`),
+  // the bound and the optional [norm, coef, #clipped, #non-finite] report
+  rla::MLP3Clip clip{nullptr, 0, 0.f, nullptr};
+  const bool has_part = clip_part.has_value() && clip_part->defined();
+  const bool has_out = clip_out.has_value() && clip_out->defined();
+  if (has_part || has_out || clip_max_norm != 0.0 || clip_nblk >= 0) {
+    TORCH_CHECK(kind == rla::kMLP3TailAdam, "mlp3: clip arguments belong to the ADAM tail (kind 3), not kind ", kind);
+    TORCH_CHECK(has_part, "mlp3: clip_max_norm / clip_out need clip_part");
+    TORCH_CHECK(clip_max_norm > 0.0, "mlp3: clip_max_norm must be > 0");
+    check_dev(*clip_part, "clip_part", at::kFloat);
+    TORCH_CHECK(clip_part->device() == params.device(), "clip_part must be on ", params.device(), ", not ",
+                clip_part->device());
+    if (clip_nblk < 0) clip_nblk = clip_part->numel();  // default: every partial of clip_part
+    TORCH_CHECK(clip_nblk >= 1 && clip_nblk <= rla::kClipMaxBlocks, "mlp3: clip_nblk must be in [1, ",
+                rla::kClipMaxBlocks, "], got ", clip_nblk);
+    TORCH_CHECK(clip_part->numel() >= clip_nblk, "clip_part has ", clip_part->numel(), " elements, need >= ",
+                clip_nblk);
+    clip.part = clip_part->data_ptr<float>();
+    clip.nblk = (int)clip_nblk;
+    clip.max_norm = (float)clip_max_norm;
+    if (has_out) {
+      check_dev(*clip_out, "clip_out", at::kFloat);
+      TORCH_CHECK(clip_out->device() == params.device(), "clip_out must be on ", params.device(), ", not ",
+                  clip_out->device());
+      TORCH_CHECK(clip_out->numel() >= 4, "clip_out must hold 4 floats (norm, coef, #clipped, #non-finite)");
+      clip.out = clip_out->data_ptr<float>();
+    }
+  }
   // repeat: the same launch back to back (every step's state lives on the device:
   // counters, rings, generations), issued from this C++ loop -- one host call for a
   // window of steps, a few us of launch work each against ~8 us of GPU time
   const hipStream_t st = cur_stream(params);
   for (int64_t i = 0; i < repeat; ++i)
-    TORCH_CHECK(rla::launch_mlp3(a, (int)kind, st) == 0, "fused MLP v3 launch failed");
+    TORCH_CHECK(rla::launch_mlp3(a, (int)kind, st, &clip) == 0, "fused MLP v3 launch failed");
 }
 
 void mlp_adam(Tensor params, Tensor grads, Tensor exp_avg, Tensor exp_avg_sq, Tensor shadow, int64_t L1,
@@ -1025,6 +1075,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("multi_copy", &multi_copy, "multi-tensor copy/scale/cast via a chunk table");
   m.def("scale_", &scale_, "in-place scale of an fp32 arena");
   m.def("sumsq", &sumsq, "sum of squares of an fp32 arena");
+  m.def("clip_partials", &clip_partials, "fixed-order per-block sums of squares of an fp32 arena [nblk]",
+        py::arg("x"), py::arg("nblk"), py::arg("out") = py::none());
   m.def("mlp_train_step", &mlp_train_step, "fused MNIST-MLP forward+backward(+Adam) step",
         py::arg("x_u8"), py::arg("x_f32"), py::arg("labels"), py::arg("order"), py::arg("counters"),
         py::arg("n_batches"), py::arg("B"), py::arg("L1"), py::arg("L2"), py::arg("params"),
@@ -1034,7 +1086,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("adamw"), py::arg("stamps") = py::none());
   m.def("mlp_eval", &mlp_eval, "fused MNIST-MLP forward + NLL/accuracy");
   m.def("mlp3", &mlp3, "fused MNIST-MLP step v3 (pipelined layer 1): kind 0 step, 1 head, 2 tail-grad, "
-        "3 tail-adam, 4 prime, 5 step with the in-kernel xGMI exchange, 6 one-launch step (B <= 32)");
+        "3 tail-adam, 4 prime, 5 step with the in-kernel xGMI exchange, 6 one-launch step (B <= 32)",
+        py::arg("kind"), py::arg("x_u8"), py::arg("labels"), py::arg("order"), py::arg("counters"),
+        py::arg("n_batches"), py::arg("B"), py::arg("L1"), py::arg("L2"), py::arg("params"), py::arg("grads"),
+        py::arg("exp_avg"), py::arg("exp_avg_sq"), py::arg("shadow"), py::arg("dh1t"), py::arg("xring"),
+        py::arg("h1pre"), py::arg("act"), py::arg("yring"), py::arg("stats"), py::arg("advance_step"), py::arg("lr"),
+        py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"), py::arg("grad_scale"),
+        py::arg("lr_t"), py::arg("adamw"), py::arg("stamps"), py::arg("dp_ctx"), py::arg("head_part"),
+        py::arg("hand"), py::arg("dp_proto"), py::arg("dp_loop"), py::arg("repeat"),
+        py::arg("clip_part") = py::none(), py::arg("clip_max_norm") = 0.0, py::arg("clip_out") = py::none(),
+        py::arg("clip_nblk") = -1);
   m.def("dp_pack_roundtrip", &dp_pack_roundtrip, "packed DP exchange wire form of fp32 pairs, encoded + decoded");
   m.def("mlp3_hand_words", [](int64_t l1, int64_t l2) { return rla::mlp3_hand_words((int)l1, (int)l2); });
   m.def("mlp3_hand_layout", []() {

@@ -42,6 +42,10 @@ void launch_multi_copy(const int64_t* table, int64_t nchunks, float scale, int a
                        hipStream_t stream);
 void launch_scale(float* x, int64_t n, float s, hipStream_t stream);
 void launch_sumsq(const float* x, int64_t n, float* out, hipStream_t stream);
+// Fixed-order sum of squares: part[b] = sum of g[i]^2 over block b's contiguous slice
+// (b < nblk <= kClipMaxBlocks; an empty slice gives 0).  No atomics and no memset: the
+// same input gives the same bits on every call.  g 16-byte aligned.  -1: bad nblk.
+int launch_clip_partials(const float* g, int64_t n, float* part, int nblk, hipStream_t stream);
 
 // ---------------------------------------------------------------------------
 // Fused BatchNorm(+ReLU)(+residual add) over NHWC bf16 activations viewed as
@@ -288,7 +292,22 @@ struct MLP3AdamCacheLayout {
   int step, betas, bc1, bc2_sqrt;
 };
 MLP3AdamCacheLayout mlp3_adam_cache_layout();
-int launch_mlp3(const MLP3Args& a, int kind, hipStream_t stream);
+// Global-norm gradient clipping of the ADAM tail (kMLP3TailAdam only): its own kernel
+// argument, so MLP3Args and every other kind's launch stay as they are.  `part` holds
+// launch_clip_partials' per-block sums of squares over the gradient arena; each block's
+// scalar lane sums them in index order and derives
+//   norm = sqrt(sum) * grad_scale,  coef = min(1, max_norm / (norm + 1e-6))
+// (torch.nn.utils.clip_grad_norm_), and the Adam epilogues read grads * grad_scale * coef.
+// `out` (optional, [4] fp32, written by block 0 alone): [0] norm, [1] coef,
+// [2] += 1 when coef < 1, [3] += 1 when the norm is NaN / Inf.  part == nullptr: no clipping.
+struct MLP3Clip {
+  const float* part;
+  int nblk;
+  float max_norm;
+  float* out;
+};
+constexpr int kClipMaxBlocks = 64;
+int launch_mlp3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip* clip = nullptr);
 
 int mlp3_act_rows(int L1, int L2);
 int mlp3_h1_copies(int L1);  // H1pre copies per ring slot (mlp_step3.hip H1Copies)

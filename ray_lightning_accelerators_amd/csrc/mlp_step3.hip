@@ -1477,13 +1477,17 @@ __device__ __forceinline__ void dp_end_nosync(const MLP3Args& a, uint32_t gen, i
 __device__ __forceinline__ int dp_task_owner(const MLP3Args& a, int task) { return task % a.dp_world; }
 
 // ADAM mode: flat Adam over every non-W1 parameter (after the allreduce).
+// ``clipped``: the gradient is further scaled by the clip coefficient (MLP3Clip).
 template <int L1, int L2>
-__device__ __forceinline__ void small_adam_flat(const MLP3Args& a, const AdamScal& o, int blk, int nblk) {
+__device__ __forceinline__ void small_adam_flat(const MLP3Args& a, const AdamScal& o, int blk, int nblk,
+                                                bool clipped, float coef) {
   using O = Off<L1, L2>;
   __bf16* SHW = reinterpret_cast<__bf16*>(a.shadow);
   for (int64_t i = O::B1 + (int64_t)blk * blockDim.x + threadIdx.x; i < O::NP; i += (int64_t)nblk * blockDim.x) {
     float m = a.exp_avg[i], v = a.exp_avg_sq[i];
-    const float p = adam1(a.params[i], a.grads[i] * a.grad_scale, m, v, o);
+    float gr = a.grads[i] * a.grad_scale;
+    if (clipped) gr *= coef;
+    const float p = adam1(a.params[i], gr, m, v, o);
     a.params[i] = p;
     a.exp_avg[i] = m;
     a.exp_avg_sq[i] = v;
@@ -1520,14 +1524,35 @@ __device__ __forceinline__ void tail_head_stats(const MLP3Args& a, const int64_t
   st[3] = (float)t;
 }
 
+// ADAM mode with clipping: the clip coefficient from the norm partials (kernels.h
+// MLP3Clip), by the lane that computes Adam's scalars.  Every block sums the same
+// partials in the same (index) order, so every block holds the same bits; block 0 alone
+// reports (one writer per launch, launches are stream-ordered: plain stores).
+__device__ __forceinline__ float tail_clip_coef(const MLP3Args& a, const MLP3Clip& c) {
+  float ss = 0.f;
+  for (int i = 0; i < c.nblk; ++i) ss += c.part[i];
+  const float norm = sqrtf(ss) * a.grad_scale;
+  const float coef = fminf(1.f, c.max_norm / (norm + 1e-6f));
+  if (blockIdx.x == 0 && c.out) {
+    c.out[0] = norm;
+    c.out[1] = coef;
+    if (coef < 1.f) c.out[2] += 1.f;
+    if (!(fabsf(norm) <= 3.402823466e+38f)) c.out[3] += 1.f;
+  }
+  return coef;
+}
+
 template <int L1, int L2>
-__global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, int mode) {
+__global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, int mode, MLP3Clip clip) {
   constexpr int TN1 = L1 / 16;
   constexpr int NT = 64 * TN1;
   __shared__ __attribute__((aligned(16))) __bf16 sX[kBMax * kXSS];
   __shared__ __attribute__((aligned(16))) __bf16 sXn[kBMax * kXSS];
   __shared__ __attribute__((aligned(16))) __bf16 sW[L1 * kXSS];
   __shared__ AdamScal sh_o;
+  __shared__ float sh_coef;  // ADAM mode: the clip coefficient, beside sh_o
+  __shared__ int sh_clip;    // ... and whether this launch clips (published with it: the
+                             // clip argument's registers are free before the tile loop)
   const int tid = threadIdx.x, lane = tid & 63, ct = tid >> 6, r16 = lane & 15, g = lane >> 4;
   const bool dp = mode == kFusedDP;
   const bool do_grad = mode == kFused || mode == kGrad || dp;
@@ -1545,8 +1570,13 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
   const int64_t t_step = cn[0];  // already advanced by the head kernel
   const float lr_now = a.lr_ptr ? a.lr_ptr[0] : a.lr;
   auto scalars = [&]() {
-    if (tid == 0 && do_adam)
+    if (tid == 0 && do_adam) {
       adam_scalars(sh_o, t_step, lr_now, a.beta1, a.beta2, a.eps, a.weight_decay, a.adamw);
+      if (mode == kAdam) {
+        sh_clip = clip.part != nullptr;
+        if (clip.part) sh_coef = tail_clip_coef(a, clip);
+      }
+    }
   };
   if ((int)blockIdx.x >= kTiles) {  // small parameters (block-uniform branch)
     const int sblk = (int)blockIdx.x - kTiles;
@@ -1562,7 +1592,8 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
     if (mode == kAdam) {
       scalars();
       __syncthreads();
-      small_adam_flat<L1, L2>(a, sh_o, sblk, (int)gridDim.x - kTiles);
+      const bool clipped = sh_clip != 0;
+      small_adam_flat<L1, L2>(a, sh_o, sblk, (int)gridDim.x - kTiles, clipped, clipped ? sh_coef : 1.f);
       stamp_max(a, 11);
       return;
     }
@@ -1707,9 +1738,12 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
   }
   if (do_adam) {
     const AdamScal o = sh_o;
+    const bool clipped = mode == kAdam && sh_clip != 0;
+    const float coef = clipped ? sh_coef : 1.f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const float gr = (mode == kAdam) ? g4.v[i] * a.grad_scale : acc[i];
+      float gr = (mode == kAdam) ? g4.v[i] * a.grad_scale : acc[i];
+      if (clipped) gr *= coef;
       p4.v[i] = adam1(p4.v[i], gr, m4.v[i], v4.v[i], o);
       w4[i] = (__bf16)p4.v[i];
     }
@@ -2123,7 +2157,7 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args a) {
 }
 
 template <int L1, int L2>
-int dispatch3(const MLP3Args& a, int kind, hipStream_t stream) {
+int dispatch3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip& clip) {
   constexpr int kOneGrid = 1 + kTiles + One<L1, L2>::NSMALL;
   if (kind == kMLP3Step1) {
     if (a.B > 32 || !a.hand || kOneGrid > 256) return -5;
@@ -2173,7 +2207,7 @@ int dispatch3(const MLP3Args& a, int kind, hipStream_t stream) {
     int extra = (int)((nsmall + NT - 1) / NT);
     grid += extra < 64 ? extra : 64;
   }
-  if (mode >= 0) hipLaunchKernelGGL((mlp3_tail_kernel<L1, L2>), dim3(grid), dim3(NT), 0, stream, a, mode);
+  if (mode >= 0) hipLaunchKernelGGL((mlp3_tail_kernel<L1, L2>), dim3(grid), dim3(NT), 0, stream, a, mode, clip);
   return 0;
 }
 
@@ -2207,9 +2241,15 @@ MLP3HandLayout mlp3_hand_layout() {
 }
 MLP3AdamCacheLayout mlp3_adam_cache_layout() { return {kHandAdamStep, kHandAdamBetas, kHandAdamBc1, kHandAdamBc2}; }
 
-int launch_mlp3(const MLP3Args& a, int kind, hipStream_t stream) {
+int launch_mlp3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip* clip_in) {
   if (a.B > kBMax || a.B < 1) return -2;
-#define RLA_CASE(a1, a2) if (a.L1 == a1 && a.L2 == a2) return dispatch3<a1, a2>(a, kind, stream);
+  // clipping belongs to the ADAM tail alone; every other kind launches without it
+  MLP3Clip clip{nullptr, 0, 0.f, nullptr};
+  if (clip_in && clip_in->part) {
+    if (kind != kMLP3TailAdam || clip_in->nblk < 1 || clip_in->nblk > kClipMaxBlocks) return -8;
+    clip = *clip_in;
+  }
+#define RLA_CASE(a1, a2) if (a.L1 == a1 && a.L2 == a2) return dispatch3<a1, a2>(a, kind, stream, clip);
   RLA_CASE(32, 32) RLA_CASE(32, 64) RLA_CASE(32, 128) RLA_CASE(32, 256)
   RLA_CASE(64, 64) RLA_CASE(64, 128) RLA_CASE(64, 256)
   RLA_CASE(128, 64) RLA_CASE(128, 128) RLA_CASE(128, 256)

@@ -253,6 +253,56 @@ __global__ __launch_bounds__(kOptThreads) void sumsq_kernel(const float* x, int6
   }
 }
 
+// Sum of squares for the fused MNIST step's gradient clipping, reproducible bit for bit
+// (sumsq_kernel's float atomics make its value depend on arrival order).  The n / 4
+// 16-byte quads are split into gridDim.x contiguous slices of ceil(quads / blocks); the
+// last block also owns the n % 4 scalar tail.  Every reduction has a fixed order:
+//   thread   quad q0 + tid, + 256, ... into four accumulators (one per component),
+//            then the tail element (last block, tid < n % 4), then (a0 + a1) + (a2 + a3);
+//   wave     xor butterfly 32, 16, ..., 1 (every lane ends with the same value);
+//   block    the four wave sums through LDS, added in wave order.
+// part[b] is a plain store by thread 0; a block with an empty slice stores 0.
+// (ops/optim.py clip_partials is the same order in torch, the depth bound is derived in
+// tests/test_clip_reference.py.)
+__global__ __launch_bounds__(kOptThreads) void clip_partials_kernel(const float* __restrict__ g, int64_t n,
+                                                                    float* __restrict__ part) {
+  const int64_t n4 = n >> 2;
+  const int64_t per = (n4 + gridDim.x - 1) / gridDim.x;
+  int64_t q0 = (int64_t)blockIdx.x * per;
+  if (q0 > n4) q0 = n4;
+  int64_t q1 = q0 + per;
+  if (q1 > n4) q1 = n4;
+  const float4* g4 = reinterpret_cast<const float4*>(g);
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  for (int64_t q = q0 + threadIdx.x; q < q1; q += kOptThreads) {
+    const float4 v = g4[q];
+    a0 += v.x * v.x;
+    a1 += v.y * v.y;
+    a2 += v.z * v.z;
+    a3 += v.w * v.w;
+  }
+  if (blockIdx.x == gridDim.x - 1) {
+    const int64_t i = (n4 << 2) + threadIdx.x;
+    if (i < n) a0 += g[i] * g[i];
+  }
+  float acc = (a0 + a1) + (a2 + a3);
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  __shared__ float wsum[kOptThreads / kWave];
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float s = wsum[0];
+    for (int w = 1; w < kOptThreads / kWave; ++w) s += wsum[w];
+    part[blockIdx.x] = s;
+  }
+}
+
+int launch_clip_partials(const float* g, int64_t n, float* part, int nblk, hipStream_t stream) {
+  if (nblk < 1 || nblk > kClipMaxBlocks || n < 0) return -1;
+  hipLaunchKernelGGL(clip_partials_kernel, dim3((unsigned)nblk), dim3(kOptThreads), 0, stream, g, n, part);
+  return 0;
+}
+
 void launch_scale(float* x, int64_t n, float s, hipStream_t stream) {
   if (n <= 0) return;
   hipLaunchKernelGGL(scale_kernel, dim3(opt_grid(n)), dim3(kOptThreads), 0, stream, x, n, s);

@@ -498,7 +498,12 @@ class Trainer:
             from .graph_step import maybe_graph_step
 
             return maybe_graph_step(self, model)
-        if self.accumulate_grad_batches != 1 or self.gradient_clip_val:
+        if self.accumulate_grad_batches != 1:
+            return None
+        # gradient_clip_val: only a fused step that clips itself (it reads
+        # trainer.gradient_clip_val); a model declines by leaving
+        # ``fused_step_clips_gradients`` unset, or by raising in configure_fused_step
+        if self.gradient_clip_val and not getattr(model, "fused_step_clips_gradients", False):
             return None
         try:
             return model.configure_fused_step(self)

@@ -13,7 +13,10 @@ HBM as uint8, and each step is TWO launches -- a head kernel (forward, loss,
 backward of the small layers, next-batch gather) and a 49+ workgroup tail
 (dW1, Adam, the next step's layer-1 partial).  At world size > 1 the tail also
 exchanges the gradient tiles with the peers over xGMI inside its Adam epilogue
-(``RLAConfig.fused_dp``), else head / tail / allreduce / tail.  Batches the
+(``RLAConfig.fused_dp``), else head / tail / allreduce / tail.
+``Trainer(gradient_clip_val=c)`` stays on the HIP path: head / tail(grad) /
+[allreduce] / norm partials / tail(adam), the clip coefficient derived on the
+device (``FusedMLPEngine(clip_norm=c)``).  Batches the
 resident path cannot serve (e.g. user transforms) use a one-launch fp32-input
 kernel; CPU / unsupported shapes use the ordinary autograd path.
 """
@@ -98,6 +101,9 @@ class LightningMNISTClassifier(LightningModule):
         return DataLoader(self._val_set, batch_size=self.batch_size, drop_last=True)
 
     # ------------------------------------------------------------ fast path
+    # the fused step clips by global norm itself (Trainer(gradient_clip_val=...))
+    fused_step_clips_gradients = True
+
     def configure_fused_step(self, trainer):
         if type(self).training_step is not LightningMNISTClassifier.training_step or \
                 type(self).forward is not LightningMNISTClassifier.forward:
@@ -162,6 +168,10 @@ class FusedMNISTStep:
         self.gs = opt._rla_groups[0]
         self.dev = dev
         self.world = trainer.world_size
+        clip = float(getattr(trainer, "gradient_clip_val", 0.0) or 0.0)
+        if clip < 0.0:
+            raise RuntimeError("fused step cannot clip to a negative norm")
+        self.clip_norm = clip if clip > 0.0 else None
         self.counters = torch.zeros(2, dtype=torch.int64, device=dev)
         self.counters[0] = self.gs.step
         self.lr_val = float(opt.param_groups[0]["lr"])
@@ -189,7 +199,8 @@ class FusedMNISTStep:
                     exp_avg=self.gs.m[: self.np], exp_avg_sq=self.gs.v[: self.np])
         dp_ctx = None
         rearm = None
-        if self.world > 1 and get_config().fused_dp:
+        # clipping needs the whole averaged gradient before Adam: the allreduce route
+        if self.world > 1 and get_config().fused_dp and self.clip_norm is None:
             from ..parallel.comm import get_native_comm
 
             comm = get_native_comm()  # every rank reaches here together (first epoch)
@@ -199,7 +210,8 @@ class FusedMNISTStep:
         eng = FusedMLPEngine(self.L1, self.L2, B, lr=float(g["lr"]), betas=tuple(g["betas"]), eps=g["eps"],
                              weight_decay=g["weight_decay"], device=self.dev, world_size=self.world,
                              rank=self.trainer.global_rank, allreduce=self._allreduce, buffers=bufs,
-                             stats_ring=ENGINE_STATS_RING, dp_context=dp_ctx, dp_rearm=rearm)
+                             stats_ring=ENGINE_STATS_RING, dp_context=dp_ctx, dp_rearm=rearm,
+                             clip_norm=self.clip_norm)
         eng.set_step(self.gs.step)
         eng.lr_tensor = self.lr_tensor  # LR schedulers update one device scalar
         eng.attach_dataset(self._u8, self._labels)
@@ -287,7 +299,7 @@ class FusedMNISTStep:
         p = self.arena.data[: self.np]
         gr = self.arena.grad[: self.np]
         m, v = self.gs.m[: self.np], self.gs.v[: self.np]
-        fused = self.world == 1
+        fused = self.world == 1 and self.clip_norm is None
         kw = dict(L1=self.L1, L2=self.L2, exp_avg=m, exp_avg_sq=v, stats=self.stats, apply_adam=fused,
                   advance_step=True, lr=self.lr_val, betas=(b1, b2), eps=g["eps"], weight_decay=g["weight_decay"],
                   lr_tensor=self.lr_tensor, counters=self.counters)
@@ -309,7 +321,14 @@ class FusedMNISTStep:
         if not fused:
             if self._allreduce is not None and self.acc.sync is not None:
                 self._allreduce(self.arena.grad[: self.np])
-            from ..ops.optim import fused_adam_
+            from ..ops.optim import clip_partials, fused_adam_
+
+            if self.clip_norm is not None:
+                # loader-fed batches are rare and slow anyway: the coefficient with torch
+                # ops on the device (no host sync), the gradient scaled in place
+                norm = clip_partials(gr, 32).sum().sqrt() * (1.0 / self.world)
+                coef = torch.clamp(self.clip_norm / (norm + 1e-6), max=1.0)
+                gr.mul_(coef)
 
             fused_adam_(p, gr, m, v, lr=self.lr_val, betas=(b1, b2), eps=g["eps"], weight_decay=g["weight_decay"],
                         grad_scale=1.0 / self.world, step=self.counters[0:1], lr_tensor=self.lr_tensor)

@@ -313,6 +313,10 @@ def mlp3_launch(
     dp_proto: int = -1,
     dp_loop: bool = False,
     repeat: int = 1,
+    clip_part: Optional[torch.Tensor] = None,
+    clip_max_norm: float = 0.0,
+    clip_out: Optional[torch.Tensor] = None,
+    clip_nblk: Optional[int] = None,
 ) -> None:
     """One v3 launch (GPU only; ``repeat``: that many identical launches back to back
     from one C++ loop -- every step's state lives on the device).  ``kind``: MLP3_STEP (head + fused tail, world size 1),
@@ -331,12 +335,26 @@ def mlp3_launch(
     per granule), DP_OWNER (2, reduce-scatter / owner Adam / all-gather); -1 reads
     ``RLA_DP_PROTO``.  ``dp_loop``: loopback diagnostic (one process plays every rank of
     ``dp_ctx`` through its own region).  ``order`` is [2, n_batches * B]:
-    the current and the next epoch's sample order (counters[4] selects)."""
+    the current and the next epoch's sample order (counters[4] selects).
+
+    Gradient clipping (MLP3_TAIL_ADAM only; any other kind raises before a launch):
+    ``clip_part`` = ``ops.optim.clip_partials(grads, nblk)``, ``clip_max_norm`` > 0.  The
+    tail sums the partials in index order, ``norm = sqrt(sum) * grad_scale``, ``coef =
+    min(1, clip_max_norm / (norm + 1e-6))`` (``torch.nn.utils.clip_grad_norm_``), and its
+    Adam reads ``grads * grad_scale * coef``.  ``clip_nblk``: partials to read (default:
+    all of ``clip_part``).  ``clip_out`` (optional, 4 fp32): [0] norm, [1] coef,
+    [2] += 1 when coef < 1, [3] += 1 when the norm is NaN / Inf."""
+    if clip_part is not None or clip_out is not None or clip_max_norm or clip_nblk is not None:
+        if kind != MLP3_TAIL_ADAM:
+            raise ValueError(f"mlp3_launch: clip arguments belong to MLP3_TAIL_ADAM, not kind {kind}")
+        if clip_part is None or not clip_max_norm > 0.0:
+            raise ValueError("mlp3_launch: clipping needs clip_part and clip_max_norm > 0")
     require().mlp3(
         int(kind), x_u8, labels, order, counters, int(n_batches), int(B), int(L1), int(L2), params, grads, exp_avg,
         exp_avg_sq, shadow, dh1t, xring, h1pre, act, yring, stats, bool(advance_step), float(lr), float(betas[0]),
         float(betas[1]), float(eps), float(weight_decay), float(grad_scale), lr_tensor, bool(adamw), stamps,
         [int(v) for v in (dp_ctx or ())], head_part, hand, int(dp_proto), bool(dp_loop), int(repeat),
+        clip_part, float(clip_max_norm), clip_out, -1 if clip_nblk is None else int(clip_nblk),
     )
 
 

@@ -214,6 +214,74 @@ def sumsq(x: torch.Tensor) -> torch.Tensor:
     return (x.float() * x.float()).sum().reshape(1)
 
 
+CLIP_THREADS = 256  # csrc/optim_kernels.hip kOptThreads
+CLIP_MAX_BLOCKS = 64  # csrc/kernels.h kClipMaxBlocks
+
+
+def clip_slices(n: int, nblk: int) -> List[Tuple[int, int]]:
+    """Element range ``[lo, hi)`` of each of ``clip_partials``' ``nblk`` blocks: the
+    ``n // 4`` 16-byte quads in contiguous runs of ``ceil(quads / nblk)``, the ``n % 4``
+    scalar tail with the last block; blocks past the data get an empty range."""
+    n4 = n // 4
+    per = -(-n4 // nblk)
+    out = []
+    for b in range(nblk):
+        q0 = min(b * per, n4)
+        q1 = min(q0 + per, n4)
+        # the last block's quads always end at n4 (nblk * per >= n4): its range runs on into the tail
+        out.append((4 * q0, n if b == nblk - 1 else 4 * q1))
+    return out
+
+
+def clip_partials(x: torch.Tensor, nblk: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per-block sums of squares of a flat fp32 arena, ``[nblk]``, in a FIXED order:
+    the same input gives the same bits on every call (``sumsq`` adds with float
+    atomics).  The fused MNIST step's gradient clipping sums them in index order.
+
+    ``1 <= nblk <= 64``; block ``b`` covers ``clip_slices(n, nblk)[b]``.  GPU: ``x``
+    must start on a 16-byte boundary (float4 loads; the ``n % 4`` tail is scalar), else
+    ``RuntimeError`` before a launch.  CPU: the kernel's summation order in torch fp32
+    -- per thread the quads ``q0 + tid, + 256, ...`` into one accumulator per component,
+    the tail element, ``(a0 + a1) + (a2 + a3)``, an xor butterfly over the 64 lanes, the
+    four waves in order."""
+    nblk = int(nblk)
+    if not 1 <= nblk <= CLIP_MAX_BLOCKS:
+        raise ValueError(f"clip_partials: nblk must be in [1, {CLIP_MAX_BLOCKS}], got {nblk}")
+    if out is not None and (out.numel() != nblk or out.dtype != torch.float32 or out.device != x.device):
+        raise ValueError(f"clip_partials: out must be {nblk} fp32 elements on {x.device}")
+    if use_native(x):
+        return require().clip_partials(x, nblk, out)
+    with torch.no_grad():
+        flat = x.detach().reshape(-1).float()
+        n = flat.numel()
+        n4 = n // 4
+        per = -(-n4 // nblk)
+        iters = -(-per // CLIP_THREADS)
+        sq = torch.zeros(nblk, iters * CLIP_THREADS * 4)
+        for b in range(nblk):
+            q0 = min(b * per, n4)
+            q1 = min(q0 + per, n4)
+            seg = flat[4 * q0:4 * q1]
+            sq[b, : seg.numel()] = seg * seg
+        sq = sq.view(nblk, iters, CLIP_THREADS, 4)
+        acc = torch.zeros(nblk, CLIP_THREADS, 4)
+        for it in range(iters):
+            acc += sq[:, it]  # the padding adds +0: exact
+        tail = flat[4 * n4:]
+        acc[nblk - 1, : tail.numel(), 0] += tail * tail
+        a = ((acc[..., 0] + acc[..., 1]) + (acc[..., 2] + acc[..., 3])).view(nblk, CLIP_THREADS // 64, 64)
+        lanes = torch.arange(64)
+        for off in (32, 16, 8, 4, 2, 1):
+            a = a + a[..., lanes ^ off]
+        part = a[:, 0, 0].clone()
+        for w in range(1, CLIP_THREADS // 64):
+            part += a[:, w, 0]
+    if out is not None:
+        out.copy_(part)
+        return out
+    return part.to(x.device)
+
+
 def iter_chunks(n: int, chunk: int) -> Iterable[Tuple[int, int]]:
     for off in range(0, n, chunk):
         yield off, min(chunk, n - off)

@@ -20,6 +20,10 @@ re-designed for MI355X instead of translating PL's DDP loop:
   its gradient values with the peers over xGMI inside its Adam epilogue (kinds
   Step1DP / StepDP); otherwise head -> tail(grad) -> allreduce(SUM) ->
   tail(adam), the 1/world average folded into ``grad_scale``;
+* ``clip_norm`` (global-norm gradient clipping, ``torch.nn.utils.clip_grad_norm_``):
+  at every batch and world size head -> tail(grad) -> [allreduce] -> norm partials
+  (``ops.optim.clip_partials``, fixed summation order) -> tail(adam), which derives
+  the coefficient on the device -- no host sync, bitwise-reproducible, graph-capturable;
 * the step's device work can be captured into a hipGraph (``capture``): batch
   cursor, step counter, ring slot and epoch buffer live on the device, so
   replays advance by themselves.
@@ -39,7 +43,7 @@ import torch.distributed as dist
 
 from ..config import get_config
 from ..ops import fused_mlp
-from ..ops.optim import fused_adam_
+from ..ops.optim import clip_partials, fused_adam_
 
 log = logging.getLogger(__name__)
 
@@ -59,6 +63,12 @@ class FusedStepNumericsError(RuntimeError):
                 f"reported loss stays finite); last affected optimizer step {int(last_step)}. "
                 "Remedies: Trainer(fused_step=False) (fp32 autograd path), a lower learning rate, or "
                 "RLA_MLP_SATURATION=warn to keep training with a warning.")
+
+
+# blocks of the clipped step's norm launch: 32 x 256 threads cover the default arena's
+# 6,970 quads in one pass, and the ADAM tail's scalar lane sums 32 partials
+CLIP_NBLK = 32
+_CLIP_HEALTH0 = {"clip_norm_last": None, "clip_coef_last": None, "clipped_steps": 0, "nonfinite_norm_steps": 0}
 
 
 def shard_indices(n: int, world: int, rank: int, epoch: int, seed: int, shuffle: bool,
@@ -98,6 +108,7 @@ class FusedMLPEngine:
         dp_proto: Optional[str] = None,
         dp_rearm: Optional[Callable[[], None]] = None,
         dp_loop: bool = False,
+        clip_norm: Optional[float] = None,
     ):
         """``buffers``: optional external fp32 tensors ``params`` / ``grads`` /
         ``exp_avg`` / ``exp_avg_sq`` (e.g. views of a Trainer's parameter arena,
@@ -111,7 +122,18 @@ class FusedMLPEngine:
         2); unset: ``RLA_DP_PROTO``.  ``dp_rearm``: collective reset of the exchange
         region (``NativeCommunicator.dp_rearm``), run before a protocol is first used.
         ``dp_loop``: loopback diagnostic (``dp_context`` of one process whose regions
-        all point at its own; see scripts/dp_overhead_probe.py)."""
+        all point at its own; see scripts/dp_overhead_probe.py).
+        ``clip_norm``: clip the (world-averaged) gradient to this global L2 norm before
+        Adam, as ``torch.nn.utils.clip_grad_norm_`` does; None / 0: no clipping.  The step
+        then always runs head -> tail(grad) -> [allreduce] -> norm partials -> tail(adam);
+        it does not combine with ``dp_context`` (the in-kernel exchange never holds the
+        whole averaged gradient before its Adam)."""
+        clip_norm = float(clip_norm) if clip_norm else None
+        if clip_norm is not None and not clip_norm > 0.0:
+            raise ValueError(f"clip_norm must be positive, got {clip_norm}")
+        if clip_norm is not None and dp_context is not None:
+            raise ValueError("clip_norm needs the allreduce route: the in-kernel data-parallel exchange "
+                             "(dp_context) cannot clip -- pass allreduce= and no dp_context")
         if not fused_mlp.mlp_supported(layer_1, layer_2):
             raise ValueError(f"no fused kernel for layer sizes {layer_1}/{layer_2}")
         if not 1 <= batch_size <= 256:
@@ -147,6 +169,14 @@ class FusedMLPEngine:
             self.exp_avg = torch.zeros(n, device=self.device)
             self.exp_avg_sq = torch.zeros(n, device=self.device)
         self.lr_tensor = torch.full((1,), self.lr, device=self.device)
+        self.clip_norm = clip_norm
+        self.clip_part = self.clip_out = None
+        if clip_norm is not None:
+            self.clip_part = torch.zeros(CLIP_NBLK, device=self.device)
+            # [0] norm, [1] coefficient of the last step, [2] steps clipped, [3] steps with a NaN / Inf norm
+            self.clip_out = torch.zeros(4, device=self.device)
+        self._clip_last = dict(_CLIP_HEALTH0)
+        self._clip_since = 0  # global_step when clip_out was last zeroed
         lay = fused_mlp.mlp_shadow_layout(self.L1, self.L2)
         self.shadow = torch.zeros(lay["total"], dtype=torch.bfloat16, device=self.device)
         bufs = fused_mlp.mlp3_buffers(self.L1, self.L2, self.B, self.device)
@@ -169,7 +199,9 @@ class FusedMLPEngine:
         # intermittent fidelity failures in long GPU sessions; round 6's post-mortem
         # showed the step bitwise equal to the two-launch step from a fresh engine in
         # the failing session (docs/one_launch_investigation.md), so the gate is gone.
-        self.one_launch = self.B <= fused_mlp.ONE_LAUNCH_MAX_B and os.environ.get("RLA_MLP_ONE_LAUNCH") != "0"
+        # clipping needs the whole gradient between two launches: never one launch
+        self.one_launch = (self.B <= fused_mlp.ONE_LAUNCH_MAX_B and os.environ.get("RLA_MLP_ONE_LAUNCH") != "0"
+                           and clip_norm is None)
         # world size > 1 with the xGMI context: the same one launch, each block
         # exchanging its values with the peers (protocol: self.dp_proto)
         self.dp_proto = "packed"
@@ -316,11 +348,27 @@ class FusedMLPEngine:
         graph replays.  ``blocking=False``: the last reading a ``check`` made, no sync.
         The CPU reference engine sums in fp32: all zeros."""
         if not self.native:
-            return {"saturated": 0, "nonfinite": 0, "last_step": 0, "timed_out": False}
+            return {"saturated": 0, "nonfinite": 0, "last_step": 0, "timed_out": False, **self._clip_health(True)}
         if not blocking:
-            return dict(self._health_last)
+            return {**self._health_last, **self._clip_health(False)}
         self._health_last = self._health_dict(self.hand[self._hl["err"]:self._hl["last_step"] + 1].tolist())
-        return dict(self._health_last)
+        return {**self._health_last, **self._clip_health(True)}
+
+    def _clip_health(self, blocking: bool) -> Dict[str, object]:
+        """The clipped step's report (``clip_out``): ``clip_norm_last`` / ``clip_coef_last``
+        -- the last step's gradient norm and coefficient (None before the first step or
+        without ``clip_norm``), ``clipped_steps`` -- steps whose coefficient was below 1,
+        ``nonfinite_norm_steps`` -- steps whose norm was NaN / Inf (passed through, as
+        torch does).  Device-side counts: graph replays included.  ``blocking=False``:
+        the last blocking reading.  An engine without ``clip_norm`` reports none of them."""
+        if self.clip_out is None:
+            return {}
+        if blocking:
+            norm, coef, clipped, bad = self.clip_out.tolist()
+            seen = self.global_step > self._clip_since  # a step ran since the engine was built / reset
+            self._clip_last = {"clip_norm_last": norm if seen else None, "clip_coef_last": coef if seen else None,
+                               "clipped_steps": int(clipped), "nonfinite_norm_steps": int(bad)}
+        return dict(self._clip_last)
 
     def reset_health(self) -> None:
         """Zero the saturation / non-finite counts and the last affected step
@@ -328,6 +376,10 @@ class FusedMLPEngine:
         ``check(blocking=False)`` is dropped: it predates the reset."""
         if self.native:
             self.hand[self._hl["sat"]:self._hl["last_step"] + 1].zero_()
+        if self.clip_out is not None:
+            self.clip_out.zero_()
+        self._clip_last = dict(_CLIP_HEALTH0)
+        self._clip_since = self.global_step
         self._hand_probe = None
         self._health_reported = (0, 0)
         self._health_last = {"saturated": 0, "nonfinite": 0, "last_step": 0,
@@ -472,7 +524,16 @@ class FusedMLPEngine:
             self._reference_step()
         else:
             kw = self._kw3()
-            if self.world_size == 1 and not self.dp_loop:
+            if self.clip_norm is not None:
+                fused_mlp.mlp3_launch(fused_mlp.MLP3_HEAD, stats=self.stats, **kw)
+                fused_mlp.mlp3_launch(fused_mlp.MLP3_TAIL_GRAD, stats=self.stats, **kw)
+                if self.allreduce is not None:
+                    self.allreduce(self.comm_buffer)
+                clip_partials(self.grads, CLIP_NBLK, out=self.clip_part)
+                fused_mlp.mlp3_launch(fused_mlp.MLP3_TAIL_ADAM, grad_scale=1.0 / self.world_size,
+                                      clip_part=self.clip_part, clip_max_norm=self.clip_norm,
+                                      clip_out=self.clip_out, **kw)
+            elif self.world_size == 1 and not self.dp_loop:
                 kind = fused_mlp.MLP3_STEP1 if self.one_launch else fused_mlp.MLP3_STEP
                 fused_mlp.mlp3_launch(kind, stats=self.stats, **kw)
             elif self.dp_ctx is not None:
@@ -492,7 +553,7 @@ class FusedMLPEngine:
         """fp32 PyTorch step with the device kernels' batch / counter semantics."""
         c = self.counters
         cursor, ob = int(c[1]), int(c[4])
-        fused = self.world_size == 1
+        fused = self.world_size == 1 and self.clip_norm is None
         fused_mlp.mlp_train_step(
             self.params, self.grads, L1=self.L1, L2=self.L2, B=self.B, labels=self.labels, x_u8=self.x_u8,
             order=self.order[ob], counters=c[:2], n_batches=self.n_batches, exp_avg=self.exp_avg,
@@ -507,9 +568,29 @@ class FusedMLPEngine:
         if not fused:
             if self.allreduce is not None:
                 self.allreduce(self.comm_buffer)
+            if self.clip_norm is not None:
+                self._reference_clip()
             fused_adam_(self.params, self.grads, self.exp_avg, self.exp_avg_sq, lr=self.lr, betas=self.betas,
                         eps=self.eps, weight_decay=self.wd, grad_scale=1.0 / self.world_size,
                         step=self.counters[0:1], lr_tensor=self.lr_tensor)
+
+    def _reference_clip(self) -> None:
+        """The ADAM tail's clipping in torch fp32: scales ``grads`` in place by the
+        coefficient (the 1 / world average stays in ``grad_scale``) and keeps ``clip_out``."""
+        part = clip_partials(self.grads, CLIP_NBLK, out=self.clip_part)
+        ss = torch.zeros((), dtype=torch.float32)
+        for i in range(CLIP_NBLK):  # index order, as the kernel's scalar lane
+            ss = ss + part[i]
+        norm = ss.sqrt() * torch.tensor(1.0 / self.world_size, dtype=torch.float32)
+        coef = torch.clamp(torch.tensor(self.clip_norm, dtype=torch.float32) / (norm + 1e-6), max=1.0)
+        if bool(torch.isnan(coef)):
+            coef = torch.ones(())  # fminf(1, NaN) = 1: the kernel passes a NaN norm through
+        if float(coef) < 1.0:
+            self.grads.mul_(coef)
+            self.clip_out[2] += 1
+        if not bool(torch.isfinite(norm)):
+            self.clip_out[3] += 1
+        self.clip_out[0], self.clip_out[1] = norm, coef
 
     def _advance_host(self, n: int) -> None:
         self.global_step += n
