@@ -164,10 +164,14 @@ __device__ __forceinline__ int64_t ld_state(const int64_t* p, int i) {
 }
 
 // Diagnostic stamp (probe builds only pass a.stamps): latest end over many blocks.
+// PROBE = false (the production instances of the one-launch step): no code at all.
+template <bool PROBE = true>
 __device__ __forceinline__ void stamp_max(const MLP3Args& a, int k) {
-  if (a.stamps && threadIdx.x == 0)
-    atomicMax(reinterpret_cast<unsigned long long*>(a.stamps + k),
-              (unsigned long long)__builtin_amdgcn_s_memrealtime());
+  if constexpr (PROBE) {
+    if (a.stamps && threadIdx.x == 0)
+      atomicMax(reinterpret_cast<unsigned long long*>(a.stamps + k),
+                (unsigned long long)__builtin_amdgcn_s_memrealtime());
+  }
 }
 
 // One-launch step bookkeeping (mlp3_one_kernel): counters[kSeq] counts its
@@ -211,8 +215,11 @@ constexpr float kH1Sat = 32.0f;  // == kFixSat / kFix
 // whose (step, betas) differ from the key computes the values itself, so nothing on
 // the host invalidates the entry: a fresh buffer, set_step, a checkpoint load, a
 // two-launch step or other betas just miss once.  Same ordering rule as the counters:
-// read through the scalar path before the block's acknowledgement, written by block 0
-// after every block's acknowledgement.
+// read through the scalar path before the block's acknowledgement (one request per wave,
+// in the kernel's state batch; the acknowledgement waits lgkmcnt(0) too), written by
+// block 0 after every block's acknowledgement.
+// (A fifth word -- the learning rate block 0 saw and its quotient step_size, so that a hit
+// divides nothing -- was built and measured: no gain, profiles/r14_one_launch_prologue.)
 constexpr int kHandAdamStep = 20, kHandAdamBetas = 21, kHandAdamBc1 = 22, kHandAdamBc2 = 23;
 static_assert(kHandAdamStep > kHandLastStep && kHandAdamBc2 < kHandWords, "cache words are spare words of hand");
 __device__ __forceinline__ unsigned long long adam_betas_key(float b1, float b2) {
@@ -271,6 +278,7 @@ __device__ __forceinline__ void h1_report(const MLP3Args& a, const H1Health& h, 
 // only) by the one wave that uses them, so the round trip hides under the head pass.
 struct RepPre {
   bool active;  // wave-uniform: the PreWave of a W1 tile block
+  int64_t slot;  // counters[3], set by the hook once it has waited for the step state
   int64_t si;
   int kt;
   uint4 xn;
@@ -371,7 +379,8 @@ __device__ __forceinline__ HeadStats head_stats(const float* sZ) {
   return HeadStats{0.f + loss, 0.f + correct, 0.f + cnt};
 }
 
-template <int BC, int L1, int L2, bool MULTI, bool REP, class Hook = NoHook>
+// PROBE = false: every stamp below compiles away (the one-launch production instances)
+template <int BC, int L1, int L2, bool MULTI, bool REP, class Hook = NoHook, bool PROBE = true>
 __device__ __forceinline__ void head_body(const MLP3Args& a, char* smem, RepPre* pre = nullptr,
                                           const Hook& hook = Hook{}) {
   using C = Cfg3<BC, L1, L2>;
@@ -393,13 +402,14 @@ __device__ __forceinline__ void head_body(const MLP3Args& a, char* smem, RepPre*
 
   const int nchunks = MULTI ? (a.B + BC - 1) / BC : 1;
   const int c = MULTI ? (int)blockIdx.x : 0;  // this workgroup's batch rows [c * BC, c * BC + BC)
-  const bool stamp_ok = a.stamps && tid == 0 && c == 0 && (!REP || blockIdx.x == 0);
+  const bool stamp_ok = PROBE && a.stamps && tid == 0 && c == 0 && (!REP || blockIdx.x == 0);
 
   // device counters: uniform scalar loads, no LDS broadcast round trip
-  const int64_t t = ld_state(a.counters, 0) + 1;
-  const int64_t cursor = ld_state(a.counters, 1);
-  const int64_t slot = ld_state(a.counters, 3);
-  const int64_t ob = ld_state(a.counters, 4);
+  // (REP: the caller's state batch; `slot` comes from the hook, which waits for it)
+  const int64_t t = REP ? 0 : ld_state(a.counters, 0) + 1;
+  const int64_t cursor = REP ? 0 : ld_state(a.counters, 1);
+  int64_t slot = REP ? 0 : ld_state(a.counters, 3);
+  const int64_t ob = REP ? 0 : ld_state(a.counters, 4);
   const int Bp = (a.B + 31) / 32 * 32;
   __bf16* ACT = reinterpret_cast<__bf16*>(a.act);
   __bf16* DH1T = reinterpret_cast<__bf16*>(a.dh1t);
@@ -523,6 +533,7 @@ __device__ __forceinline__ void head_body(const MLP3Args& a, char* smem, RepPre*
       asm volatile("" ::: "memory");  // the hook's loads stay younger than every load above
       hook();
       asm volatile("" ::: "memory");
+      slot = pre->slot;
     }
     // LDS writes last: their waits cover only the earliest loads (in-order vmcnt)
     if (tid < NBIAS) sBias[tid] = bias_v;
@@ -641,7 +652,10 @@ __device__ __forceinline__ void head_body(const MLP3Args& a, char* smem, RepPre*
       // gfx9 encoding: vmcnt in bits 3:0, expcnt 7 (bits 6:4), lgkmcnt 15 (bits 11:8).
       asm volatile("" ::: "memory");
       static_assert(kRepHookLoads < 16, "vmcnt immediate");
-      __builtin_amdgcn_s_waitcnt(0x0F70 | kRepHookLoads);  // vmcnt(kRepHookLoads): the hook's loads may fly on
+      // lgkmcnt(0) with it, explicitly: every scalar load of state another block overwrites
+      // (counters, kSeq, the Adam cache words) has returned before the acknowledgement too --
+      // free here, the LDS traffic ahead of it is consumed by now.
+      __builtin_amdgcn_s_waitcnt(0x0070 | kRepHookLoads);  // vmcnt(kRepHookLoads): the hook's loads may fly on
       asm volatile("" ::: "memory");
       __syncthreads();
       if (tid == 0)
@@ -1809,6 +1823,19 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
 // themselves, there.  Bits as adam_scalars() in either case.
 // The small-parameter blocks run their Adam in registers before the acknowledgement
 // wait and only store after it.
+//
+// Prologue (profiles/r14_one_launch_prologue): two scalar batches, each waited for once.
+//   kernarg batch  every MLP3Args field read before the first barrier, requested at entry
+//                  and pinned in SGPRs by an empty asm (left to itself the compiler fetched
+//                  the arguments in three to five dependent batches and fetched some of
+//                  them again under register pressure, one scalar round trip each);
+//   state batch    counters[0, 1, 3, 4, kSeq], the four Adam cache words, *lr_ptr (and the
+//                  exchange generation), requested right after it and waited for at the
+//                  top of the hook -- behind the biases, H1pre, labels, weight fragments
+//                  and the small blocks' Adam-state prefetch, which need kernel arguments
+//                  only, so their round trip and the state's overlap.  counters[kSeq] is
+//                  parked in LDS by thread 0, which alone reads it later.
+// The hook's loads stay the youngest kRepHookLoads vector loads of every wave.
 // ---------------------------------------------------------------------------
 template <int L1, int L2>
 struct One {
@@ -1823,10 +1850,17 @@ struct One {
 };
 static_assert(One<128, 256>::lds <= 160 * 1024, "one-launch LDS budget");
 
+// The ordering rule of the hand-off, for the acknowledging side: every load of state that
+// another block overwrites has RETURNED before this block's acknowledgement -- the vector
+// loads of shared state (vmcnt) and the scalar loads of the counters, counters[kSeq] and
+// the Adam cache words (lgkmcnt).  The acknowledgement's s_waitcnt in head_body names
+// both: vmcnt(kRepHookLoads) lgkmcnt(0).  Each of those scalar words is requested once
+// per wave, in the kernel's state batch, and never again (mlp3_one_kernel).
 // lane 0 waits for launch `seq`'s acknowledgements, then the whole block proceeds
-__device__ __forceinline__ void one_wait_acks(const MLP3Args& a, int64_t seq, int* sh_fail) {
+// (`sh_seq`: counters[kSeq] as thread 0 parked it in LDS after its state wait)
+__device__ __forceinline__ void one_wait_acks(const MLP3Args& a, const int64_t* sh_seq, int* sh_fail) {
   if (threadIdx.x == 0) {
-    const long long target = (long long)(seq + 1) * (long long)gridDim.x;
+    const long long target = (long long)(*sh_seq + 1) * (long long)gridDim.x;
     const long long* ack = reinterpret_cast<const long long*>(a.hand + kHandAck);
     int64_t n = 0;
     *sh_fail = 0;
@@ -1863,14 +1897,18 @@ __device__ __forceinline__ void one_wait_acks(const MLP3Args& a, int64_t seq, in
 // protocol's code (a run-time switch over all three cost the head pass ~0.5 us and
 // the tile epilogue ~1.4 us of register pressure, profiles/r3_dp/dp_phases.log).
 // NW: the rank class of the packed / owner polls (world size <= NW; see dp_peer_issue).
-template <int L1, int L2, int DPP, int NW = 8>
-__global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args a) {
+// PROBE: the phase stamps (scripts/dp_phase_probe.py, mlp_phase_probe.py) exist only in
+// the probe instances, which dispatch3 picks when a.stamps is set; in the production
+// instances no stamp, no branch on a.stamps and no exec mask saved around one is compiled.
+template <int L1, int L2, int DPP, int NW = 8, bool PROBE = false>
+__global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args ka) {
   constexpr bool DP = DPP >= 0;
   using C = typename One<L1, L2>::C;
   using S = SmallTasks<L1, L2>;
   constexpr int TN1 = L1 / 16, Bp = 32;
   __shared__ __attribute__((aligned(16))) char smem[One<L1, L2>::lds];
   __shared__ int sh_fail;
+  __shared__ int64_t sh_seq;  // counters[kSeq], parked by thread 0 after the state wait
   __bf16* sH2T = (__bf16*)(smem + One<L1, L2>::oImg);
   __bf16* sDH2T = sH2T + L2 * C::TS;
   __bf16* sDH1T = sDH2T + L2 * C::TS;
@@ -1882,19 +1920,43 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args a) {
   const int blk = blockIdx.x;
   const bool tile = blk >= 1 && blk <= kTiles, small = blk > kTiles;
   const int kt = blk - 1;
-  if (a.stamps && blk == 1 && tid == 0) a.stamps[8] = __builtin_amdgcn_s_memrealtime();
-  stamp_max(a, 13);  // probe builds: the latest block start (dispatch skew)
+  // ---- the kernarg batch: every argument read before the first barrier, requested at
+  // entry and waited for once.  The empty asm makes each value an SGPR the compiler can
+  // neither re-request later (it did, under register pressure: a dependent scalar round
+  // trip each time) nor fetch in further batches along the way.
+  // The asm sees the pointers as GLOBAL ones (a generic pointer out of an asm would turn
+  // every access through it into a flat_ instruction, which counts on lgkmcnt as well).
+  MLP3Args a = ka;
+#define RLA_PIN(f) auto g_##f = (__attribute__((address_space(1))) std::remove_pointer_t<decltype(a.f)>*)a.f
+  RLA_PIN(counters); RLA_PIN(hand); RLA_PIN(lr_ptr); RLA_PIN(params); RLA_PIN(exp_avg); RLA_PIN(exp_avg_sq);
+  RLA_PIN(shadow); RLA_PIN(h1pre); RLA_PIN(yring); RLA_PIN(xring); RLA_PIN(order); RLA_PIN(dp_gen); RLA_PIN(dp_err);
+#undef RLA_PIN
+  asm volatile(""
+               : "+s"(g_counters), "+s"(g_hand), "+s"(g_lr_ptr), "+s"(g_params), "+s"(g_exp_avg), "+s"(g_exp_avg_sq),
+                 "+s"(g_shadow), "+s"(g_h1pre), "+s"(g_yring), "+s"(g_xring), "+s"(g_order), "+s"(a.order_stride),
+                 "+s"(a.n_batches), "+s"(a.B), "+s"(a.advance_step), "+s"(a.lr), "+s"(a.beta1), "+s"(a.beta2),
+                 "+s"(a.eps), "+s"(a.weight_decay), "+s"(a.adamw), "+s"(g_dp_err));
+  if constexpr (DP) asm volatile("" : "+s"(g_dp_gen));
+  a.counters = (int64_t*)g_counters, a.hand = (unsigned long long*)g_hand, a.lr_ptr = (const float*)g_lr_ptr;
+  a.params = (float*)g_params, a.exp_avg = (float*)g_exp_avg, a.exp_avg_sq = (float*)g_exp_avg_sq;
+  a.shadow = (uint16_t*)g_shadow, a.h1pre = (int*)g_h1pre, a.yring = (int*)g_yring;
+  a.xring = (uint16_t*)g_xring, a.order = (const int64_t*)g_order;
+  a.dp_gen = (uint32_t*)g_dp_gen, a.dp_err = (int*)g_dp_err;
+  if (PROBE && a.stamps && blk == 1 && tid == 0) a.stamps[8] = __builtin_amdgcn_s_memrealtime();
+  stamp_max<PROBE>(a, 13);  // probe builds: the latest block start (dispatch skew)
 
-  // the state of this step: nobody overwrites it before every block's ack
-  const int64_t c0 = ld_state(a.counters, 0), cursor = ld_state(a.counters, 1);
-  const int64_t slot = ld_state(a.counters, 3), ob = ld_state(a.counters, 4);
-  const int64_t seq = ld_state(a.counters, kSeq);
-  // the cached bias corrections and their key, written by the previous launch's block 0
+  // ---- the state batch: this step's counters, the Adam cache entry the previous
+  // launch's block 0 left, the device learning rate (and the exchange generation),
+  // requested once, here, and waited for once, at the top of the hook below -- behind
+  // every head-pass load that needs kernel arguments only, so the two round trips
+  // overlap.  Nobody overwrites any of it before every block's acknowledgement.
+  int64_t c0 = ld_state(a.counters, 0), cursor = ld_state(a.counters, 1);
+  int64_t slot = ld_state(a.counters, 3), ob = ld_state(a.counters, 4);
+  int64_t seq = ld_state(a.counters, kSeq);
   const int64_t* hand_s = reinterpret_cast<const int64_t*>(a.hand);
-  const int64_t ck_step = ld_state(hand_s, kHandAdamStep), ck_betas = ld_state(hand_s, kHandAdamBetas);
-  const int64_t ck_bc1 = ld_state(hand_s, kHandAdamBc1), ck_bc2 = ld_state(hand_s, kHandAdamBc2);
-  const int64_t t_adam = a.advance_step ? c0 + 1 : c0;  // the step this launch's Adam belongs to
-  const uint32_t dgen = DP ? dp_gen_now(a) : 0u;
+  int64_t ck_step = ld_state(hand_s, kHandAdamStep), ck_betas = ld_state(hand_s, kHandAdamBetas);
+  int64_t ck_bc1 = ld_state(hand_s, kHandAdamBc1), ck_bc2 = ld_state(hand_s, kHandAdamBc2);
+  uint32_t dgen = DP ? dp_gen_now(a) : 0u;
   const int B = a.B;
 
   // ---- tail-role loads that need nothing from this step, issued before the head
@@ -1910,7 +1972,10 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args a) {
   // the device learning rate through the SCALAR path: as a vector load, the f64 bias
   // corrections below (thread 0) waited vmcnt(0) for it -- i.e. for every prologue
   // prefetch -- before wave 0 issued a single head-pass load (profiles/r4_dp)
-  const float lr_now = a.lr_ptr ? ((const __attribute__((address_space(4))) float*)(a.lr_ptr))[0] : a.lr;
+  // (as bits: a float select is a VALU select, and the value has to stay an SGPR)
+  uint32_t lr_bits =
+      a.lr_ptr ? ((const __attribute__((address_space(4))) uint32_t*)(a.lr_ptr))[0] : __float_as_uint(a.lr);
+  float lr_now = 0.f;
   // wave 0 of a tile: row (lane & 31) of X[t] (parked by the previous step) and the
   // sample index of row (lane & 31) of the NEXT batch (its pixels load after the ack)
   __bf16* XR = reinterpret_cast<__bf16*>(a.xring);
@@ -1923,13 +1988,21 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args a) {
   pre.kt = tile ? kt : 0;
   pre.xn = make_uint4(0u, 0u, 0u, 0u);
   pre.yn = -1;
-  int64_t nc = cursor + 1, nob = ob;
-  if (nc >= a.n_batches) { nc = 0; nob ^= 1; }
+  int64_t t_adam = 0;  // the step this launch's Adam belongs to
   // the private prologue loads, exactly kRepHookLoads per wave on every block (clamped
   // addresses where the wave does not need them): the next sample index first (its
   // value is needed right after the ack, so it is waited for before the others)
   const int kt_c = tile ? kt : 0;
   auto hook = [&]() {
+    // the one wait for the state batch: from here on the values are plain SGPRs
+    asm volatile(""
+                 : "+s"(c0), "+s"(cursor), "+s"(slot), "+s"(ob), "+s"(seq), "+s"(ck_step), "+s"(ck_betas), "+s"(ck_bc1),
+                   "+s"(ck_bc2), "+s"(lr_bits), "+s"(dgen));
+    lr_now = __uint_as_float(lr_bits);
+    pre.slot = slot;
+    t_adam = a.advance_step ? c0 + 1 : c0;
+    int64_t nc = cursor + 1, nob = ob;
+    if (nc >= a.n_batches) { nc = 0; nob ^= 1; }
     pre.si = a.order[nob * a.order_stride + nc * B + (xb < B ? xb : 0)];
     const __bf16* cur = XR + (slot * kTiles + kt_c) * tile_elems + xb * 16;
     xc0 = ld8(cur);
@@ -1937,6 +2010,7 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args a) {
     p4 = *reinterpret_cast<const F4*>(a.params + gidx);
     m4 = *reinterpret_cast<const F4*>(a.exp_avg + gidx);
     v4 = *reinterpret_cast<const F4*>(a.exp_avg_sq + gidx);
+    if (tid == 0) sh_seq = seq;  // read back by thread 0 where it polls / advances (no SGPR pair held)
     // Adam's scalars, behind the wave's last load (they are needed after the head pass
     // only): the bias corrections from the cache block 0 of the previous launch filled
     // -- a wave-uniform branch on scalar loads, consumed before the block's
@@ -1956,11 +2030,11 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args a) {
     }
   };
   // ---- the serial chain, on this CU (tile wave 0 also issues the next batch's loads) ----
-  head_body<32, L1, L2, false, true>(a, smem, &pre, hook);
+  head_body<32, L1, L2, false, true, decltype(hook), PROBE>(a, smem, &pre, hook);
 
   // (the block's acknowledgement went out inside head_body, once its loads had landed)
-  if (a.stamps && blk == 1 && tid == 0) a.stamps[9] = __builtin_amdgcn_s_memrealtime();
-  stamp_max(a, 12);  // probe builds: the latest head-pass end over all blocks
+  if (PROBE && a.stamps && blk == 1 && tid == 0) a.stamps[9] = __builtin_amdgcn_s_memrealtime();
+  stamp_max<PROBE>(a, 12);  // probe builds: the latest head-pass end over all blocks
 
   if (tile) {
     // the next batch's pixels (+ label, tile 0) were issued inside the head pass
@@ -1969,7 +2043,7 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args a) {
       *reinterpret_cast<bf16x8*>(sX + xb * kXSS + 8) = xc1;
     }
     __syncthreads();
-    if (a.stamps && blk == 1 && tid == 0) a.stamps[7] = __builtin_amdgcn_s_memrealtime();
+    if (PROBE && a.stamps && blk == 1 && tid == 0) a.stamps[7] = __builtin_amdgcn_s_memrealtime();
     bf16x4 w4;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     if (mw) {
@@ -1982,6 +2056,9 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args a) {
     }
     bool adam_done = false, store_mv = true;
     if constexpr (DP) {  // the tile's allreduce, inside the epilogue (protocol: a.dp_proto)
+      // the exchange reads the kernel argument itself: its run-time index into dp_regions
+      // would keep the pinned copy `a` in memory instead of registers
+      const MLP3Args& a = ka;
       const uint32_t gen = dgen;
       const int dslot = (int)(gen & 1u);
       int fail = 0;
@@ -2050,8 +2127,8 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args a) {
       if (kt == 0) a.yring[(slot ^ 1) * Bp + xb] = xb < B ? yn : -1;
     }
     __syncthreads();
-    if (a.stamps && blk == 1 && tid == 0) a.stamps[14] = __builtin_amdgcn_s_memrealtime();
-    stamp_max(a, 15);  // probe builds: the latest tile block past its staging barrier
+    if (PROBE && a.stamps && blk == 1 && tid == 0) a.stamps[14] = __builtin_amdgcn_s_memrealtime();
+    stamp_max<PROBE>(a, 15);  // probe builds: the latest tile block past its staging barrier
     if (mw) {
       // next step's layer-1 partial: H1pre[b][m] += sum_{16 px} X'[b][px] W1[m][px]
       constexpr int G = H1Copies<L1>::G;
@@ -2069,13 +2146,14 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args a) {
       }
       h1_report(a, health, c0 + 1);
     }
-    if (a.stamps && blk == 1 && tid == 0) a.stamps[10] = __builtin_amdgcn_s_memrealtime();
-    stamp_max(a, 5);  // probe builds: the latest W1-tile block end
+    if (PROBE && a.stamps && blk == 1 && tid == 0) a.stamps[10] = __builtin_amdgcn_s_memrealtime();
+    stamp_max<PROBE>(a, 5);  // probe builds: the latest W1-tile block end
   } else if (small) {
     const RepLds L{(const __bf16*)(smem + C::oH1T), sH2T, sDH2T, (const __bf16*)(smem + C::odZT), sDH1T, C::TS};
     small_compute<L1, L2, true>(a, true, task, r, &L);
     bool adam_done = false, store_mv = true;
     if constexpr (DP) {
+      const MLP3Args& a = ka;  // as in the tile's exchange above
       const uint32_t gen = dgen;
       const int dslot = (int)(gen & 1u);
       int fail = 0;
@@ -2113,9 +2191,9 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args a) {
     if (!adam_done) small_adam(r, *sh_o);
     // (asking for the acknowledgement count ahead of small_compute, to hide the poll's
     // round trip, cost the step 0.35 us: profiles/r11_adam_cache)
-    one_wait_acks(a, seq, &sh_fail);  // every block has read the weights / biases this overwrites
+    one_wait_acks(a, &sh_seq, &sh_fail);  // every block has read the weights / biases this overwrites
     small_store<L1, L2>(a, r, store_mv);  // r.v: the new weights
-    stamp_max(a, 6);  // probe builds: the latest small-parameter block end
+    stamp_max<PROBE>(a, 6);  // probe builds: the latest small-parameter block end
   } else {
     // block 0: stats, the consumed H1pre slot zeroed (the invariant), then the advanced state
     // the rows' parked loss stats, summed by wave 0 before it polls for the acks
@@ -2127,7 +2205,7 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args a) {
     const int64_t t_next = a.advance_step ? t_adam + 1 : t_adam;
     AdamBias nbc{0.0, 0.0};
     if (w == 1 && lane < 2) nbc = adam_bias2(t_next, a.beta1, a.beta2);
-    one_wait_acks(a, seq, &sh_fail);
+    one_wait_acks(a, &sh_seq, &sh_fail);
     if (tid == 64) {  // every block has consumed the previous entry
       a.hand[kHandAdamStep] = (unsigned long long)t_next;
       a.hand[kHandAdamBetas] = adam_betas_key(a.beta1, a.beta2);
@@ -2142,7 +2220,7 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args a) {
       if (nc >= a.n_batches) { nc = 0; nob ^= 1; }
       const int64_t st[kCnt] = {a.advance_step ? t : t - 1, nc, cursor, slot ^ 1, nob};
       for (int k = 0; k < kCnt; ++k) a.counters[k] = a.counters[kCnt + k] = st[k];
-      a.counters[kSeq] = seq + 1;
+      a.counters[kSeq] = sh_seq + 1;
       if (a.stats) {
         float* sr = a.stats + (int)((t - 1) % (a.stats_ring > 0 ? a.stats_ring : 1)) * 4;
         sr[0] = hs.loss * (1.f / (float)B);
@@ -2150,17 +2228,33 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args a) {
         sr[2] = hs.cnt;
         sr[3] = (float)t;
       }
-      if (a.stamps) a.stamps[4] = __builtin_amdgcn_s_memrealtime();
+      if (PROBE && a.stamps) a.stamps[4] = __builtin_amdgcn_s_memrealtime();
     }
   }
-  stamp_max(a, 11);
+  stamp_max<PROBE>(a, 11);
 }
+
+// The probe instances of the one-launch step (a.stamps set): the widths and protocols the
+// probe scripts run -- the plain step at 32-64 and 128-256, and at 32-64 the packed (rank
+// classes 2 and 8) and owner (rank class 8) exchanges.  Anything else with stamps is an
+// error (-9), never a silent run of an unstamped kernel.
+template <int L1, int L2>
+constexpr bool kProbePlain = (L1 == 32 && L2 == 64) || (L1 == 128 && L2 == 256);
+template <int L1, int L2>
+constexpr bool kProbeDP = L1 == 32 && L2 == 64;
 
 template <int L1, int L2>
 int dispatch3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip& clip) {
   constexpr int kOneGrid = 1 + kTiles + One<L1, L2>::NSMALL;
   if (kind == kMLP3Step1) {
     if (a.B > 32 || !a.hand || kOneGrid > 256) return -5;
+    if (a.stamps) {
+      if constexpr (kProbePlain<L1, L2>)
+        hipLaunchKernelGGL((mlp3_one_kernel<L1, L2, -1, 8, true>), dim3(kOneGrid), dim3(kThreads), 0, stream, a);
+      else
+        return -9;
+      return 0;
+    }
     hipLaunchKernelGGL((mlp3_one_kernel<L1, L2, -1>), dim3(kOneGrid), dim3(kThreads), 0, stream, a);
     return 0;
   }
@@ -2174,6 +2268,16 @@ int dispatch3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip& c
       return -7;
     const dim3 g(kOneGrid), b(kThreads);
     const int nw = a.dp_world <= 2 ? 2 : (a.dp_world <= 4 ? 4 : 8);
+    if (a.stamps) {
+      if constexpr (kProbeDP<L1, L2>) {
+        if (a.dp_proto == 1 && nw == 2) hipLaunchKernelGGL((mlp3_one_kernel<L1, L2, 1, 2, true>), g, b, 0, stream, a);
+        else if (a.dp_proto == 1 && nw == 8) hipLaunchKernelGGL((mlp3_one_kernel<L1, L2, 1, 8, true>), g, b, 0, stream, a);
+        else if (a.dp_proto == 2 && nw == 8) hipLaunchKernelGGL((mlp3_one_kernel<L1, L2, 2, 8, true>), g, b, 0, stream, a);
+        else return -9;
+        return 0;
+      }
+      return -9;
+    }
     if (a.dp_proto == 0) hipLaunchKernelGGL((mlp3_one_kernel<L1, L2, 0>), g, b, 0, stream, a);
     else if (a.dp_proto == 1 && nw == 2) hipLaunchKernelGGL((mlp3_one_kernel<L1, L2, 1, 2>), g, b, 0, stream, a);
     else if (a.dp_proto == 1 && nw == 4) hipLaunchKernelGGL((mlp3_one_kernel<L1, L2, 1, 4>), g, b, 0, stream, a);
