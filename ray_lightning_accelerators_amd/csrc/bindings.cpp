@@ -220,7 +220,8 @@ void mlp_train_step(optional<Tensor> x_u8, optional<Tensor> x_f32, Tensor labels
 }
 
 // v3 pipelined step.  kind: 0 step (head + fused tail), 1 head only (grads),
-// 2 tail GRAD, 3 tail ADAM (after the allreduce), 4 PRIME (H1pre of the pending batch).
+// 2 tail GRAD, 3 tail ADAM (after the allreduce), 4 PRIME (H1pre of the pending batch),
+// 8 tail ACC (a micro-batch that does not close its accumulation window).
 void mlp3(int64_t kind, Tensor x_u8, Tensor labels, Tensor order, Tensor counters, int64_t n_batches, int64_t B,
           int64_t L1, int64_t L2, Tensor params, Tensor grads, Tensor exp_avg, Tensor exp_avg_sq, Tensor shadow,
           Tensor dh1t, Tensor xring, Tensor h1pre, Tensor act, Tensor yring, optional<Tensor> stats,
@@ -228,8 +229,9 @@ void mlp3(int64_t kind, Tensor x_u8, Tensor labels, Tensor order, Tensor counter
           double beta1, double beta2, double eps, double weight_decay, double grad_scale, optional<Tensor> lr_t,
           bool adamw, optional<Tensor> stamps, std::vector<int64_t> dp_ctx, optional<Tensor> head_part,
           optional<Tensor> hand, int64_t dp_proto, bool dp_loop, int64_t repeat, optional<Tensor> clip_part,
-          double clip_max_norm, optional<Tensor> clip_out, int64_t clip_nblk) {
-  TORCH_CHECK(kind >= 0 && kind <= 7, "mlp3: bad kind ", kind);
+          double clip_max_norm, optional<Tensor> clip_out, int64_t clip_nblk, bool acc_add, bool acc_rows,
+          optional<Tensor> acc_head_row) {
+  TORCH_CHECK(kind >= 0 && kind <= 8, "mlp3: bad kind ", kind);
   TORCH_CHECK(repeat >= 1, "mlp3: repeat must be >= 1");
   TORCH_CHECK(rla::mlp_supported((int)L1, (int)L2), "no fused MLP kernel for layer sizes ", L1, "/", L2);
   TORCH_CHECK(B >= 1 && B <= 256, "fused MLP step supports 1 <= batch <= 256");
@@ -366,12 +368,24 @@ void mlp3(int64_t kind, Tensor x_u8, Tensor labels, Tensor order, Tensor counter
       clip.out = clip_out->data_ptr<float>();
     }
   }
+  // gradient accumulation (GRAD tail / tail ACC; launch_mlp3 refuses it anywhere else)
+  rla::MLP3Acc acc{acc_add ? 1 : 0, acc_rows ? 1 : 0, nullptr};
+  if (acc_head_row.has_value() && acc_head_row->defined()) {
+    check_dev(*acc_head_row, "acc_head_row", at::kFloat);
+    TORCH_CHECK(acc_head_row->device() == params.device() && acc_head_row->numel() >= 4,
+                "acc_head_row must hold 4 floats on ", params.device());
+    acc.head_row = acc_head_row->data_ptr<float>();
+  }
+  if (acc_rows) TORCH_CHECK(counters.numel() > rla::kMLP3RowWord, "mlp3: acc_rows needs counters of >= 12 int64");
   // repeat: the same launch back to back (every step's state lives on the device:
   // counters, rings, generations), issued from this C++ loop -- one host call for a
   // window of steps, a few us of launch work each against ~8 us of GPU time
   const hipStream_t st = cur_stream(params);
   for (int64_t i = 0; i < repeat; ++i)
-    TORCH_CHECK(rla::launch_mlp3(a, (int)kind, st, &clip) == 0, "fused MLP v3 launch failed");
+  {
+    const int rc = rla::launch_mlp3(a, (int)kind, st, &clip, &acc);
+    TORCH_CHECK(rc == 0, "fused MLP v3 launch failed (kind ", kind, ", code ", rc, ")");
+  }
 }
 
 void mlp_adam(Tensor params, Tensor grads, Tensor exp_avg, Tensor exp_avg_sq, Tensor shadow, int64_t L1,
@@ -1086,7 +1100,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("adamw"), py::arg("stamps") = py::none());
   m.def("mlp_eval", &mlp_eval, "fused MNIST-MLP forward + NLL/accuracy");
   m.def("mlp3", &mlp3, "fused MNIST-MLP step v3 (pipelined layer 1): kind 0 step, 1 head, 2 tail-grad, "
-        "3 tail-adam, 4 prime, 5 step with the in-kernel xGMI exchange, 6 one-launch step (B <= 32)",
+        "3 tail-adam, 4 prime, 5 step with the in-kernel xGMI exchange, 6 one-launch step (B <= 32), "
+        "8 tail-acc (gradient accumulation: a micro-batch inside its window)",
         py::arg("kind"), py::arg("x_u8"), py::arg("labels"), py::arg("order"), py::arg("counters"),
         py::arg("n_batches"), py::arg("B"), py::arg("L1"), py::arg("L2"), py::arg("params"), py::arg("grads"),
         py::arg("exp_avg"), py::arg("exp_avg_sq"), py::arg("shadow"), py::arg("dh1t"), py::arg("xring"),
@@ -1095,7 +1110,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("lr_t"), py::arg("adamw"), py::arg("stamps"), py::arg("dp_ctx"), py::arg("head_part"),
         py::arg("hand"), py::arg("dp_proto"), py::arg("dp_loop"), py::arg("repeat"),
         py::arg("clip_part") = py::none(), py::arg("clip_max_norm") = 0.0, py::arg("clip_out") = py::none(),
-        py::arg("clip_nblk") = -1);
+        py::arg("clip_nblk") = -1, py::arg("acc_add") = false, py::arg("acc_rows") = false,
+        py::arg("acc_head_row") = py::none());
   m.def("dp_pack_roundtrip", &dp_pack_roundtrip, "packed DP exchange wire form of fp32 pairs, encoded + decoded");
   m.def("mlp3_hand_words", [](int64_t l1, int64_t l2) { return rla::mlp3_hand_words((int)l1, (int)l2); });
   m.def("mlp3_hand_layout", []() {

@@ -277,7 +277,7 @@ struct MLP3Args {
   int64_t hand_spin;
 };
 enum MLP3Kind { kMLP3Step = 0, kMLP3Head = 1, kMLP3TailGrad = 2, kMLP3TailAdam = 3, kMLP3Prime = 4,
-                kMLP3StepDP = 5, kMLP3Step1 = 6, kMLP3Step1DP = 7 };
+                kMLP3StepDP = 5, kMLP3Step1 = 6, kMLP3Step1DP = 7, kMLP3TailAcc = 8 };
 int64_t mlp3_hand_words(int L1, int L2);  // int64 words of the one-launch step's hand-off buffer
 // word indices of `hand`: ack / err (the one-launch hand-off), sat / nonfinite / last_step
 // (exact, monotonic u64 health counts of the layer-1 partial sums)
@@ -307,7 +307,29 @@ struct MLP3Clip {
   float* out;
 };
 constexpr int kClipMaxBlocks = 64;
-int launch_mlp3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip* clip = nullptr);
+// Gradient accumulation (kMLP3TailGrad / kMLP3TailAcc only): its own kernel argument, as
+// MLP3Clip.  A window of K micro-batches ends in one optimizer step; every micro-batch but
+// the last runs head -> TailAcc (gradients, no Adam, the next batch's layer-1 partial from
+// the unchanged weights), the last head -> TailGrad -> ... -> TailAdam.
+//   add       grads += this micro-batch's gradient (one fp32 add per element) instead of the
+//             overwrite; the first micro-batch of a window overwrites, so nothing zero-fills.
+//   rows      one stats row per MICRO-batch: the tail writes the row at
+//             counters[kMLP3RowWord] % stats_ring and advances that word (the optimizer step
+//             no longer identifies a row); column 3 is the optimizer step the batch feeds.
+//   head_row  [4] fp32, with `rows` and B <= 32: where this micro-batch's one-block head left
+//             its row (the head launch was given it as a one-row `stats`).
+// All zero / nullptr: the launches as they were.
+struct MLP3Acc {
+  int add;
+  int rows;
+  const float* head_row;
+};
+constexpr int kMLP3RowWord = 11;  // counters word: stats rows written under MLP3Acc::rows
+// Returns 0, or a negative code before any launch: -8 misplaced clip arguments, -10 MLP3Acc
+// flags on a kind other than TailGrad / TailAcc (or rows without a row source), -11 TailAcc
+// with clip arguments.
+int launch_mlp3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip* clip = nullptr,
+                const MLP3Acc* acc = nullptr);
 
 int mlp3_act_rows(int L1, int L2);
 int mlp3_h1_copies(int L1);  // H1pre copies per ring slot (mlp_step3.hip H1Copies)

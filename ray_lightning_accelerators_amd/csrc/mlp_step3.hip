@@ -35,6 +35,19 @@
 // H1pre for the pending batch from the current weights (after init / load /
 // broadcast).
 //
+// Gradient accumulation (MLP3Acc, kernels.h): a window of K micro-batches ends in one
+// optimizer step.  A micro-batch inside its window runs head(advance_step = 0) -> ACC: the
+// GRAD tail's gradients, added into `grads` (one fp32 add per element; the window's first
+// micro-batch overwrites, so nothing zero-fills), no Adam, and what the ADAM tail does
+// besides Adam -- the next batch's layer-1 partial from the unchanged bf16 shadow, the
+// zero-fill of the consumed H1pre slot, the counter publish.  The micro-batch that closes
+// the window runs head -> GRAD (adding) -> [allreduce] -> [norm partials] -> ADAM with
+// grad_scale 1 / (world K).  Accumulation never runs as one launch.
+// Stats rows under accumulation are written by the TAIL (GRAD or ACC; last small block, where
+// tail_head_stats already runs for B > 32), one row per micro-batch at
+// counters[kMLP3RowWord] % ring, which that lane advances: the head kernels are untouched --
+// a one-block head is simply given a one-row `stats` and the tail files that row.
+//
 // Device state (graph-replay safe): counters[0] optimizer step, [1] cursor of
 // the NEXT batch, [2] cursor the last head consumed, [3] ring slot the next head
 // reads, [4] which of the two `order` epoch buffers counters[1] indexes.
@@ -65,7 +78,7 @@ constexpr int kBMax = 256;
 constexpr int kCnt = 5;  // counters: [0, 5) current state, [5, 10) the head's advanced copy
 constexpr int kHeadRows = 32;  // batch rows per head workgroup
 
-enum TailMode { kFused = 0, kGrad = 1, kAdam = 2, kPrime = 3, kFusedDP = 4 };
+enum TailMode { kFused = 0, kGrad = 1, kAdam = 2, kPrime = 3, kFusedDP = 4, kAcc = 5 };
 
 // rows of the `act` hand-off buffer ([rows][Bp] bf16)
 template <int L1, int L2>
@@ -994,8 +1007,10 @@ __device__ __forceinline__ void small_compute(const MLP3Args& a, bool prefetch_a
   }
 }
 
+// ``add`` (gradient branch only): grads += the value, one fp32 add (accumulation).
 template <int L1, int L2>
-__device__ __forceinline__ void small_finalize(const MLP3Args& a, bool adam, const SmallRes& r, const AdamScal& o) {
+__device__ __forceinline__ void small_finalize(const MLP3Args& a, bool adam, const SmallRes& r, const AdamScal& o,
+                                               bool add = false) {
   using O = Off<L1, L2>;
   if (r.kind < 0) return;
   __bf16* SHW = reinterpret_cast<__bf16*>(a.shadow);
@@ -1013,7 +1028,7 @@ __device__ __forceinline__ void small_finalize(const MLP3Args& a, bool adam, con
       SHW[r.gi[i]] = (__bf16)p_;
       sh4[i] = (__bf16)p_;
     } else {
-      a.grads[r.gi[i]] = r.v[i];
+      a.grads[r.gi[i]] = add ? a.grads[r.gi[i]] + r.v[i] : r.v[i];
     }
   }
   if (adam && r.kind == 0) *reinterpret_cast<bf16x4*>(SHW + O::W2T + (int64_t)r.colv * L2 + r.rowv) = sh4;
@@ -1538,6 +1553,40 @@ __device__ __forceinline__ void tail_head_stats(const MLP3Args& a, const int64_t
   st[3] = (float)t;
 }
 
+// Accumulating tails (MLP3Acc): the micro-batch's stats row.  Its values come from the
+// head -- `head_part` for a multi-block head, else the one row the one-block head wrote to
+// `acc.head_row` -- and go to row counters[kMLP3RowWord] % ring (`rows`: one row per
+// micro-batch, the word advanced here, by the only lane that touches it) or, without
+// `rows`, to the optimizer step's row as tail_head_stats.  `step`: the optimizer step the
+// micro-batch contributes to.  Same place in the launch as tail_head_stats.
+__device__ __forceinline__ void tail_acc_stats(const MLP3Args& a, const MLP3Acc& acc, int64_t step) {
+  float l = 0.f, k = 0.f, n = 0.f;
+  if (a.B > kHeadRows) {
+    for (int cb = 0; cb < (a.B + kHeadRows - 1) / kHeadRows; ++cb) {
+      l += a.head_part[cb * 4 + 0];
+      k += a.head_part[cb * 4 + 1];
+      n += a.head_part[cb * 4 + 2];
+    }
+    l = l / (float)a.B;
+  } else {
+    l = acc.head_row[0];
+    k = acc.head_row[1];
+    n = acc.head_row[2];
+  }
+  const int64_t ring = a.stats_ring > 0 ? a.stats_ring : 1;
+  int64_t row = (step - 1) % ring;
+  if (acc.rows) {
+    const int64_t seen = a.counters[kMLP3RowWord];
+    row = seen % ring;
+    a.counters[kMLP3RowWord] = seen + 1;
+  }
+  float* st = a.stats + row * 4;
+  st[0] = l;
+  st[1] = k;
+  st[2] = n;
+  st[3] = (float)step;
+}
+
 // ADAM mode with clipping: the clip coefficient from the norm partials (kernels.h
 // MLP3Clip), by the lane that computes Adam's scalars.  Every block sums the same
 // partials in the same (index) order, so every block holds the same bits; block 0 alone
@@ -1556,8 +1605,25 @@ __device__ __forceinline__ float tail_clip_coef(const MLP3Args& a, const MLP3Cli
   return coef;
 }
 
-template <int L1, int L2>
-__global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, int mode, MLP3Clip clip) {
+// ACC = false: the tail as every kind but the accumulating ones launches it (mode at run
+// time, `ga` unused).  ACC = true: the accumulating tails, MODE (kGrad or kAcc) a
+// compile-time constant so neither instance carries the Adam / exchange code:
+//   kGrad  the gradients, added into `grads` when ga.add;
+//   kAcc   the tail of a micro-batch that does not close its window: those gradients, no
+//          Adam (params / exp_avg / exp_avg_sq / shadow are not written), then what the ADAM
+//          tail does besides Adam -- the next batch's layer-1 partial into H1pre slot cn[3]
+//          (W1 tile from the bf16 shadow, as PRIME reads it), the zero-fill of the consumed
+//          slot by the small blocks, the counter publish.
+// Both write the micro-batch's stats row when ga.rows (tail_acc_stats).
+// One kernel text for both: `ga` is the LAST kernel argument, so the ACC = false instances
+// keep the argument offsets (and the instruction stream) they had without it.
+template <int L1, int L2, bool ACC = false, int MODE = -1>
+__global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, int mode_rt, MLP3Clip clip,
+                                                                   MLP3Acc ga) {
+  static_assert(ACC ? (MODE == kGrad || MODE == kAcc) : MODE < 0, "accumulating tails fix their mode");
+  const int mode = ACC ? MODE : mode_rt;
+  const bool acc_tail = ACC && mode == kAcc;   // compile-time in either instance
+  const bool add = ACC && ga.add != 0;
   constexpr int TN1 = L1 / 16;
   constexpr int NT = 64 * TN1;
   __shared__ __attribute__((aligned(16))) __bf16 sX[kBMax * kXSS];
@@ -1569,7 +1635,7 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
                              // clip argument's registers are free before the tile loop)
   const int tid = threadIdx.x, lane = tid & 63, ct = tid >> 6, r16 = lane & 15, g = lane >> 4;
   const bool dp = mode == kFusedDP;
-  const bool do_grad = mode == kFused || mode == kGrad || dp;
+  const bool do_grad = mode == kFused || mode == kGrad || dp || acc_tail;
   const bool do_adam = mode == kFused || mode == kAdam || dp;
   const bool do_fwd = mode != kGrad;
   if (a.stamps && blockIdx.x == 0 && tid == 0) a.stamps[8] = __builtin_amdgcn_s_memrealtime();
@@ -1594,7 +1660,7 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
   };
   if ((int)blockIdx.x >= kTiles) {  // small parameters (block-uniform branch)
     const int sblk = (int)blockIdx.x - kTiles;
-    if (mode == kFused || mode == kFusedDP || mode == kAdam) {
+    if (mode == kFused || mode == kFusedDP || mode == kAdam || acc_tail) {
       // the H1pre slot the head consumed (cn[3] ^ 1) is zero for the step after
       // this one to accumulate into (the one-launch step relies on it)
       const int Bp = (a.B + 31) / 32 * 32;
@@ -1612,7 +1678,7 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
       return;
     }
     SmallRes r;
-    small_compute<L1, L2>(a, mode != kGrad, sblk * TN1 + ct, r);
+    small_compute<L1, L2>(a, mode != kGrad && !acc_tail, sblk * TN1 + ct, r);
     scalars();
     __syncthreads();
     if (mode == kFusedDP) {
@@ -1640,8 +1706,14 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
           if (r.valid[i]) r.v[i] = dp_sum1(a, dslot, r.gi[i]) * scale;
       }
     }
-    small_finalize<L1, L2>(a, mode != kGrad, r, sh_o);
-    if (blockIdx.x == gridDim.x - 1 && tid == 0 && a.stats && a.B > kHeadRows) tail_head_stats(a, cn);
+    small_finalize<L1, L2>(a, mode != kGrad && !acc_tail, r, sh_o, add);
+    if constexpr (ACC) {
+      // cn[0]: already advanced when this micro-batch closes its window (kGrad), else the step to come
+      if (blockIdx.x == gridDim.x - 1 && tid == 0 && a.stats && (a.B > kHeadRows || ga.rows))
+        tail_acc_stats(a, ga, acc_tail ? cn[0] + 1 : cn[0]);
+    } else {
+      if (blockIdx.x == gridDim.x - 1 && tid == 0 && a.stats && a.B > kHeadRows) tail_head_stats(a, cn);
+    }
     stamp_max(a, 11);
     return;
   }
@@ -1658,9 +1730,9 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
     m4 = *reinterpret_cast<const F4*>(a.exp_avg + gidx);
     v4 = *reinterpret_cast<const F4*>(a.exp_avg_sq + gidx);
   }
-  if (mode == kAdam) g4 = *reinterpret_cast<const F4*>(a.grads + gidx);
+  if (mode == kAdam || add) g4 = *reinterpret_cast<const F4*>(a.grads + gidx);  // add: the running sum
   bf16x4 w4;
-  if (mode == kPrime) w4 = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const __bf16*>(a.shadow) + gidx);
+  if (mode == kPrime || acc_tail) w4 = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const __bf16*>(a.shadow) + gidx);
 
   const int64_t slot = cn[3];
   const int64_t tile_elems = (int64_t)Bp * 16;
@@ -1718,10 +1790,14 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
       acc = mfma16(afrag, ld8(dh + b0), acc);
     }
   }
-  if (mode == kGrad) {
+  if (mode == kGrad || acc_tail) {
     F4 gg{{acc[0], acc[1], acc[2], acc[3]}};
+    if (add) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) gg.v[i] = g4.v[i] + acc[i];
+    }
     *reinterpret_cast<F4*>(a.grads + gidx) = gg;
-    return;
+    if (mode == kGrad) return;
   }
   if (dp) {  // allreduce of this tile inside the epilogue (xGMI push / flag / fixed-order sum)
     __shared__ uint32_t sh_dgen;
@@ -1809,8 +1885,8 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
 // slot) -- first waits for launch `seq`'s (seq + 1) * gridDim.x acks.  The W1
 // tiles write nothing another block reads (the head reads H1pre, not W1) and
 // never wait.  Invariant kept by every step kind: the H1pre slot the tiles add
-// into (slot ^ 1) is zero when a step starts (block 0 / the two-launch tail
-// zero the consumed slot; prime zeroes both).
+// into (slot ^ 1) is zero when a step starts (block 0 / the two-launch tail / the
+// ADAM and ACC tails zero the consumed slot; prime zeroes both).
 //
 // Adam's scalars: every block but block 0 needs them for its tail role.  Their two
 // f64 pow() (~500 dependent instructions on one lane) used to run on thread 0 of each
@@ -2244,7 +2320,7 @@ template <int L1, int L2>
 constexpr bool kProbeDP = L1 == 32 && L2 == 64;
 
 template <int L1, int L2>
-int dispatch3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip& clip) {
+int dispatch3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip& clip, const MLP3Acc& acc) {
   constexpr int kOneGrid = 1 + kTiles + One<L1, L2>::NSMALL;
   if (kind == kMLP3Step1) {
     if (a.B > 32 || !a.hand || kOneGrid > 256) return -5;
@@ -2300,6 +2376,15 @@ int dispatch3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip& c
     else
       hipLaunchKernelGGL((mlp3_head_kernel<kHeadRows, L1, L2, false>), dim3(1 + kTiles), dim3(kThreads), 0, stream, a);
   }
+  if (kind == kMLP3TailAcc || (kind == kMLP3TailGrad && (acc.add || acc.rows))) {
+    // accumulating tails: the 49 tile blocks plus the small blocks, as GRAD
+    const dim3 g(kTiles + SmallTasks<L1, L2>::NBLK), b(NT);
+    if (kind == kMLP3TailAcc)
+      hipLaunchKernelGGL((mlp3_tail_kernel<L1, L2, true, kAcc>), g, b, 0, stream, a, (int)kAcc, clip, acc);
+    else
+      hipLaunchKernelGGL((mlp3_tail_kernel<L1, L2, true, kGrad>), g, b, 0, stream, a, (int)kGrad, clip, acc);
+    return 0;
+  }
   int mode = -1, grid = kTiles;
   if (kind == kMLP3Step) { mode = kFused; grid += SmallTasks<L1, L2>::NBLK; }
   else if (kind == kMLP3StepDP) { mode = kFusedDP; grid += SmallTasks<L1, L2>::NBLK; }
@@ -2311,7 +2396,7 @@ int dispatch3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip& c
     int extra = (int)((nsmall + NT - 1) / NT);
     grid += extra < 64 ? extra : 64;
   }
-  if (mode >= 0) hipLaunchKernelGGL((mlp3_tail_kernel<L1, L2>), dim3(grid), dim3(NT), 0, stream, a, mode, clip);
+  if (mode >= 0) hipLaunchKernelGGL((mlp3_tail_kernel<L1, L2>), dim3(grid), dim3(NT), 0, stream, a, mode, clip, acc);
   return 0;
 }
 
@@ -2345,15 +2430,24 @@ MLP3HandLayout mlp3_hand_layout() {
 }
 MLP3AdamCacheLayout mlp3_adam_cache_layout() { return {kHandAdamStep, kHandAdamBetas, kHandAdamBc1, kHandAdamBc2}; }
 
-int launch_mlp3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip* clip_in) {
+int launch_mlp3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip* clip_in, const MLP3Acc* acc_in) {
   if (a.B > kBMax || a.B < 1) return -2;
+  // TailAcc never clips: its window is still open
+  if (kind == kMLP3TailAcc && clip_in && (clip_in->part || clip_in->out)) return -11;
   // clipping belongs to the ADAM tail alone; every other kind launches without it
   MLP3Clip clip{nullptr, 0, 0.f, nullptr};
   if (clip_in && clip_in->part) {
     if (kind != kMLP3TailAdam || clip_in->nblk < 1 || clip_in->nblk > kClipMaxBlocks) return -8;
     clip = *clip_in;
   }
-#define RLA_CASE(a1, a2) if (a.L1 == a1 && a.L2 == a2) return dispatch3<a1, a2>(a, kind, stream, clip);
+  // accumulation belongs to the GRAD tail and to TailAcc
+  MLP3Acc acc{0, 0, nullptr};
+  if (acc_in && (acc_in->add || acc_in->rows || acc_in->head_row)) {
+    if (kind != kMLP3TailGrad && kind != kMLP3TailAcc) return -10;
+    if (acc_in->rows && (!a.stats || (a.B <= kHeadRows && !acc_in->head_row))) return -10;
+    acc = *acc_in;
+  }
+#define RLA_CASE(a1, a2) if (a.L1 == a1 && a.L2 == a2) return dispatch3<a1, a2>(a, kind, stream, clip, acc);
   RLA_CASE(32, 32) RLA_CASE(32, 64) RLA_CASE(32, 128) RLA_CASE(32, 256)
   RLA_CASE(64, 64) RLA_CASE(64, 128) RLA_CASE(64, 256)
   RLA_CASE(128, 64) RLA_CASE(128, 128) RLA_CASE(128, 256)

@@ -498,7 +498,10 @@ class Trainer:
             from .graph_step import maybe_graph_step
 
             return maybe_graph_step(self, model)
-        if self.accumulate_grad_batches != 1:
+        # accumulate_grad_batches: only a fused step that accumulates itself (it reads
+        # trainer.accumulate_grad_batches and counts the optimizer steps); a model
+        # declines by leaving ``fused_step_accumulates`` unset
+        if self.accumulate_grad_batches != 1 and not getattr(model, "fused_step_accumulates", False):
             return None
         # gradient_clip_val: only a fused step that clips itself (it reads
         # trainer.gradient_clip_val); a model declines by leaving
@@ -1034,6 +1037,8 @@ class Trainer:
         f = self._fused
         if f is None or not hasattr(f, "train_chunk"):
             return 1
+        if self.accumulate_grad_batches != 1:
+            return 1  # _run_chunked equates batches with global steps: windows go out per batch
         k = self.steps_per_dispatch if self.steps_per_dispatch is not None else get_config().steps_per_dispatch
         k = min(int(k), int(getattr(f, "max_chunk", 1)))
         if k <= 1 or self._batch_hooks_overridden(model, chunk_aware_ok=True):

@@ -16,7 +16,12 @@ exchanges the gradient tiles with the peers over xGMI inside its Adam epilogue
 (``RLAConfig.fused_dp``), else head / tail / allreduce / tail.
 ``Trainer(gradient_clip_val=c)`` stays on the HIP path: head / tail(grad) /
 [allreduce] / norm partials / tail(adam), the clip coefficient derived on the
-device (``FusedMLPEngine(clip_norm=c)``).  Batches the
+device (``FusedMLPEngine(clip_norm=c)``).
+``Trainer(accumulate_grad_batches=K)`` stays on it too (``FusedMLPEngine(accumulate=K)``):
+a batch inside its window is head / tail(acc) -- gradients added up on the device, no
+Adam -- and the batch that closes it head / tail(grad) / [allreduce] / [norm partials] /
+tail(adam) with every micro-batch weighted 1/K; the Trainer dispatches per batch and this
+step counts the optimizer steps (``counts_steps``).  Batches the
 resident path cannot serve (e.g. user transforms) use a one-launch fp32-input
 kernel; CPU / unsupported shapes use the ordinary autograd path.
 """
@@ -103,6 +108,8 @@ class LightningMNISTClassifier(LightningModule):
     # ------------------------------------------------------------ fast path
     # the fused step clips by global norm itself (Trainer(gradient_clip_val=...))
     fused_step_clips_gradients = True
+    # ... and accumulates gradients over Trainer(accumulate_grad_batches=K) batches itself
+    fused_step_accumulates = True
 
     def configure_fused_step(self, trainer):
         if type(self).training_step is not LightningMNISTClassifier.training_step or \
@@ -172,6 +179,10 @@ class FusedMNISTStep:
         if clip < 0.0:
             raise RuntimeError("fused step cannot clip to a negative norm")
         self.clip_norm = clip if clip > 0.0 else None
+        # accumulate_grad_batches: micro-batches per optimizer step; this object then counts
+        # trainer.global_step itself (one per window, as Trainer._autograd_step does)
+        self.accumulate = max(1, int(getattr(trainer, "accumulate_grad_batches", 1) or 1))
+        self.counts_steps = self.accumulate > 1
         self.counters = torch.zeros(2, dtype=torch.int64, device=dev)
         self.counters[0] = self.gs.step
         self.lr_val = float(opt.param_groups[0]["lr"])
@@ -199,8 +210,9 @@ class FusedMNISTStep:
                     exp_avg=self.gs.m[: self.np], exp_avg_sq=self.gs.v[: self.np])
         dp_ctx = None
         rearm = None
-        # clipping needs the whole averaged gradient before Adam: the allreduce route
-        if self.world > 1 and get_config().fused_dp and self.clip_norm is None:
+        # clipping needs the whole averaged gradient before Adam: the allreduce route;
+        # accumulation steps once per window, the in-kernel exchange at every batch
+        if self.world > 1 and get_config().fused_dp and self.clip_norm is None and self.accumulate == 1:
             from ..parallel.comm import get_native_comm
 
             comm = get_native_comm()  # every rank reaches here together (first epoch)
@@ -211,7 +223,7 @@ class FusedMNISTStep:
                              weight_decay=g["weight_decay"], device=self.dev, world_size=self.world,
                              rank=self.trainer.global_rank, allreduce=self._allreduce, buffers=bufs,
                              stats_ring=ENGINE_STATS_RING, dp_context=dp_ctx, dp_rearm=rearm,
-                             clip_norm=self.clip_norm)
+                             clip_norm=self.clip_norm, accumulate=self.accumulate)
         eng.set_step(self.gs.step)
         eng.lr_tensor = self.lr_tensor  # LR schedulers update one device scalar
         eng.attach_dataset(self._u8, self._labels)
@@ -292,7 +304,70 @@ class FusedMNISTStep:
     def on_lr_change(self) -> None:
         self._sync_lr()
 
+    def _train_micro_batch(self, batch, batch_idx: int):
+        """``train_batch`` under ``accumulate_grad_batches=K``: one micro-batch.  Batch i of
+        the epoch closes its window when (i + 1) % K == 0 or it is the epoch's last; only
+        then do Adam, ``trainer.global_step``, the optimizer's step counts and the
+        step-interval LR schedulers move.  Returns the batch's own stats row."""
+        self._sync_lr()
+        K = self.accumulate
+        g = self.opt.param_groups[0]
+        b1, b2 = g["betas"]
+        if isinstance(batch, tuple) and len(batch) == 2 and batch[0] == "__rla_resident__":
+            eng = self.eng
+            eng.lr, eng.betas, eng.eps, eng.wd = self.lr_val, (b1, b2), g["eps"], g["weight_decay"]
+            before = eng.optimizer_steps
+            eng.step()  # one micro-batch (no graph is captured on this per-batch path)
+            closing = eng.optimizer_steps != before
+            row = eng.stats[(eng.global_step - 1) % eng.stats.size(0)]  # one ring row per micro-batch
+        else:
+            from ..ops.optim import clip_partials, fused_adam_
+
+            p, gr = self.arena.data[: self.np], self.arena.grad[: self.np]
+            m, v = self.gs.m[: self.np], self.gs.v[: self.np]
+            n = int(getattr(self.trainer, "num_training_batches", 0) or 0)
+            micro = batch_idx % K
+            closing = (batch_idx + 1) % K == 0 or (n > 0 and batch_idx + 1 >= n)
+            self.counters[0] = self.gs.step
+            x, y = batch
+            x = x.to(self.dev, non_blocking=True).reshape(x.size(0), -1).float().contiguous()
+            y = y.to(self.dev, non_blocking=True).long().contiguous()
+            stats = torch.zeros(1, 4, device=self.dev)  # this batch's own row
+            fused_mlp.mlp_train_step(p, gr, B=x.size(0), labels=y, x_f32=x, L1=self.L1, L2=self.L2, exp_avg=m,
+                                     exp_avg_sq=v, stats=stats, accumulate_grad=micro > 0, apply_adam=False,
+                                     advance_step=closing, lr=self.lr_val, betas=(b1, b2), eps=g["eps"],
+                                     weight_decay=g["weight_decay"], lr_tensor=self.lr_tensor,
+                                     counters=self.counters)
+            if closing:
+                scale = 1.0 / (self.world * K)
+                if self._allreduce is not None and self.acc.sync is not None:
+                    self._allreduce(gr)
+                if self.clip_norm is not None:
+                    norm = clip_partials(gr, 32).sum().sqrt() * scale
+                    gr.mul_(torch.clamp(self.clip_norm / (norm + 1e-6), max=1.0))
+                fused_adam_(p, gr, m, v, lr=self.lr_val, betas=(b1, b2), eps=g["eps"],
+                            weight_decay=g["weight_decay"], grad_scale=scale, step=self.counters[0:1],
+                            lr_tensor=self.lr_tensor)
+                if self.eng is not None:
+                    self.eng.refresh_shadow()  # params moved outside the engine
+            row = stats[0]
+        if closing:
+            self.gs.step += 1
+            for q in g["params"]:
+                st = self.opt.state.get(q)
+                if st is not None and "step" in st:
+                    st["step"].fill_(float(self.gs.step))
+            self.trainer.global_step += 1
+            self.trainer._update_lr_schedulers("step")
+        loss = row[0]
+        self.model.log("ptl/train_loss", loss)
+        self.model.log("ptl/train_accuracy", row[1] / row[2].clamp(min=1))
+        self.trainer.callback_metrics["loss"] = loss
+        return {"loss": loss}
+
     def train_batch(self, batch, batch_idx: int):
+        if self.accumulate > 1:
+            return self._train_micro_batch(batch, batch_idx)
         self._sync_lr()
         g = self.opt.param_groups[0]
         b1, b2 = g["betas"]

@@ -168,6 +168,10 @@ def mlp_refresh_shadow(params: torch.Tensor, shadow: torch.Tensor, L1: int, L2: 
 
 
 MLP3_STEP, MLP3_HEAD, MLP3_TAIL_GRAD, MLP3_TAIL_ADAM, MLP3_PRIME, MLP3_STEP_DP, MLP3_STEP1, MLP3_STEP1_DP = range(8)
+# the tail of a micro-batch that does not close its gradient-accumulation window
+MLP3_TAIL_ACC = 8
+# counters word that counts the stats rows written under ``acc_rows`` (kernels.h kMLP3RowWord)
+MLP3_ROW_WORD = 11
 ONE_LAUNCH_MAX_B = 32  # MLP3_STEP1 / MLP3_STEP1_DP: one head workgroup
 # exchange protocols of MLP3_STEP1_DP (csrc/mlp_step3.hip, "Wave-positioned exchange protocols")
 DP_GRANULE, DP_PACKED, DP_OWNER = 0, 1, 2
@@ -266,7 +270,8 @@ def mlp3_buffers(L1: int, L2: int, B: int, device) -> Dict[str, torch.Tensor]:
         "act": torch.zeros((L1 + 2 * L2 + 16) * bp, dtype=torch.bfloat16, device=device),
         "yring": torch.full((2 * bp,), -1, dtype=torch.int32, device=device),
         # [0, 5) current state, [5, 10) the head's advanced copy (published by the tail),
-        # [10] the one-launch step's launch sequence number (its hand-off tag)
+        # [10] the one-launch step's launch sequence number (its hand-off tag),
+        # [11] stats rows written by accumulating tails (one per micro-batch)
         "counters": torch.zeros(16, dtype=torch.int64, device=device),
         # one-launch step: [0] per-block state acknowledgements (monotonic), [16] wait-timeout flag;
         # every step kind: [17] saturated / [18] non-finite layer-1 partials, [19] last such step
@@ -317,6 +322,9 @@ def mlp3_launch(
     clip_max_norm: float = 0.0,
     clip_out: Optional[torch.Tensor] = None,
     clip_nblk: Optional[int] = None,
+    acc_add: bool = False,
+    acc_rows: bool = False,
+    acc_head_row: Optional[torch.Tensor] = None,
 ) -> None:
     """One v3 launch (GPU only; ``repeat``: that many identical launches back to back
     from one C++ loop -- every step's state lives on the device).  ``kind``: MLP3_STEP (head + fused tail, world size 1),
@@ -343,7 +351,25 @@ def mlp3_launch(
     min(1, clip_max_norm / (norm + 1e-6))`` (``torch.nn.utils.clip_grad_norm_``), and its
     Adam reads ``grads * grad_scale * coef``.  ``clip_nblk``: partials to read (default:
     all of ``clip_part``).  ``clip_out`` (optional, 4 fp32): [0] norm, [1] coef,
-    [2] += 1 when coef < 1, [3] += 1 when the norm is NaN / Inf."""
+    [2] += 1 when coef < 1, [3] += 1 when the norm is NaN / Inf.
+
+    Gradient accumulation (MLP3_TAIL_GRAD / MLP3_TAIL_ACC only; any other kind raises
+    before a launch): MLP3_TAIL_ACC is the tail of a micro-batch that does not close its
+    window -- gradients, no Adam, the next batch's layer-1 partial from the unchanged
+    weights; it takes no clip arguments.  ``acc_add``: ``grads`` += this micro-batch's
+    gradient (one fp32 add per element) instead of the overwrite.  ``acc_rows``: the tail
+    writes the micro-batch's stats row at ``counters[MLP3_ROW_WORD] % ring`` and advances
+    that word; ``acc_head_row`` ([4] fp32, B <= 32) is where the head launch, given it as
+    a one-row ``stats``, left the row."""
+    if acc_add or acc_rows or acc_head_row is not None:
+        if kind not in (MLP3_TAIL_GRAD, MLP3_TAIL_ACC):
+            raise ValueError(f"mlp3_launch: accumulation arguments belong to MLP3_TAIL_GRAD / MLP3_TAIL_ACC, "
+                             f"not kind {kind}")
+        if acc_rows and (stats is None or (int(B) <= ONE_LAUNCH_MAX_B and acc_head_row is None)):
+            raise ValueError(f"mlp3_launch: acc_rows needs stats (and acc_head_row for B <= 32), kind {kind}")
+    if kind == MLP3_TAIL_ACC and (clip_part is not None or clip_out is not None or clip_max_norm
+                                  or clip_nblk is not None):
+        raise ValueError(f"mlp3_launch: MLP3_TAIL_ACC (kind {kind}) takes no clip arguments: its window is open")
     if clip_part is not None or clip_out is not None or clip_max_norm or clip_nblk is not None:
         if kind != MLP3_TAIL_ADAM:
             raise ValueError(f"mlp3_launch: clip arguments belong to MLP3_TAIL_ADAM, not kind {kind}")
@@ -355,6 +381,7 @@ def mlp3_launch(
         float(betas[1]), float(eps), float(weight_decay), float(grad_scale), lr_tensor, bool(adamw), stamps,
         [int(v) for v in (dp_ctx or ())], head_part, hand, int(dp_proto), bool(dp_loop), int(repeat),
         clip_part, float(clip_max_norm), clip_out, -1 if clip_nblk is None else int(clip_nblk),
+        bool(acc_add), bool(acc_rows), acc_head_row,
     )
 
 

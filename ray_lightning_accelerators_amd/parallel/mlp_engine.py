@@ -24,6 +24,13 @@ re-designed for MI355X instead of translating PL's DDP loop:
   at every batch and world size head -> tail(grad) -> [allreduce] -> norm partials
   (``ops.optim.clip_partials``, fixed summation order) -> tail(adam), which derives
   the coefficient on the device -- no host sync, bitwise-reproducible, graph-capturable;
+* ``accumulate=K`` (gradient accumulation, ``Trainer(accumulate_grad_batches=K)``): a
+  window of K micro-batches ends in one optimizer step.  A micro-batch inside its window is
+  TWO launches, head -> tail(acc) (gradients added into ``grads``, no Adam, the next
+  batch's layer 1 from the unchanged weights); the one that closes it is head ->
+  tail(grad, adding) -> [allreduce] -> [norm partials] -> tail(adam, grad_scale 1/(world K)).
+  The window position is a function of ``step_in_epoch``, ``n_batches`` and K alone (no
+  device read); the epoch's last window may be short and is still weighted 1/K;
 * the step's device work can be captured into a hipGraph (``capture``): batch
   cursor, step counter, ring slot and epoch buffer live on the device, so
   replays advance by themselves.
@@ -109,6 +116,7 @@ class FusedMLPEngine:
         dp_rearm: Optional[Callable[[], None]] = None,
         dp_loop: bool = False,
         clip_norm: Optional[float] = None,
+        accumulate: int = 1,
     ):
         """``buffers``: optional external fp32 tensors ``params`` / ``grads`` /
         ``exp_avg`` / ``exp_avg_sq`` (e.g. views of a Trainer's parameter arena,
@@ -127,7 +135,19 @@ class FusedMLPEngine:
         Adam, as ``torch.nn.utils.clip_grad_norm_`` does; None / 0: no clipping.  The step
         then always runs head -> tail(grad) -> [allreduce] -> norm partials -> tail(adam);
         it does not combine with ``dp_context`` (the in-kernel exchange never holds the
-        whole averaged gradient before its Adam)."""
+        whole averaged gradient before its Adam).
+        ``accumulate``: micro-batches per optimizer step (K >= 1; 1: the engine without the
+        argument).  Micro-batch i of an epoch closes its window when (i + 1) % K == 0 or it
+        is the epoch's last; every micro-batch's gradient weighs 1 / K, clipping applies to
+        the averaged sum, the allreduce runs once per window, ``counters[0]`` advances once
+        per window while cursor / ring slot / stats rows advance per micro-batch.  Like
+        ``clip_norm`` it never runs as one launch and does not combine with ``dp_context``."""
+        if isinstance(accumulate, bool) or int(accumulate) != accumulate or int(accumulate) < 1:
+            raise ValueError(f"accumulate must be an integer >= 1, got {accumulate!r}")
+        accumulate = int(accumulate)
+        if accumulate > 1 and dp_context is not None:
+            raise ValueError("accumulate > 1 needs the allreduce route: the in-kernel data-parallel exchange "
+                             "(dp_context) steps at every batch -- pass allreduce= and no dp_context")
         clip_norm = float(clip_norm) if clip_norm else None
         if clip_norm is not None and not clip_norm > 0.0:
             raise ValueError(f"clip_norm must be positive, got {clip_norm}")
@@ -170,6 +190,11 @@ class FusedMLPEngine:
             self.exp_avg_sq = torch.zeros(n, device=self.device)
         self.lr_tensor = torch.full((1,), self.lr, device=self.device)
         self.clip_norm = clip_norm
+        self.accumulate = accumulate
+        # the one-block head's stats row of the current micro-batch (accumulation: the tail
+        # moves it to the row counters[MLP3_ROW_WORD] names, one ring row per micro-batch)
+        self._head_row = torch.zeros(1, 4, device=self.device)
+        self.optimizer_steps = 0  # host count of optimizer steps == counters[0]
         self.clip_part = self.clip_out = None
         if clip_norm is not None:
             self.clip_part = torch.zeros(CLIP_NBLK, device=self.device)
@@ -199,9 +224,10 @@ class FusedMLPEngine:
         # intermittent fidelity failures in long GPU sessions; round 6's post-mortem
         # showed the step bitwise equal to the two-launch step from a fresh engine in
         # the failing session (docs/one_launch_investigation.md), so the gate is gone.
-        # clipping needs the whole gradient between two launches: never one launch
+        # clipping needs the whole gradient between two launches: never one launch;
+        # nor does accumulation (Adam only at a window's close)
         self.one_launch = (self.B <= fused_mlp.ONE_LAUNCH_MAX_B and os.environ.get("RLA_MLP_ONE_LAUNCH") != "0"
-                           and clip_norm is None)
+                           and clip_norm is None and accumulate == 1)
         # world size > 1 with the xGMI context: the same one launch, each block
         # exchanging its values with the peers (protocol: self.dp_proto)
         self.dp_proto = "packed"
@@ -387,6 +413,7 @@ class FusedMLPEngine:
 
     def set_step(self, step: int) -> None:
         self.counters[0] = int(step)
+        self.optimizer_steps = int(step)
         self._publish_counters()
 
     @property
@@ -514,12 +541,48 @@ class FusedMLPEngine:
             fused_mlp.mlp3_launch(fused_mlp.MLP3_PRIME, **self._kw3())
         self._primed = True
 
-    def _device_step(self) -> None:
-        """One optimizer step on the device (or the fp32 reference step on the CPU)."""
+    def _window(self, pos: int, in_graph: bool = False):
+        """(index inside its accumulation window, whether it closes the window) of the
+        micro-batch at epoch position ``pos``.  ``in_graph``: ``pos`` counts from a
+        window-aligned start before the epoch's short last window (what a graph holds)."""
+        k = self.accumulate
+        closing = (pos + 1) % k == 0 or (not in_graph and pos + 1 >= self.n_batches)
+        return pos % k, closing
+
+    @property
+    def _grad_scale(self) -> float:
+        return 1.0 / (self.world_size * self.accumulate)
+
+    def _device_step(self, graph_pos: Optional[int] = None) -> None:
+        """One batch on the device (or the fp32 reference step on the CPU): an optimizer
+        step, or with ``accumulate`` > 1 one micro-batch (``graph_pos``: its position in
+        the graph being captured, else ``step_in_epoch`` places it)."""
         if self.x_u8 is None:
             raise RuntimeError("set_data() first")
         if not self._primed:
             self.prime()
+        if self.accumulate > 1:
+            micro, closing = (self._window(self.step_in_epoch) if graph_pos is None
+                              else self._window(graph_pos, in_graph=True))
+            if not self.native:
+                self._reference_step(micro, closing)
+                return
+            kw = self._kw3()
+            acc = dict(acc_add=micro > 0, acc_rows=True, acc_head_row=self._head_row)
+            # a one-block head writes its row to _head_row (a one-row ring); the tail files it
+            fused_mlp.mlp3_launch(fused_mlp.MLP3_HEAD, stats=self._head_row, advance_step=closing, **kw)
+            if not closing:
+                fused_mlp.mlp3_launch(fused_mlp.MLP3_TAIL_ACC, stats=self.stats, **acc, **kw)
+                return
+            fused_mlp.mlp3_launch(fused_mlp.MLP3_TAIL_GRAD, stats=self.stats, **acc, **kw)
+            if self.allreduce is not None:
+                self.allreduce(self.comm_buffer)
+            clip = {}
+            if self.clip_norm is not None:
+                clip_partials(self.grads, CLIP_NBLK, out=self.clip_part)
+                clip = dict(clip_part=self.clip_part, clip_max_norm=self.clip_norm, clip_out=self.clip_out)
+            fused_mlp.mlp3_launch(fused_mlp.MLP3_TAIL_ADAM, grad_scale=self._grad_scale, **clip, **kw)
+            return
         if not self.native:
             self._reference_step()
         else:
@@ -549,29 +612,38 @@ class FusedMLPEngine:
                     self.allreduce(self.comm_buffer)
                 fused_mlp.mlp3_launch(fused_mlp.MLP3_TAIL_ADAM, grad_scale=1.0 / self.world_size, **kw)
 
-    def _reference_step(self) -> None:
-        """fp32 PyTorch step with the device kernels' batch / counter semantics."""
+    def _reference_step(self, micro: int = 0, closing: bool = True) -> None:
+        """fp32 PyTorch step with the device kernels' batch / counter semantics
+        (``accumulate`` > 1: micro-batch ``micro`` of its window, Adam when ``closing``)."""
         c = self.counters
         cursor, ob = int(c[1]), int(c[4])
-        fused = self.world_size == 1 and self.clip_norm is None
+        acc = self.accumulate > 1
+        fused = self.world_size == 1 and self.clip_norm is None and not acc
         fused_mlp.mlp_train_step(
             self.params, self.grads, L1=self.L1, L2=self.L2, B=self.B, labels=self.labels, x_u8=self.x_u8,
             order=self.order[ob], counters=c[:2], n_batches=self.n_batches, exp_avg=self.exp_avg,
-            exp_avg_sq=self.exp_avg_sq, stats=self.stats, apply_adam=fused, advance_step=True, lr=self.lr,
+            exp_avg_sq=self.exp_avg_sq, stats=self._head_row if acc else self.stats, accumulate_grad=micro > 0,
+            apply_adam=fused, advance_step=closing, lr=self.lr,
             betas=self.betas, eps=self.eps, weight_decay=self.wd, lr_tensor=self.lr_tensor,
         )
         c[2] = cursor
         c[3] = int(c[3]) ^ 1
         if cursor + 1 >= self.n_batches:
             c[4] = ob ^ 1
+        if acc:  # one stats row per micro-batch, as the accumulating tails file it
+            w = fused_mlp.MLP3_ROW_WORD
+            self.stats[int(c[w]) % self.stats.size(0)] = self._head_row[0]
+            c[w] += 1
         self._publish_counters()
+        if not closing:
+            return
         if not fused:
             if self.allreduce is not None:
                 self.allreduce(self.comm_buffer)
             if self.clip_norm is not None:
                 self._reference_clip()
             fused_adam_(self.params, self.grads, self.exp_avg, self.exp_avg_sq, lr=self.lr, betas=self.betas,
-                        eps=self.eps, weight_decay=self.wd, grad_scale=1.0 / self.world_size,
+                        eps=self.eps, weight_decay=self.wd, grad_scale=self._grad_scale,
                         step=self.counters[0:1], lr_tensor=self.lr_tensor)
 
     def _reference_clip(self) -> None:
@@ -581,7 +653,7 @@ class FusedMLPEngine:
         ss = torch.zeros((), dtype=torch.float32)
         for i in range(CLIP_NBLK):  # index order, as the kernel's scalar lane
             ss = ss + part[i]
-        norm = ss.sqrt() * torch.tensor(1.0 / self.world_size, dtype=torch.float32)
+        norm = ss.sqrt() * torch.tensor(self._grad_scale, dtype=torch.float32)
         coef = torch.clamp(torch.tensor(self.clip_norm, dtype=torch.float32) / (norm + 1e-6), max=1.0)
         if bool(torch.isnan(coef)):
             coef = torch.ones(())  # fminf(1, NaN) = 1: the kernel passes a NaN norm through
@@ -593,6 +665,10 @@ class FusedMLPEngine:
         self.clip_out[0], self.clip_out[1] = norm, coef
 
     def _advance_host(self, n: int) -> None:
+        if self.accumulate == 1:
+            self.optimizer_steps += n
+        else:  # the windows that close among the n batches from step_in_epoch on
+            self.optimizer_steps += sum(self._window(self.step_in_epoch + i)[1] for i in range(n))
         self.global_step += n
         self.step_in_epoch += n
         if self.step_in_epoch >= self.n_batches:
@@ -619,21 +695,30 @@ class FusedMLPEngine:
         chunks end at log / validation / epoch boundaries) runs as a few replays
         instead of eager launches (~40 us of host work per eager step against
         ~9 us of GPU time, so eager remainders starved the GPU)."""
+        K = self.accumulate
+        if K > 1 and (steps_per_graph < K or steps_per_graph % K != 0):
+            # a graph holds whole windows: each captured launch has its place in the window baked in
+            raise ValueError(f"capture({steps_per_graph}): with accumulate={K} a graph must hold whole windows "
+                             f"(a multiple of {K} batches)")
         if not self.native:
             return False
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
-        # warm the allocator / RCCL outside capture (a real step; keeps counters consistent)
-        with torch.cuda.stream(s):
-            self._device_step()
-        torch.cuda.current_stream().wait_stream(s)
-        self._advance_host(1)
+        # warm the allocator / RCCL outside capture (a real step; keeps counters consistent);
+        # accumulation: K real batches, so both kinds of micro-batch have run
+        for _ in range(K):
+            with torch.cuda.stream(s):
+                self._device_step()
+            torch.cuda.current_stream().wait_stream(s)
+            self._advance_host(1)
+            if K > 1:  # the next warm-up batch follows what _advance_host enqueued
+                s.wait_stream(torch.cuda.current_stream())
 
         def record(n: int):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, stream=s):
-                for _ in range(n):
-                    self._device_step()
+                for i in range(n):
+                    self._device_step(i if K > 1 else None)
             return g
 
         try:
@@ -645,7 +730,7 @@ class FusedMLPEngine:
         self._graph_steps = steps_per_graph
         self._tail_graphs = {}
         if remainders:
-            k = 1
+            k = K  # 1 without accumulation; else whole windows only
             while k < steps_per_graph:
                 try:
                     self._tail_graphs[k] = record(k)  # capture only: the device state does not move
@@ -656,6 +741,11 @@ class FusedMLPEngine:
 
     def _graph_ok(self, remaining: int, k: Optional[int] = None) -> bool:
         k = self._graph_steps if k is None else k
+        if self.accumulate > 1:
+            # only from a window-aligned position, and only before the epoch's short last window
+            full = self.n_batches // self.accumulate * self.accumulate
+            if self.step_in_epoch % self.accumulate != 0 or self.step_in_epoch + k > full:
+                return False
         return (self._graph is not None and self._primed and remaining >= k
                 and self.step_in_epoch + k <= self.n_batches)
 
@@ -669,7 +759,8 @@ class FusedMLPEngine:
         return None, 1
 
     def step(self) -> None:
-        """Run one (or ``steps_per_graph`` when captured) optimizer step(s)."""
+        """Run one (or ``steps_per_graph`` when captured) batch(es): optimizer steps, or
+        micro-batches with ``accumulate`` > 1."""
         if self._graph_ok(self._graph_steps):
             self._graph.replay()
             self._advance_host(self._graph_steps)
@@ -690,7 +781,9 @@ class FusedMLPEngine:
 
     # --------------------------------------------------------------- export
     def recent_stats(self, n: int = 1) -> torch.Tensor:
-        """Last n (loss, correct, count, step) rows, oldest first (host copy)."""
+        """Last n (loss, correct, count, step) rows, oldest first (host copy).  With
+        ``accumulate`` > 1: the last n micro-batch rows (column 3: the optimizer step each
+        contributes to)."""
         t = self.global_step
         ring = self.stats.size(0)
         rows = [(t - 1 - i) % ring for i in range(min(n, t, ring))][::-1]
