@@ -222,16 +222,39 @@ void mlp_train_step(optional<Tensor> x_u8, optional<Tensor> x_f32, Tensor labels
 // v3 pipelined step.  kind: 0 step (head + fused tail), 1 head only (grads),
 // 2 tail GRAD, 3 tail ADAM (after the allreduce), 4 PRIME (H1pre of the pending batch),
 // 8 tail ACC (a micro-batch that does not close its accumulation window).
+// sgd_momentum given (kinds 0 and 3 only): the tail applies torch.optim.SGD instead of Adam;
+// exp_avg is then the velocity (None allowed when the momentum is 0) and exp_avg_sq is unused.
 void mlp3(int64_t kind, Tensor x_u8, Tensor labels, Tensor order, Tensor counters, int64_t n_batches, int64_t B,
-          int64_t L1, int64_t L2, Tensor params, Tensor grads, Tensor exp_avg, Tensor exp_avg_sq, Tensor shadow,
+          int64_t L1, int64_t L2, Tensor params, Tensor grads, optional<Tensor> exp_avg_o,
+          optional<Tensor> exp_avg_sq_o, Tensor shadow,
           Tensor dh1t, Tensor xring, Tensor h1pre, Tensor act, Tensor yring, optional<Tensor> stats,
           bool advance_step, double lr,
           double beta1, double beta2, double eps, double weight_decay, double grad_scale, optional<Tensor> lr_t,
           bool adamw, optional<Tensor> stamps, std::vector<int64_t> dp_ctx, optional<Tensor> head_part,
           optional<Tensor> hand, int64_t dp_proto, bool dp_loop, int64_t repeat, optional<Tensor> clip_part,
           double clip_max_norm, optional<Tensor> clip_out, int64_t clip_nblk, bool acc_add, bool acc_rows,
-          optional<Tensor> acc_head_row) {
+          optional<Tensor> acc_head_row, optional<double> sgd_momentum, double sgd_dampening, bool sgd_nesterov) {
   TORCH_CHECK(kind >= 0 && kind <= 8, "mlp3: bad kind ", kind);
+  // SGD: refused here, before any launch, wherever it does not belong
+  rla::MLP3Sgd sgd{0, 0.f, 0.f, 0};
+  const bool has_m = exp_avg_o.has_value() && exp_avg_o->defined();
+  const bool has_v = exp_avg_sq_o.has_value() && exp_avg_sq_o->defined();
+  if (sgd_momentum.has_value()) {
+    TORCH_CHECK_VALUE(kind == rla::kMLP3Step || kind == rla::kMLP3TailAdam,
+                      "mlp3: SGD arguments belong to the step (kind 0) and the ADAM tail (kind 3), not kind ", kind);
+    TORCH_CHECK_VALUE(*sgd_momentum >= 0.0, "mlp3: sgd_momentum must be >= 0, got ", *sgd_momentum);
+    TORCH_CHECK_VALUE(*sgd_momentum == 0.0 || has_m, "mlp3: SGD with momentum needs the velocity tensor (exp_avg)");
+    TORCH_CHECK_VALUE(!sgd_nesterov || (*sgd_momentum > 0.0 && sgd_dampening == 0.0),
+                      "mlp3: Nesterov momentum requires a momentum and zero dampening");
+    sgd = rla::MLP3Sgd{1, (float)*sgd_momentum, (float)sgd_dampening, sgd_nesterov ? 1 : 0};
+  } else {
+    TORCH_CHECK_VALUE(sgd_dampening == 0.0 && !sgd_nesterov, "mlp3: sgd_dampening / sgd_nesterov need sgd_momentum");
+    // the kinds whose launch applies Adam (the rest never touch the optimizer state: an SGD
+    // engine launches them without exp_avg_sq)
+    const bool applies = kind == rla::kMLP3Step || kind == rla::kMLP3TailAdam || kind == rla::kMLP3StepDP ||
+                         kind == rla::kMLP3Step1 || kind == rla::kMLP3Step1DP;
+    TORCH_CHECK(!applies || (has_m && has_v), "mlp3: Adam (kind ", kind, ") needs exp_avg and exp_avg_sq");
+  }
   TORCH_CHECK(repeat >= 1, "mlp3: repeat must be >= 1");
   TORCH_CHECK(rla::mlp_supported((int)L1, (int)L2), "no fused MLP kernel for layer sizes ", L1, "/", L2);
   TORCH_CHECK(B >= 1 && B <= 256, "fused MLP step supports 1 <= batch <= 256");
@@ -240,10 +263,15 @@ void mlp3(int64_t kind, Tensor x_u8, Tensor labels, Tensor order, Tensor counter
   const rla::MLPShadowLayout lay = rla::mlp_shadow_layout((int)L1, (int)L2);
   check_dev(params, "params", at::kFloat);
   check_dev(grads, "grads", at::kFloat);
-  check_dev(exp_avg, "exp_avg", at::kFloat);
-  check_dev(exp_avg_sq, "exp_avg_sq", at::kFloat);
-  TORCH_CHECK(params.numel() == np && grads.numel() == np && exp_avg.numel() == np && exp_avg_sq.numel() == np,
+  if (has_m) check_dev(*exp_avg_o, "exp_avg", at::kFloat);
+  if (has_v) check_dev(*exp_avg_sq_o, "exp_avg_sq", at::kFloat);
+  TORCH_CHECK(params.numel() == np && grads.numel() == np && (!has_m || exp_avg_o->numel() == np) &&
+                  (!has_v || exp_avg_sq_o->numel() == np),
               "param / grad / Adam arenas must hold ", np, " floats");
+  if (sgd.enabled && has_m) {
+    TORCH_CHECK(exp_avg_o->device() == params.device(), "the velocity must be on ", params.device());
+    check_aligned(*exp_avg_o, "momentum_buffer (exp_avg)", 16);
+  }
   check_dev(shadow, "shadow", at::kBFloat16);
   TORCH_CHECK(shadow.numel() >= lay.total, "shadow must hold ", lay.total, " bf16");
   check_dev(dh1t, "dh1t", at::kBFloat16);
@@ -276,8 +304,8 @@ void mlp3(int64_t kind, Tensor x_u8, Tensor labels, Tensor order, Tensor counter
   a.B = (int)B; a.L1 = (int)L1; a.L2 = (int)L2;
   a.params = params.data_ptr<float>();
   a.grads = grads.data_ptr<float>();
-  a.exp_avg = exp_avg.data_ptr<float>();
-  a.exp_avg_sq = exp_avg_sq.data_ptr<float>();
+  a.exp_avg = has_m ? exp_avg_o->data_ptr<float>() : nullptr;
+  a.exp_avg_sq = has_v ? exp_avg_sq_o->data_ptr<float>() : nullptr;
   a.shadow = reinterpret_cast<uint16_t*>(shadow.data_ptr());
   a.dh1t = reinterpret_cast<uint16_t*>(dh1t.data_ptr());
   a.xring = reinterpret_cast<uint16_t*>(xring.data_ptr());
@@ -383,7 +411,7 @@ void mlp3(int64_t kind, Tensor x_u8, Tensor labels, Tensor order, Tensor counter
   const hipStream_t st = cur_stream(params);
   for (int64_t i = 0; i < repeat; ++i)
   {
-    const int rc = rla::launch_mlp3(a, (int)kind, st, &clip, &acc);
+    const int rc = rla::launch_mlp3(a, (int)kind, st, &clip, &acc, &sgd);
     TORCH_CHECK(rc == 0, "fused MLP v3 launch failed (kind ", kind, ", code ", rc, ")");
   }
 }
@@ -1101,7 +1129,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mlp_eval", &mlp_eval, "fused MNIST-MLP forward + NLL/accuracy");
   m.def("mlp3", &mlp3, "fused MNIST-MLP step v3 (pipelined layer 1): kind 0 step, 1 head, 2 tail-grad, "
         "3 tail-adam, 4 prime, 5 step with the in-kernel xGMI exchange, 6 one-launch step (B <= 32), "
-        "8 tail-acc (gradient accumulation: a micro-batch inside its window)",
+        "8 tail-acc (gradient accumulation: a micro-batch inside its window); sgd_momentum: SGD in the tail of 0 / 3",
         py::arg("kind"), py::arg("x_u8"), py::arg("labels"), py::arg("order"), py::arg("counters"),
         py::arg("n_batches"), py::arg("B"), py::arg("L1"), py::arg("L2"), py::arg("params"), py::arg("grads"),
         py::arg("exp_avg"), py::arg("exp_avg_sq"), py::arg("shadow"), py::arg("dh1t"), py::arg("xring"),
@@ -1111,7 +1139,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("hand"), py::arg("dp_proto"), py::arg("dp_loop"), py::arg("repeat"),
         py::arg("clip_part") = py::none(), py::arg("clip_max_norm") = 0.0, py::arg("clip_out") = py::none(),
         py::arg("clip_nblk") = -1, py::arg("acc_add") = false, py::arg("acc_rows") = false,
-        py::arg("acc_head_row") = py::none());
+        py::arg("acc_head_row") = py::none(), py::arg("sgd_momentum") = py::none(), py::arg("sgd_dampening") = 0.0,
+        py::arg("sgd_nesterov") = false);
   m.def("dp_pack_roundtrip", &dp_pack_roundtrip, "packed DP exchange wire form of fp32 pairs, encoded + decoded");
   m.def("mlp3_hand_words", [](int64_t l1, int64_t l2) { return rla::mlp3_hand_words((int)l1, (int)l2); });
   m.def("mlp3_hand_layout", []() {

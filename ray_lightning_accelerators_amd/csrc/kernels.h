@@ -325,11 +325,25 @@ struct MLP3Acc {
   const float* head_row;
 };
 constexpr int kMLP3RowWord = 11;  // counters word: stats rows written under MLP3Acc::rows
+// SGD instead of Adam in the tail (kMLP3Step / kMLP3TailAdam only; torch.optim.SGD's
+// semantics, mlp_common.h sgd1): its own compile-time instances of the tail kernel, which take
+// this struct as their last kernel argument -- in the slot where the Adam instances take
+// MLP3Acc, so those keep their argument offsets.  The velocity lives behind
+// MLP3Args::exp_avg (neither read nor written when momentum == 0); exp_avg_sq is never
+// touched and may be null.  lr / weight_decay / grad_scale / lr_ptr are MLP3Args'; the first
+// optimizer step (counters[0] <= 1 after the head's advance) sets the velocity to the gradient.
+// enabled == 0: Adam, the launches as they were.
+struct MLP3Sgd {
+  int enabled;
+  float momentum, dampening;
+  int nesterov;
+};
 // Returns 0, or a negative code before any launch: -8 misplaced clip arguments, -10 MLP3Acc
 // flags on a kind other than TailGrad / TailAcc (or rows without a row source), -11 TailAcc
-// with clip arguments.
+// with clip arguments, -12 MLP3Sgd on a kind other than Step / TailAdam (or momentum without
+// a velocity buffer).
 int launch_mlp3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip* clip = nullptr,
-                const MLP3Acc* acc = nullptr);
+                const MLP3Acc* acc = nullptr, const MLP3Sgd* sgd = nullptr);
 
 int mlp3_act_rows(int L1, int L2);
 int mlp3_h1_copies(int L1);  // H1pre copies per ring slot (mlp_step3.hip H1Copies)

@@ -81,6 +81,26 @@ __device__ __forceinline__ float adam1(float p, float g, float& m, float& v, con
   return fmaf(-o.step_size, m / denom, p);
 }
 
+// torch.optim.SGD's per-step scalars.  `first`: the launch belongs to optimizer step
+// t <= 1, where the velocity is the gradient itself (optim_kernels.hip sgd_kernel's rule).
+struct SgdScal {
+  float lr, momentum, one_minus_damp, wd;
+  int nesterov, first;
+};
+
+// One SGD element, torch's order of operations; explicit FMAs and no contraction, like
+// adam1: the tile epilogue and both small-parameter routes write the same bits.  `buf`
+// is neither read nor written when momentum == 0.
+__device__ __forceinline__ float sgd1(float p, float g, float& buf, const SgdScal& o) {
+#pragma clang fp contract(off)
+  if (o.wd != 0.f) g = fmaf(o.wd, p, g);
+  if (o.momentum != 0.f) {
+    buf = o.first ? g : fmaf(o.momentum, buf, o.one_minus_damp * g);
+    g = o.nesterov ? fmaf(o.momentum, buf, g) : buf;
+  }
+  return fmaf(-o.lr, g, p);
+}
+
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 // ds_read_b64_tr_b16: lane i of each 16-lane group receives column i of the
 // 4x16 bf16 block whose rows lanes 4q+p point at.

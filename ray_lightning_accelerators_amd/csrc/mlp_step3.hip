@@ -48,6 +48,16 @@
 // counters[kMLP3RowWord] % ring, which that lane advances: the head kernels are untouched --
 // a one-block head is simply given a one-row `stats` and the tail files that row.
 //
+// SGD (MLP3Sgd, kernels.h): compile-time instances of the tail (kinds Step and TailAdam
+// only) that apply torch.optim.SGD -- weight decay, momentum, dampening, Nesterov; sgd1 in
+// mlp_common.h -- where the other instances apply Adam: in the W1 tile epilogue and on the
+// small parameters of either route.  The velocity lives behind `exp_avg` and is not touched
+// without momentum; `exp_avg_sq` is never touched.  The first optimizer step (counters[0]
+// <= 1) sets the velocity to the gradient.  Everything the tail does besides the update is
+// unchanged, so the next batch's layer 1 still comes from the tile in registers.  SGD never
+// runs as one launch or with the in-kernel exchange; AdamW is `adamw` of MLP3Args on
+// every route.
+//
 // Device state (graph-replay safe): counters[0] optimizer step, [1] cursor of
 // the NEXT batch, [2] cursor the last head consumed, [3] ring slot the next head
 // reads, [4] which of the two `order` epoch buffers counters[1] indexes.
@@ -56,6 +66,7 @@
 // wave-instruction covers 256 contiguous bytes.  The integer atomics are
 // associative, so H1pre (and the step) does not depend on arrival order.
 #include <cfloat>
+#include <type_traits>
 
 #include "common.h"
 #include "kernels.h"
@@ -895,9 +906,11 @@ struct RepLds {
 // REP (the one-launch step): called twice -- L == nullptr: task setup + Adam
 // prefetch only (before the block's head pass); then with L: the gradient from
 // this block's LDS images instead of act / dh1t (r keeps the first call's state)
-template <int L1, int L2, bool REP = false>
+// SGD (the SGD tail): the prefetch is the weight, plus the velocity (behind exp_avg) when
+// ``sgd_mom``; exp_avg_sq is never read.
+template <int L1, int L2, bool REP = false, bool SGD = false>
 __device__ __forceinline__ void small_compute(const MLP3Args& a, bool prefetch_adam, int task, SmallRes& r,
-                                              const RepLds* L = nullptr) {
+                                              const RepLds* L = nullptr, bool sgd_mom = false) {
   const bool setup = !REP || L == nullptr, compute = !REP || L != nullptr;
   using O = Off<L1, L2>;
   using A = Act<L1, L2>;
@@ -956,7 +969,12 @@ __device__ __forceinline__ void small_compute(const MLP3Args& a, bool prefetch_a
     if (setup && prefetch_adam)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {  // unconditional: gi is in bounds for invalid rows too (row 0)
-        r.pv[i] = a.params[r.gi[i]]; r.mv[i] = a.exp_avg[r.gi[i]]; r.vv[i] = a.exp_avg_sq[r.gi[i]];
+        if constexpr (SGD) {
+          r.pv[i] = a.params[r.gi[i]];
+          if (sgd_mom) r.mv[i] = a.exp_avg[r.gi[i]];
+        } else {
+          r.pv[i] = a.params[r.gi[i]]; r.mv[i] = a.exp_avg[r.gi[i]]; r.vv[i] = a.exp_avg_sq[r.gi[i]];
+        }
       }
     if (!compute) return;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -987,7 +1005,14 @@ __device__ __forceinline__ void small_compute(const MLP3Args& a, bool prefetch_a
     if (setup) {
       r.kind = 2;
       r.valid[0] = true;
-      if (prefetch_adam) { r.pv[0] = a.params[r.gi[0]]; r.mv[0] = a.exp_avg[r.gi[0]]; r.vv[0] = a.exp_avg_sq[r.gi[0]]; }
+      if constexpr (SGD) {
+        if (prefetch_adam) {
+          r.pv[0] = a.params[r.gi[0]];
+          if (sgd_mom) r.mv[0] = a.exp_avg[r.gi[0]];
+        }
+      } else {
+        if (prefetch_adam) { r.pv[0] = a.params[r.gi[0]]; r.mv[0] = a.exp_avg[r.gi[0]]; r.vv[0] = a.exp_avg_sq[r.gi[0]]; }
+      }
     }
     if (!compute) return;
     float s8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -1008,8 +1033,10 @@ __device__ __forceinline__ void small_compute(const MLP3Args& a, bool prefetch_a
 }
 
 // ``add`` (gradient branch only): grads += the value, one fp32 add (accumulation).
-template <int L1, int L2>
-__device__ __forceinline__ void small_finalize(const MLP3Args& a, bool adam, const SmallRes& r, const AdamScal& o,
+// Scal = SgdScal: sgd1 in Adam's place, the velocity behind exp_avg (untouched when
+// momentum == 0), exp_avg_sq untouched.
+template <int L1, int L2, class Scal = AdamScal>
+__device__ __forceinline__ void small_finalize(const MLP3Args& a, bool adam, const SmallRes& r, const Scal& o,
                                                bool add = false) {
   using O = Off<L1, L2>;
   if (r.kind < 0) return;
@@ -1021,10 +1048,17 @@ __device__ __forceinline__ void small_finalize(const MLP3Args& a, bool adam, con
     if (!r.valid[i]) continue;
     if (adam) {
       float m_ = r.mv[i], v_ = r.vv[i];
-      const float p_ = adam1(r.pv[i], r.v[i], m_, v_, o);
-      a.params[r.gi[i]] = p_;
-      a.exp_avg[r.gi[i]] = m_;
-      a.exp_avg_sq[r.gi[i]] = v_;
+      float p_;
+      if constexpr (std::is_same<Scal, SgdScal>::value) {
+        p_ = sgd1(r.pv[i], r.v[i], m_, o);
+        a.params[r.gi[i]] = p_;
+        if (o.momentum != 0.f) a.exp_avg[r.gi[i]] = m_;
+      } else {
+        p_ = adam1(r.pv[i], r.v[i], m_, v_, o);
+        a.params[r.gi[i]] = p_;
+        a.exp_avg[r.gi[i]] = m_;
+        a.exp_avg_sq[r.gi[i]] = v_;
+      }
       SHW[r.gi[i]] = (__bf16)p_;
       sh4[i] = (__bf16)p_;
     } else {
@@ -1507,19 +1541,30 @@ __device__ __forceinline__ int dp_task_owner(const MLP3Args& a, int task) { retu
 
 // ADAM mode: flat Adam over every non-W1 parameter (after the allreduce).
 // ``clipped``: the gradient is further scaled by the clip coefficient (MLP3Clip).
-template <int L1, int L2>
-__device__ __forceinline__ void small_adam_flat(const MLP3Args& a, const AdamScal& o, int blk, int nblk,
+// Scal = SgdScal: sgd1 in Adam's place (small_finalize's rules for the state).
+template <int L1, int L2, class Scal = AdamScal>
+__device__ __forceinline__ void small_adam_flat(const MLP3Args& a, const Scal& o, int blk, int nblk,
                                                 bool clipped, float coef) {
   using O = Off<L1, L2>;
   __bf16* SHW = reinterpret_cast<__bf16*>(a.shadow);
   for (int64_t i = O::B1 + (int64_t)blk * blockDim.x + threadIdx.x; i < O::NP; i += (int64_t)nblk * blockDim.x) {
-    float m = a.exp_avg[i], v = a.exp_avg_sq[i];
-    float gr = a.grads[i] * a.grad_scale;
-    if (clipped) gr *= coef;
-    const float p = adam1(a.params[i], gr, m, v, o);
-    a.params[i] = p;
-    a.exp_avg[i] = m;
-    a.exp_avg_sq[i] = v;
+    float p;
+    if constexpr (std::is_same<Scal, SgdScal>::value) {
+      float m = o.momentum != 0.f ? a.exp_avg[i] : 0.f;
+      float gr = a.grads[i] * a.grad_scale;
+      if (clipped) gr *= coef;
+      p = sgd1(a.params[i], gr, m, o);
+      a.params[i] = p;
+      if (o.momentum != 0.f) a.exp_avg[i] = m;
+    } else {
+      float m = a.exp_avg[i], v = a.exp_avg_sq[i];
+      float gr = a.grads[i] * a.grad_scale;
+      if (clipped) gr *= coef;
+      p = adam1(a.params[i], gr, m, v, o);
+      a.params[i] = p;
+      a.exp_avg[i] = m;
+      a.exp_avg_sq[i] = v;
+    }
     const __bf16 pb = (__bf16)p;
     SHW[i] = pb;
     if (i >= O::W2 && i < O::B2) {
@@ -1617,11 +1662,31 @@ __device__ __forceinline__ float tail_clip_coef(const MLP3Args& a, const MLP3Cli
 // Both write the micro-batch's stats row when ga.rows (tail_acc_stats).
 // One kernel text for both: `ga` is the LAST kernel argument, so the ACC = false instances
 // keep the argument offsets (and the instruction stream) they had without it.
-template <int L1, int L2, bool ACC = false, int MODE = -1>
+//
+// SGD = true (kFused / kAdam only, never ACC): torch.optim.SGD where the other instances
+// apply Adam -- the W1 tile epilogue, small_finalize (kFused) and small_adam_flat (kAdam)
+// call sgd1 with the SgdScal lane 0 publishes (no pow).  The velocity lives behind
+// a.exp_avg and is neither loaded nor stored when momentum == 0; a.exp_avg_sq is never
+// touched.  Clip coefficient, grad_scale, the three bf16 shadows, the next batch's layer-1
+// partial, the H1pre zero-fill, health counts and stats rows are the Adam instances'.
+// The last kernel argument of these instances is MLP3Sgd, in MLP3Acc's slot (an SGD tail
+// never accumulates), so every other instance keeps its argument offsets.
+template <bool SGD>
+struct TailLastArg { using type = MLP3Acc; };
+template <>
+struct TailLastArg<true> { using type = MLP3Sgd; };
+
+template <int L1, int L2, bool ACC = false, int MODE = -1, bool SGD = false>
 __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, int mode_rt, MLP3Clip clip,
-                                                                   MLP3Acc ga) {
+                                                                   typename TailLastArg<SGD>::type last) {
   static_assert(ACC ? (MODE == kGrad || MODE == kAcc) : MODE < 0, "accumulating tails fix their mode");
-  const int mode = ACC ? MODE : mode_rt;
+  static_assert(!(ACC && SGD), "the accumulating tails apply no optimizer");
+  MLP3Acc ga{0, 0, nullptr};
+  MLP3Sgd sg{0, 0.f, 0.f, 0};
+  if constexpr (SGD) sg = last; else ga = last;
+  const bool sgd_mom = SGD && sg.momentum != 0.f;  // the velocity exists
+  // an SGD instance runs kFused or kAdam and carries no other mode's code
+  const int mode = ACC ? MODE : (SGD ? (mode_rt == kFused ? (int)kFused : (int)kAdam) : mode_rt);
   const bool acc_tail = ACC && mode == kAcc;   // compile-time in either instance
   const bool add = ACC && ga.add != 0;
   constexpr int TN1 = L1 / 16;
@@ -1629,14 +1694,14 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
   __shared__ __attribute__((aligned(16))) __bf16 sX[kBMax * kXSS];
   __shared__ __attribute__((aligned(16))) __bf16 sXn[kBMax * kXSS];
   __shared__ __attribute__((aligned(16))) __bf16 sW[L1 * kXSS];
-  __shared__ AdamScal sh_o;
+  __shared__ typename std::conditional<SGD, SgdScal, AdamScal>::type sh_o;
   __shared__ float sh_coef;  // ADAM mode: the clip coefficient, beside sh_o
   __shared__ int sh_clip;    // ... and whether this launch clips (published with it: the
                              // clip argument's registers are free before the tile loop)
   const int tid = threadIdx.x, lane = tid & 63, ct = tid >> 6, r16 = lane & 15, g = lane >> 4;
   const bool dp = mode == kFusedDP;
   const bool do_grad = mode == kFused || mode == kGrad || dp || acc_tail;
-  const bool do_adam = mode == kFused || mode == kAdam || dp;
+  const bool do_adam = mode == kFused || mode == kAdam || dp;  // the optimizer: Adam, or SGD
   const bool do_fwd = mode != kGrad;
   if (a.stamps && blockIdx.x == 0 && tid == 0) a.stamps[8] = __builtin_amdgcn_s_memrealtime();
   // every block reads the head's NEXT copy (never written in this launch);
@@ -1651,7 +1716,10 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
   const float lr_now = a.lr_ptr ? a.lr_ptr[0] : a.lr;
   auto scalars = [&]() {
     if (tid == 0 && do_adam) {
-      adam_scalars(sh_o, t_step, lr_now, a.beta1, a.beta2, a.eps, a.weight_decay, a.adamw);
+      if constexpr (SGD)
+        sh_o = SgdScal{lr_now, sg.momentum, 1.f - sg.dampening, a.weight_decay, sg.nesterov, t_step <= 1 ? 1 : 0};
+      else
+        adam_scalars(sh_o, t_step, lr_now, a.beta1, a.beta2, a.eps, a.weight_decay, a.adamw);
       if (mode == kAdam) {
         sh_clip = clip.part != nullptr;
         if (clip.part) sh_coef = tail_clip_coef(a, clip);
@@ -1678,7 +1746,7 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
       return;
     }
     SmallRes r;
-    small_compute<L1, L2>(a, mode != kGrad && !acc_tail, sblk * TN1 + ct, r);
+    small_compute<L1, L2, false, SGD>(a, mode != kGrad && !acc_tail, sblk * TN1 + ct, r, nullptr, sgd_mom);
     scalars();
     __syncthreads();
     if (mode == kFusedDP) {
@@ -1727,8 +1795,12 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
   F4 p4{}, m4{}, v4{}, g4{};
   if (do_adam) {
     p4 = *reinterpret_cast<const F4*>(a.params + gidx);
-    m4 = *reinterpret_cast<const F4*>(a.exp_avg + gidx);
-    v4 = *reinterpret_cast<const F4*>(a.exp_avg_sq + gidx);
+    if constexpr (SGD) {
+      if (sgd_mom) m4 = *reinterpret_cast<const F4*>(a.exp_avg + gidx);
+    } else {
+      m4 = *reinterpret_cast<const F4*>(a.exp_avg + gidx);
+      v4 = *reinterpret_cast<const F4*>(a.exp_avg_sq + gidx);
+    }
   }
   if (mode == kAdam || add) g4 = *reinterpret_cast<const F4*>(a.grads + gidx);  // add: the running sum
   bf16x4 w4;
@@ -1827,19 +1899,24 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
     }
   }
   if (do_adam) {
-    const AdamScal o = sh_o;
+    const auto o = sh_o;
     const bool clipped = mode == kAdam && sh_clip != 0;
     const float coef = clipped ? sh_coef : 1.f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       float gr = (mode == kAdam) ? g4.v[i] * a.grad_scale : acc[i];
       if (clipped) gr *= coef;
-      p4.v[i] = adam1(p4.v[i], gr, m4.v[i], v4.v[i], o);
+      if constexpr (SGD) p4.v[i] = sgd1(p4.v[i], gr, m4.v[i], o);
+      else p4.v[i] = adam1(p4.v[i], gr, m4.v[i], v4.v[i], o);
       w4[i] = (__bf16)p4.v[i];
     }
     *reinterpret_cast<F4*>(a.params + gidx) = p4;
-    *reinterpret_cast<F4*>(a.exp_avg + gidx) = m4;
-    *reinterpret_cast<F4*>(a.exp_avg_sq + gidx) = v4;
+    if constexpr (SGD) {
+      if (sgd_mom) *reinterpret_cast<F4*>(a.exp_avg + gidx) = m4;
+    } else {
+      *reinterpret_cast<F4*>(a.exp_avg + gidx) = m4;
+      *reinterpret_cast<F4*>(a.exp_avg_sq + gidx) = v4;
+    }
     *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(a.shadow) + gidx) = w4;
   }
   // ---- next step's layer-1 partial: H1pre[b][m] += sum_{16 px} X'[b][px] W1[m][px] ----
@@ -2320,7 +2397,8 @@ template <int L1, int L2>
 constexpr bool kProbeDP = L1 == 32 && L2 == 64;
 
 template <int L1, int L2>
-int dispatch3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip& clip, const MLP3Acc& acc) {
+int dispatch3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip& clip, const MLP3Acc& acc,
+              const MLP3Sgd& sgd) {
   constexpr int kOneGrid = 1 + kTiles + One<L1, L2>::NSMALL;
   if (kind == kMLP3Step1) {
     if (a.B > 32 || !a.hand || kOneGrid > 256) return -5;
@@ -2396,6 +2474,11 @@ int dispatch3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip& c
     int extra = (int)((nsmall + NT - 1) / NT);
     grid += extra < 64 ? extra : 64;
   }
+  if (sgd.enabled) {  // launch_mlp3 admits it for Step / TailAdam only: the same grid, the SGD instance
+    hipLaunchKernelGGL((mlp3_tail_kernel<L1, L2, false, -1, true>), dim3(grid), dim3(NT), 0, stream, a, mode, clip,
+                       sgd);
+    return 0;
+  }
   if (mode >= 0) hipLaunchKernelGGL((mlp3_tail_kernel<L1, L2>), dim3(grid), dim3(NT), 0, stream, a, mode, clip, acc);
   return 0;
 }
@@ -2430,8 +2513,18 @@ MLP3HandLayout mlp3_hand_layout() {
 }
 MLP3AdamCacheLayout mlp3_adam_cache_layout() { return {kHandAdamStep, kHandAdamBetas, kHandAdamBc1, kHandAdamBc2}; }
 
-int launch_mlp3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip* clip_in, const MLP3Acc* acc_in) {
+int launch_mlp3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip* clip_in, const MLP3Acc* acc_in,
+                const MLP3Sgd* sgd_in) {
   if (a.B > kBMax || a.B < 1) return -2;
+  // SGD belongs to the two kinds whose tail applies the optimizer outside the one-launch
+  // kernel and the in-kernel exchange
+  MLP3Sgd sgd{0, 0.f, 0.f, 0};
+  if (sgd_in && sgd_in->enabled) {
+    if (kind != kMLP3Step && kind != kMLP3TailAdam) return -12;
+    if (!(sgd_in->momentum >= 0.f) || (sgd_in->momentum != 0.f && !a.exp_avg)) return -12;
+    if (sgd_in->nesterov && (sgd_in->momentum <= 0.f || sgd_in->dampening != 0.f)) return -12;
+    sgd = *sgd_in;
+  }
   // TailAcc never clips: its window is still open
   if (kind == kMLP3TailAcc && clip_in && (clip_in->part || clip_in->out)) return -11;
   // clipping belongs to the ADAM tail alone; every other kind launches without it
@@ -2447,7 +2540,7 @@ int launch_mlp3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip*
     if (acc_in->rows && (!a.stats || (a.B <= kHeadRows && !acc_in->head_row))) return -10;
     acc = *acc_in;
   }
-#define RLA_CASE(a1, a2) if (a.L1 == a1 && a.L2 == a2) return dispatch3<a1, a2>(a, kind, stream, clip, acc);
+#define RLA_CASE(a1, a2) if (a.L1 == a1 && a.L2 == a2) return dispatch3<a1, a2>(a, kind, stream, clip, acc, sgd);
   RLA_CASE(32, 32) RLA_CASE(32, 64) RLA_CASE(32, 128) RLA_CASE(32, 256)
   RLA_CASE(64, 64) RLA_CASE(64, 128) RLA_CASE(64, 256)
   RLA_CASE(128, 64) RLA_CASE(128, 128) RLA_CASE(128, 256)

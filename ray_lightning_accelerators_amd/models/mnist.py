@@ -21,7 +21,13 @@ device (``FusedMLPEngine(clip_norm=c)``).
 a batch inside its window is head / tail(acc) -- gradients added up on the device, no
 Adam -- and the batch that closes it head / tail(grad) / [allreduce] / [norm partials] /
 tail(adam) with every micro-batch weighted 1/K; the Trainer dispatches per batch and this
-step counts the optimizer steps (``counts_steps``).  Batches the
+step counts the optimizer steps (``counts_steps``).
+The optimizer may be a fused single-group ``torch.optim.Adam``, ``AdamW`` or ``SGD``
+(``FusedMLPEngine(optimizer=...)``).  AdamW takes every route Adam takes, the one-launch
+step and the in-kernel exchange included.  SGD (momentum, dampening, Nesterov, weight decay)
+is applied by the tail kernel: head / tail at world size 1, else -- and under clipping or
+accumulation -- head / tail(grad | acc) / [allreduce] / [norm partials] / tail(sgd); never
+one launch, never the in-kernel exchange.  ``optimizer.state_dict()`` stays torch's.  Batches the
 resident path cannot serve (e.g. user transforms) use a one-launch fp32-input
 kernel; CPU / unsupported shapes use the ordinary autograd path.
 """
@@ -162,9 +168,14 @@ class FusedMNISTStep:
         if len(trainer.optimizers) != 1:
             raise RuntimeError("fused step expects one optimizer")
         opt = trainer.optimizers[0]
-        if type(opt) is not torch.optim.Adam or len(opt.param_groups) != 1 or \
-                not getattr(opt, "_rla_fused", False) or opt.param_groups[0].get("amsgrad"):
-            raise RuntimeError("fused step expects a fused single-group torch.optim.Adam")
+        if type(opt) not in (torch.optim.Adam, torch.optim.AdamW, torch.optim.SGD) or len(opt.param_groups) != 1 or \
+                not getattr(opt, "_rla_fused", False) or opt.param_groups[0].get("amsgrad") or \
+                opt.param_groups[0].get("maximize"):
+            raise RuntimeError("fused step expects a fused single-group torch.optim.Adam, AdamW or SGD "
+                               "(no amsgrad, no maximize)")
+        # which update the engine applies: "adam" / "adamw" / "sgd"
+        self.opt_kind = {torch.optim.Adam: "adam", torch.optim.AdamW: "adamw", torch.optim.SGD: "sgd"}[type(opt)]
+        self.sgd = self.opt_kind == "sgd"
         acc = trainer.accelerator_backend
         arena = acc.arena
         self.np = fused_mlp.mlp_param_count(L1, L2)
@@ -206,24 +217,32 @@ class FusedMNISTStep:
         from ..parallel.mlp_engine import FusedMLPEngine
 
         g = self.opt.param_groups[0]
-        bufs = dict(params=self.arena.data[: self.np], grads=self.arena.grad[: self.np],
-                    exp_avg=self.gs.m[: self.np], exp_avg_sq=self.gs.v[: self.np])
+        bufs = dict(params=self.arena.data[: self.np], grads=self.arena.grad[: self.np])
+        if self.sgd:
+            bufs["momentum_buffer"] = self.gs.buf[: self.np]
+            hyper = dict(optimizer="sgd", momentum=g.get("momentum", 0.0), dampening=g.get("dampening", 0.0),
+                         nesterov=bool(g.get("nesterov", False)))
+        else:
+            bufs.update(exp_avg=self.gs.m[: self.np], exp_avg_sq=self.gs.v[: self.np])
+            hyper = dict(optimizer=self.opt_kind, betas=tuple(g["betas"]), eps=g["eps"])
         dp_ctx = None
         rearm = None
         # clipping needs the whole averaged gradient before Adam: the allreduce route;
-        # accumulation steps once per window, the in-kernel exchange at every batch
-        if self.world > 1 and get_config().fused_dp and self.clip_norm is None and self.accumulate == 1:
+        # accumulation steps once per window, the in-kernel exchange at every batch; and the
+        # exchange's epilogue is Adam / AdamW, so SGD takes the allreduce route too
+        if self.world > 1 and get_config().fused_dp and self.clip_norm is None and self.accumulate == 1 \
+                and not self.sgd:
             from ..parallel.comm import get_native_comm
 
             comm = get_native_comm()  # every rank reaches here together (first epoch)
             if comm is not None:
                 dp_ctx = comm.dp_context(fused_mlp.mlp3_dp_capacity(self.L1, self.L2))
                 rearm = comm.dp_rearm
-        eng = FusedMLPEngine(self.L1, self.L2, B, lr=float(g["lr"]), betas=tuple(g["betas"]), eps=g["eps"],
+        eng = FusedMLPEngine(self.L1, self.L2, B, lr=float(g["lr"]),
                              weight_decay=g["weight_decay"], device=self.dev, world_size=self.world,
                              rank=self.trainer.global_rank, allreduce=self._allreduce, buffers=bufs,
                              stats_ring=ENGINE_STATS_RING, dp_context=dp_ctx, dp_rearm=rearm,
-                             clip_norm=self.clip_norm, accumulate=self.accumulate)
+                             clip_norm=self.clip_norm, accumulate=self.accumulate, **hyper)
         eng.set_step(self.gs.step)
         eng.lr_tensor = self.lr_tensor  # LR schedulers update one device scalar
         eng.attach_dataset(self._u8, self._labels)
@@ -304,6 +323,38 @@ class FusedMNISTStep:
     def on_lr_change(self) -> None:
         self._sync_lr()
 
+    def _sync_engine(self) -> None:
+        """The group's hyperparameters, refreshed per dispatch (a user or a scheduler may
+        have edited ``param_groups``)."""
+        eng, g = self.eng, self.opt.param_groups[0]
+        eng.lr, eng.wd = self.lr_val, g["weight_decay"]
+        if self.sgd:
+            eng.momentum, eng.dampening = float(g.get("momentum", 0.0)), float(g.get("dampening", 0.0))
+            eng.nesterov = bool(g.get("nesterov", False))
+            # torch's SGD state has no step: after a resume the group restarts at 1, and
+            # loader-fed batches step outside the engine.  Its device counter (the kernels'
+            # "first step" rule, the stats-ring slot) follows gs.step.
+            if eng.optimizer_steps != self.gs.step:
+                eng.set_step(self.gs.step)
+        else:
+            eng.betas, eng.eps = tuple(g["betas"]), g["eps"]
+
+    def _apply_optimizer(self, p, gr, scale: float) -> None:
+        """The optimizer over the arena after a loader-fed batch left its gradient."""
+        from ..ops.optim import fused_adam_, fused_sgd_
+
+        g = self.opt.param_groups[0]
+        if self.sgd:
+            mom = float(g.get("momentum", 0.0))
+            fused_sgd_(p, gr, self.gs.buf[: self.np] if mom != 0.0 else None, lr=self.lr_val, momentum=mom,
+                       dampening=g.get("dampening", 0.0), weight_decay=g["weight_decay"],
+                       nesterov=bool(g.get("nesterov", False)), grad_scale=scale, step=self.counters[0:1],
+                       lr_tensor=self.lr_tensor)
+        else:
+            fused_adam_(p, gr, self.gs.m[: self.np], self.gs.v[: self.np], lr=self.lr_val, betas=tuple(g["betas"]),
+                        eps=g["eps"], weight_decay=g["weight_decay"], grad_scale=scale,
+                        adamw=self.opt_kind == "adamw", step=self.counters[0:1], lr_tensor=self.lr_tensor)
+
     def _train_micro_batch(self, batch, batch_idx: int):
         """``train_batch`` under ``accumulate_grad_batches=K``: one micro-batch.  Batch i of
         the epoch closes its window when (i + 1) % K == 0 or it is the epoch's last; only
@@ -312,19 +363,17 @@ class FusedMNISTStep:
         self._sync_lr()
         K = self.accumulate
         g = self.opt.param_groups[0]
-        b1, b2 = g["betas"]
         if isinstance(batch, tuple) and len(batch) == 2 and batch[0] == "__rla_resident__":
             eng = self.eng
-            eng.lr, eng.betas, eng.eps, eng.wd = self.lr_val, (b1, b2), g["eps"], g["weight_decay"]
+            self._sync_engine()
             before = eng.optimizer_steps
             eng.step()  # one micro-batch (no graph is captured on this per-batch path)
             closing = eng.optimizer_steps != before
             row = eng.stats[(eng.global_step - 1) % eng.stats.size(0)]  # one ring row per micro-batch
         else:
-            from ..ops.optim import clip_partials, fused_adam_
+            from ..ops.optim import clip_partials
 
             p, gr = self.arena.data[: self.np], self.arena.grad[: self.np]
-            m, v = self.gs.m[: self.np], self.gs.v[: self.np]
             n = int(getattr(self.trainer, "num_training_batches", 0) or 0)
             micro = batch_idx % K
             closing = (batch_idx + 1) % K == 0 or (n > 0 and batch_idx + 1 >= n)
@@ -333,11 +382,10 @@ class FusedMNISTStep:
             x = x.to(self.dev, non_blocking=True).reshape(x.size(0), -1).float().contiguous()
             y = y.to(self.dev, non_blocking=True).long().contiguous()
             stats = torch.zeros(1, 4, device=self.dev)  # this batch's own row
-            fused_mlp.mlp_train_step(p, gr, B=x.size(0), labels=y, x_f32=x, L1=self.L1, L2=self.L2, exp_avg=m,
-                                     exp_avg_sq=v, stats=stats, accumulate_grad=micro > 0, apply_adam=False,
-                                     advance_step=closing, lr=self.lr_val, betas=(b1, b2), eps=g["eps"],
-                                     weight_decay=g["weight_decay"], lr_tensor=self.lr_tensor,
-                                     counters=self.counters)
+            fused_mlp.mlp_train_step(p, gr, B=x.size(0), labels=y, x_f32=x, L1=self.L1, L2=self.L2,
+                                     stats=stats, accumulate_grad=micro > 0, apply_adam=False,
+                                     advance_step=closing, lr=self.lr_val, weight_decay=g["weight_decay"],
+                                     lr_tensor=self.lr_tensor, counters=self.counters)
             if closing:
                 scale = 1.0 / (self.world * K)
                 if self._allreduce is not None and self.acc.sync is not None:
@@ -345,9 +393,7 @@ class FusedMNISTStep:
                 if self.clip_norm is not None:
                     norm = clip_partials(gr, 32).sum().sqrt() * scale
                     gr.mul_(torch.clamp(self.clip_norm / (norm + 1e-6), max=1.0))
-                fused_adam_(p, gr, m, v, lr=self.lr_val, betas=(b1, b2), eps=g["eps"],
-                            weight_decay=g["weight_decay"], grad_scale=scale, step=self.counters[0:1],
-                            lr_tensor=self.lr_tensor)
+                self._apply_optimizer(p, gr, scale)
                 if self.eng is not None:
                     self.eng.refresh_shadow()  # params moved outside the engine
             row = stats[0]
@@ -370,19 +416,20 @@ class FusedMNISTStep:
             return self._train_micro_batch(batch, batch_idx)
         self._sync_lr()
         g = self.opt.param_groups[0]
-        b1, b2 = g["betas"]
         p = self.arena.data[: self.np]
         gr = self.arena.grad[: self.np]
-        m, v = self.gs.m[: self.np], self.gs.v[: self.np]
-        fused = self.world == 1 and self.clip_norm is None
-        kw = dict(L1=self.L1, L2=self.L2, exp_avg=m, exp_avg_sq=v, stats=self.stats, apply_adam=fused,
-                  advance_step=True, lr=self.lr_val, betas=(b1, b2), eps=g["eps"], weight_decay=g["weight_decay"],
-                  lr_tensor=self.lr_tensor, counters=self.counters)
+        # the loader-fed kernel applies Adam / AdamW itself; SGD follows it as its own launch
+        fused = self.world == 1 and self.clip_norm is None and not self.sgd
+        kw = dict(L1=self.L1, L2=self.L2, stats=self.stats, apply_adam=fused, advance_step=True, lr=self.lr_val,
+                  weight_decay=g["weight_decay"], lr_tensor=self.lr_tensor, counters=self.counters)
+        if not self.sgd:
+            kw.update(exp_avg=self.gs.m[: self.np], exp_avg_sq=self.gs.v[: self.np], betas=tuple(g["betas"]),
+                      eps=g["eps"], adamw=self.opt_kind == "adamw")
         stats = self.stats
         if isinstance(batch, tuple) and len(batch) == 2 and batch[0] == "__rla_resident__":
             # v3 pipelined step (head + tail [+ allreduce + tail-adam]); Adam is the engine's
             eng = self.eng
-            eng.lr, eng.betas, eng.eps, eng.wd = self.lr_val, (b1, b2), g["eps"], g["weight_decay"]
+            self._sync_engine()
             eng.step()
             stats = eng.stats
             fused = True  # optimizer already applied
@@ -396,7 +443,7 @@ class FusedMNISTStep:
         if not fused:
             if self._allreduce is not None and self.acc.sync is not None:
                 self._allreduce(self.arena.grad[: self.np])
-            from ..ops.optim import clip_partials, fused_adam_
+            from ..ops.optim import clip_partials
 
             if self.clip_norm is not None:
                 # loader-fed batches are rare and slow anyway: the coefficient with torch
@@ -405,8 +452,7 @@ class FusedMNISTStep:
                 coef = torch.clamp(self.clip_norm / (norm + 1e-6), max=1.0)
                 gr.mul_(coef)
 
-            fused_adam_(p, gr, m, v, lr=self.lr_val, betas=(b1, b2), eps=g["eps"], weight_decay=g["weight_decay"],
-                        grad_scale=1.0 / self.world, step=self.counters[0:1], lr_tensor=self.lr_tensor)
+            self._apply_optimizer(p, gr, 1.0 / self.world)
         if self.eng is not None and stats is self.stats:
             self.eng.refresh_shadow()  # params moved outside the engine
         self.gs.step += 1
@@ -480,7 +526,7 @@ class FusedMNISTStep:
         eng = self.eng
         self._sync_lr()
         g = self.opt.param_groups[0]
-        eng.lr, eng.betas, eng.eps, eng.wd = self.lr_val, tuple(g["betas"]), g["eps"], g["weight_decay"]
+        self._sync_engine()
         done = 0
         if graph_steps > 1 and eng._graph is None and not self._capture_failed and get_config().use_hip_graph \
                 and n_steps >= graph_steps and eng.steps_to_epoch_end() >= graph_steps:

@@ -294,8 +294,8 @@ def mlp3_launch(
     L2: int,
     params: torch.Tensor,
     grads: torch.Tensor,
-    exp_avg: torch.Tensor,
-    exp_avg_sq: torch.Tensor,
+    exp_avg: Optional[torch.Tensor],
+    exp_avg_sq: Optional[torch.Tensor],
     shadow: torch.Tensor,
     dh1t: torch.Tensor,
     xring: torch.Tensor,
@@ -325,6 +325,9 @@ def mlp3_launch(
     acc_add: bool = False,
     acc_rows: bool = False,
     acc_head_row: Optional[torch.Tensor] = None,
+    sgd_momentum: Optional[float] = None,
+    sgd_dampening: float = 0.0,
+    sgd_nesterov: bool = False,
 ) -> None:
     """One v3 launch (GPU only; ``repeat``: that many identical launches back to back
     from one C++ loop -- every step's state lives on the device).  ``kind``: MLP3_STEP (head + fused tail, world size 1),
@@ -360,7 +363,26 @@ def mlp3_launch(
     gradient (one fp32 add per element) instead of the overwrite.  ``acc_rows``: the tail
     writes the micro-batch's stats row at ``counters[MLP3_ROW_WORD] % ring`` and advances
     that word; ``acc_head_row`` ([4] fp32, B <= 32) is where the head launch, given it as
-    a one-row ``stats``, left the row."""
+    a one-row ``stats``, left the row.
+
+    SGD (MLP3_STEP / MLP3_TAIL_ADAM only; any other kind raises before a launch):
+    ``sgd_momentum`` given (0.0 for plain SGD; None: Adam) makes the tail apply
+    ``torch.optim.SGD`` with ``lr`` / ``weight_decay`` / ``grad_scale`` (and the clip
+    coefficient) as given, ``sgd_dampening`` and ``sgd_nesterov``.  ``exp_avg`` is then the
+    velocity (torch's ``momentum_buffer``, 16-byte aligned; may be None when the momentum is 0,
+    and is never touched then) and ``exp_avg_sq`` is unused (None).  The first optimizer step
+    (``counters[0] <= 1`` after the head's advance) sets the velocity to the gradient."""
+    if sgd_momentum is not None:
+        if kind not in (MLP3_STEP, MLP3_TAIL_ADAM):
+            raise ValueError(f"mlp3_launch: SGD arguments belong to MLP3_STEP / MLP3_TAIL_ADAM, not kind {kind}")
+        if not float(sgd_momentum) >= 0.0:
+            raise ValueError(f"mlp3_launch: sgd_momentum must be >= 0, got {sgd_momentum}")
+        if float(sgd_momentum) != 0.0 and exp_avg is None:
+            raise ValueError("mlp3_launch: SGD with momentum needs the velocity tensor (exp_avg)")
+        if sgd_nesterov and (float(sgd_momentum) <= 0.0 or float(sgd_dampening) != 0.0):
+            raise ValueError("mlp3_launch: Nesterov momentum requires a momentum and zero dampening")
+    elif sgd_dampening or sgd_nesterov:
+        raise ValueError("mlp3_launch: sgd_dampening / sgd_nesterov need sgd_momentum")
     if acc_add or acc_rows or acc_head_row is not None:
         if kind not in (MLP3_TAIL_GRAD, MLP3_TAIL_ACC):
             raise ValueError(f"mlp3_launch: accumulation arguments belong to MLP3_TAIL_GRAD / MLP3_TAIL_ACC, "
@@ -382,6 +404,7 @@ def mlp3_launch(
         [int(v) for v in (dp_ctx or ())], head_part, hand, int(dp_proto), bool(dp_loop), int(repeat),
         clip_part, float(clip_max_norm), clip_out, -1 if clip_nblk is None else int(clip_nblk),
         bool(acc_add), bool(acc_rows), acc_head_row,
+        None if sgd_momentum is None else float(sgd_momentum), float(sgd_dampening), bool(sgd_nesterov),
     )
 
 

@@ -31,6 +31,11 @@ re-designed for MI355X instead of translating PL's DDP loop:
   tail(grad, adding) -> [allreduce] -> [norm partials] -> tail(adam, grad_scale 1/(world K)).
   The window position is a function of ``step_in_epoch``, ``n_batches`` and K alone (no
   device read); the epoch's last window may be short and is still weighted 1/K;
+* ``optimizer="adamw"`` is Adam's kernels with the decoupled decay on every route;
+  ``optimizer="sgd"`` (``momentum`` / ``dampening`` / ``nesterov``, ``torch.optim.SGD``) is
+  applied by SGD instances of the tail kernel: head -> tail at world size 1, else (and
+  under ``clip_norm`` / ``accumulate``) head -> tail(grad | acc) -> [allreduce] -> [norm
+  partials] -> tail(sgd); never one launch, never ``dp_context``;
 * the step's device work can be captured into a hipGraph (``capture``): batch
   cursor, step counter, ring slot and epoch buffer live on the device, so
   replays advance by themselves.
@@ -50,7 +55,7 @@ import torch.distributed as dist
 
 from ..config import get_config
 from ..ops import fused_mlp
-from ..ops.optim import clip_partials, fused_adam_
+from ..ops.optim import clip_partials, fused_adam_, fused_sgd_
 
 log = logging.getLogger(__name__)
 
@@ -117,6 +122,10 @@ class FusedMLPEngine:
         dp_loop: bool = False,
         clip_norm: Optional[float] = None,
         accumulate: int = 1,
+        optimizer: str = "adam",
+        momentum: float = 0.0,
+        dampening: float = 0.0,
+        nesterov: bool = False,
     ):
         """``buffers``: optional external fp32 tensors ``params`` / ``grads`` /
         ``exp_avg`` / ``exp_avg_sq`` (e.g. views of a Trainer's parameter arena,
@@ -141,7 +150,28 @@ class FusedMLPEngine:
         is the epoch's last; every micro-batch's gradient weighs 1 / K, clipping applies to
         the averaged sum, the allreduce runs once per window, ``counters[0]`` advances once
         per window while cursor / ring slot / stats rows advance per micro-batch.  Like
-        ``clip_norm`` it never runs as one launch and does not combine with ``dp_context``."""
+        ``clip_norm`` it never runs as one launch and does not combine with ``dp_context``.
+        ``optimizer``: "adam" (default), "adamw" (decoupled ``weight_decay``; every route,
+        the one-launch step and the in-kernel exchange included) or "sgd" --
+        ``torch.optim.SGD`` with ``momentum`` / ``dampening`` / ``nesterov`` applied by the
+        tail kernel.  SGD never runs as one launch and does not combine with ``dp_context``:
+        world size 1 without clipping or accumulation is head -> tail (two launches), every
+        other combination head -> tail(grad | acc) -> [allreduce] -> [norm partials] ->
+        tail(sgd).  Its velocity is ``momentum_buffer`` (``buffers["momentum_buffer"]`` when
+        external); ``exp_avg`` aliases it and ``exp_avg_sq`` is None."""
+        if optimizer not in ("adam", "adamw", "sgd"):
+            raise ValueError(f"optimizer must be 'adam', 'adamw' or 'sgd', got {optimizer!r}")
+        momentum, dampening, nesterov = float(momentum), float(dampening), bool(nesterov)
+        if optimizer == "sgd":
+            if not momentum >= 0.0:
+                raise ValueError(f"momentum must be >= 0, got {momentum}")
+            if nesterov and (momentum <= 0.0 or dampening != 0.0):
+                raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+            if dp_context is not None:
+                raise ValueError("optimizer='sgd' needs the allreduce route: the in-kernel data-parallel exchange "
+                                 "(dp_context) applies Adam -- pass allreduce= and no dp_context")
+        elif momentum != 0.0 or dampening != 0.0 or nesterov:
+            raise ValueError(f"momentum / dampening / nesterov belong to optimizer='sgd', not {optimizer!r}")
         if isinstance(accumulate, bool) or int(accumulate) != accumulate or int(accumulate) < 1:
             raise ValueError(f"accumulate must be an integer >= 1, got {accumulate!r}")
         accumulate = int(accumulate)
@@ -160,6 +190,10 @@ class FusedMLPEngine:
             raise ValueError("fused MLP engine supports batch sizes 1..256")
         self.L1, self.L2, self.B = int(layer_1), int(layer_2), int(batch_size)
         self.lr, self.betas, self.eps, self.wd = float(lr), tuple(betas), float(eps), float(weight_decay)
+        self.optimizer = optimizer
+        self.sgd = optimizer == "sgd"
+        self.adamw = optimizer == "adamw"
+        self.momentum, self.dampening, self.nesterov = momentum, dampening, nesterov
         self.device = torch.device(device) if device is not None else torch.device("cpu")
         self.native = self.device.type == "cuda"
         self.world_size, self.rank = int(world_size), int(rank)
@@ -175,10 +209,13 @@ class FusedMLPEngine:
         self._owner_masks = None
         n = fused_mlp.mlp_param_count(self.L1, self.L2)
         if buffers is not None:
-            for k in ("params", "grads", "exp_avg", "exp_avg_sq"):
+            names = ("params", "grads", "momentum_buffer") if self.sgd else ("params", "grads", "exp_avg", "exp_avg_sq")
+            for k in names:
                 t = buffers[k]
                 assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n and t.device == self.device, k
-                setattr(self, k, t)
+                setattr(self, "exp_avg" if k == "momentum_buffer" else k, t)
+            if self.sgd:
+                self.exp_avg_sq = None
         else:
             if init_params is None:
                 init_params = fused_mlp.init_mlp_params(self.L1, self.L2, torch.Generator().manual_seed(seed))
@@ -186,8 +223,8 @@ class FusedMLPEngine:
             # padded to 4 floats: the xGMI one-shot allreduce moves 16-byte vectors
             self._grads_padded = torch.zeros((n + 3) // 4 * 4, device=self.device)
             self.grads = self._grads_padded[:n]
-            self.exp_avg = torch.zeros(n, device=self.device)
-            self.exp_avg_sq = torch.zeros(n, device=self.device)
+            self.exp_avg = torch.zeros(n, device=self.device)  # SGD: the velocity (momentum_buffer)
+            self.exp_avg_sq = None if self.sgd else torch.zeros(n, device=self.device)
         self.lr_tensor = torch.full((1,), self.lr, device=self.device)
         self.clip_norm = clip_norm
         self.accumulate = accumulate
@@ -225,9 +262,10 @@ class FusedMLPEngine:
         # showed the step bitwise equal to the two-launch step from a fresh engine in
         # the failing session (docs/one_launch_investigation.md), so the gate is gone.
         # clipping needs the whole gradient between two launches: never one launch;
-        # nor does accumulation (Adam only at a window's close)
+        # nor does accumulation (Adam only at a window's close), nor SGD (the one-launch
+        # kernel applies Adam)
         self.one_launch = (self.B <= fused_mlp.ONE_LAUNCH_MAX_B and os.environ.get("RLA_MLP_ONE_LAUNCH") != "0"
-                           and clip_norm is None and accumulate == 1)
+                           and clip_norm is None and accumulate == 1 and not self.sgd)
         # world size > 1 with the xGMI context: the same one launch, each block
         # exchanging its values with the peers (protocol: self.dp_proto)
         self.dp_proto = "packed"
@@ -290,6 +328,12 @@ class FusedMLPEngine:
         task = torch.cat([w1, b1, w2, b2, w3, b3])  # arena order: W1 B1 W2 B2 W3 B3
         assert task.numel() == fused_mlp.mlp_param_count(L1, L2)
         return (task % world) == rank
+
+    @property
+    def momentum_buffer(self) -> Optional[torch.Tensor]:
+        """SGD's velocity (torch's ``momentum_buffer``, the arena behind ``exp_avg``); None
+        for the Adam engines."""
+        return self.exp_avg if self.sgd else None
 
     def sync_optimizer_state(self) -> None:
         """Owner protocol: every rank's Adam state becomes the owners' (each element's
@@ -529,7 +573,14 @@ class FusedMLPEngine:
                     grads=self.grads, exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq, shadow=self.shadow,
                     dh1t=self.dh1t, xring=self.xring, h1pre=self.h1pre, act=self.act, yring=self.yring,
                     head_part=self.head_part, hand=self.hand, lr=self.lr, betas=self.betas,
-                    eps=self.eps, weight_decay=self.wd, lr_tensor=self.lr_tensor)
+                    eps=self.eps, weight_decay=self.wd, lr_tensor=self.lr_tensor, adamw=self.adamw)
+
+    def _sgd_kw(self) -> dict:
+        """The SGD arguments of the launch that applies the optimizer (MLP3_STEP /
+        MLP3_TAIL_ADAM); empty for the Adam engines."""
+        if not self.sgd:
+            return {}
+        return dict(sgd_momentum=self.momentum, sgd_dampening=self.dampening, sgd_nesterov=self.nesterov)
 
     def prime(self) -> None:
         """Layer-1 pre-activations of the pending batch from the current weights."""
@@ -581,7 +632,8 @@ class FusedMLPEngine:
             if self.clip_norm is not None:
                 clip_partials(self.grads, CLIP_NBLK, out=self.clip_part)
                 clip = dict(clip_part=self.clip_part, clip_max_norm=self.clip_norm, clip_out=self.clip_out)
-            fused_mlp.mlp3_launch(fused_mlp.MLP3_TAIL_ADAM, grad_scale=self._grad_scale, **clip, **kw)
+            fused_mlp.mlp3_launch(fused_mlp.MLP3_TAIL_ADAM, grad_scale=self._grad_scale, **clip, **self._sgd_kw(),
+                                  **kw)
             return
         if not self.native:
             self._reference_step()
@@ -595,10 +647,10 @@ class FusedMLPEngine:
                 clip_partials(self.grads, CLIP_NBLK, out=self.clip_part)
                 fused_mlp.mlp3_launch(fused_mlp.MLP3_TAIL_ADAM, grad_scale=1.0 / self.world_size,
                                       clip_part=self.clip_part, clip_max_norm=self.clip_norm,
-                                      clip_out=self.clip_out, **kw)
+                                      clip_out=self.clip_out, **self._sgd_kw(), **kw)
             elif self.world_size == 1 and not self.dp_loop:
                 kind = fused_mlp.MLP3_STEP1 if self.one_launch else fused_mlp.MLP3_STEP
-                fused_mlp.mlp3_launch(kind, stats=self.stats, **kw)
+                fused_mlp.mlp3_launch(kind, stats=self.stats, **self._sgd_kw(), **kw)
             elif self.dp_ctx is not None:
                 kind = fused_mlp.MLP3_STEP1_DP if self.one_launch_dp else fused_mlp.MLP3_STEP_DP
                 fused_mlp.mlp3_launch(kind, stats=self.stats, grad_scale=1.0 / self.dp_ctx[0],
@@ -610,7 +662,8 @@ class FusedMLPEngine:
                 fused_mlp.mlp3_launch(fused_mlp.MLP3_TAIL_GRAD, stats=self.stats, **kw)  # multi-block head stats
                 if self.allreduce is not None:
                     self.allreduce(self.comm_buffer)
-                fused_mlp.mlp3_launch(fused_mlp.MLP3_TAIL_ADAM, grad_scale=1.0 / self.world_size, **kw)
+                fused_mlp.mlp3_launch(fused_mlp.MLP3_TAIL_ADAM, grad_scale=1.0 / self.world_size,
+                                      **self._sgd_kw(), **kw)
 
     def _reference_step(self, micro: int = 0, closing: bool = True) -> None:
         """fp32 PyTorch step with the device kernels' batch / counter semantics
@@ -618,13 +671,14 @@ class FusedMLPEngine:
         c = self.counters
         cursor, ob = int(c[1]), int(c[4])
         acc = self.accumulate > 1
-        fused = self.world_size == 1 and self.clip_norm is None and not acc
+        # SGD: mlp_train_step leaves the gradient, fused_sgd_ follows below
+        fused = self.world_size == 1 and self.clip_norm is None and not acc and not self.sgd
         fused_mlp.mlp_train_step(
             self.params, self.grads, L1=self.L1, L2=self.L2, B=self.B, labels=self.labels, x_u8=self.x_u8,
             order=self.order[ob], counters=c[:2], n_batches=self.n_batches, exp_avg=self.exp_avg,
             exp_avg_sq=self.exp_avg_sq, stats=self._head_row if acc else self.stats, accumulate_grad=micro > 0,
             apply_adam=fused, advance_step=closing, lr=self.lr,
-            betas=self.betas, eps=self.eps, weight_decay=self.wd, lr_tensor=self.lr_tensor,
+            betas=self.betas, eps=self.eps, weight_decay=self.wd, lr_tensor=self.lr_tensor, adamw=self.adamw,
         )
         c[2] = cursor
         c[3] = int(c[3]) ^ 1
@@ -642,8 +696,14 @@ class FusedMLPEngine:
                 self.allreduce(self.comm_buffer)
             if self.clip_norm is not None:
                 self._reference_clip()
+            if self.sgd:  # first = counters[0] <= 1, the kernels' rule
+                fused_sgd_(self.params, self.grads, self.exp_avg if self.momentum != 0.0 else None, lr=self.lr,
+                           momentum=self.momentum, dampening=self.dampening, weight_decay=self.wd,
+                           nesterov=self.nesterov, grad_scale=self._grad_scale, step=self.counters[0:1],
+                           lr_tensor=self.lr_tensor)
+                return
             fused_adam_(self.params, self.grads, self.exp_avg, self.exp_avg_sq, lr=self.lr, betas=self.betas,
-                        eps=self.eps, weight_decay=self.wd, grad_scale=self._grad_scale,
+                        eps=self.eps, weight_decay=self.wd, grad_scale=self._grad_scale, adamw=self.adamw,
                         step=self.counters[0:1], lr_tensor=self.lr_tensor)
 
     def _reference_clip(self) -> None:
@@ -793,8 +853,20 @@ class FusedMLPEngine:
         return {k: v.detach().cpu().clone() for k, v in fused_mlp.mlp_unpack(self.params, self.L1, self.L2).items()}
 
     def optimizer_state_dict(self) -> Dict:
-        """torch.optim.Adam.state_dict() layout (Lightning checkpoint `optimizer_states`).
-        Collective under the owner protocol (state consolidation)."""
+        """torch.optim.Adam / AdamW / SGD .state_dict() layout (Lightning checkpoint
+        `optimizer_states`).  Collective under the owner protocol (state consolidation)."""
+        if self.sgd:
+            # torch's SGD state: a momentum_buffer per parameter once a step has run (none
+            # without momentum), and no step count
+            names = list(fused_mlp.mlp_unpack(self.params, self.L1, self.L2))
+            state = {}
+            if self.momentum != 0.0 and self.optimizer_steps > 0:
+                buf = fused_mlp.mlp_unpack(self.exp_avg, self.L1, self.L2)
+                state = {i: {"momentum_buffer": buf[k].detach().cpu().clone()} for i, k in enumerate(names)}
+            group = {"lr": self.lr, "momentum": self.momentum, "dampening": self.dampening,
+                     "weight_decay": self.wd, "nesterov": self.nesterov, "maximize": False, "foreach": None,
+                     "differentiable": False, "fused": None, "params": list(range(len(names)))}
+            return {"state": state, "param_groups": [group]}
         self.sync_optimizer_state()
         step = float(self.counters[0].item())
         m = fused_mlp.mlp_unpack(self.exp_avg, self.L1, self.L2)
