@@ -161,6 +161,12 @@ Tensor sumsq(Tensor x) {
   return out;
 }
 
+// launch code -13 of the MLP kernels: the u8 -> bf16 affine map was refused before any launch
+void check_input_affine(int rc, const char* what, double x_scale, double x_shift) {
+  TORCH_CHECK_VALUE(rc != -13, what, ": x_scale must be finite and > 0 and x_shift finite, got x_scale = ", x_scale,
+                    ", x_shift = ", x_shift, " (nothing was launched)");
+}
+
 int64_t mlp_param_count(int64_t L1, int64_t L2) {
   return L1 * 784 + L1 + L2 * L1 + L2 + 10 * L2 + 10;
 }
@@ -171,7 +177,7 @@ void mlp_train_step(optional<Tensor> x_u8, optional<Tensor> x_f32, Tensor labels
                     optional<Tensor> exp_avg_sq, optional<Tensor> stats, bool accumulate_grad,
                     bool apply_adam, bool advance_step, double lr, double beta1, double beta2,
                     double eps, double weight_decay, optional<Tensor> lr_t, bool adamw,
-                    optional<Tensor> stamps) {
+                    optional<Tensor> stamps, double x_scale, double x_shift) {
   TORCH_CHECK(rla::mlp_supported((int)L1, (int)L2), "no fused MLP kernel for layer sizes ", L1, "/", L2);
   TORCH_CHECK(B >= 1, "batch size must be >= 1");
   const int64_t np = mlp_param_count(L1, L2);
@@ -216,7 +222,10 @@ void mlp_train_step(optional<Tensor> x_u8, optional<Tensor> x_f32, Tensor labels
   a.lr_ptr = ptr_or_null<const float>(lr_t, "lr", at::kFloat, 1);
   a.adamw = adamw;
   a.stamps = ptr_or_null<int64_t>(stamps, "stamps", at::kLong, 16);
-  TORCH_CHECK(rla::launch_mlp_train_step(a, cur_stream(params)) == 0, "fused MLP launch failed");
+  a.x_scale = (float)x_scale; a.x_shift = (float)x_shift;
+  const int rc = rla::launch_mlp_train_step(a, cur_stream(params));
+  check_input_affine(rc, "mlp_train_step", x_scale, x_shift);
+  TORCH_CHECK(rc == 0, "fused MLP launch failed");
 }
 
 // v3 pipelined step.  kind: 0 step (head + fused tail), 1 head only (grads),
@@ -233,7 +242,8 @@ void mlp3(int64_t kind, Tensor x_u8, Tensor labels, Tensor order, Tensor counter
           bool adamw, optional<Tensor> stamps, std::vector<int64_t> dp_ctx, optional<Tensor> head_part,
           optional<Tensor> hand, int64_t dp_proto, bool dp_loop, int64_t repeat, optional<Tensor> clip_part,
           double clip_max_norm, optional<Tensor> clip_out, int64_t clip_nblk, bool acc_add, bool acc_rows,
-          optional<Tensor> acc_head_row, optional<double> sgd_momentum, double sgd_dampening, bool sgd_nesterov) {
+          optional<Tensor> acc_head_row, optional<double> sgd_momentum, double sgd_dampening, bool sgd_nesterov,
+          double x_scale, double x_shift) {
   TORCH_CHECK(kind >= 0 && kind <= 8, "mlp3: bad kind ", kind);
   // SGD: refused here, before any launch, wherever it does not belong
   rla::MLP3Sgd sgd{0, 0.f, 0.f, 0};
@@ -333,6 +343,7 @@ void mlp3(int64_t kind, Tensor x_u8, Tensor labels, Tensor order, Tensor counter
   a.lr_ptr = ptr_or_null<const float>(lr_t, "lr", at::kFloat, 1);
   a.adamw = adamw;
   a.stamps = ptr_or_null<int64_t>(stamps, "stamps", at::kLong, 16);
+  a.x_scale = (float)x_scale; a.x_shift = (float)x_shift;
   if (kind == rla::kMLP3StepDP || kind == rla::kMLP3Step1DP) {
     // [world, rank, stride, spin, gen_ptr, err_ptr, region_ptr x world] from the comm engine
     TORCH_CHECK(dp_ctx.size() >= 6 && dp_ctx[0] >= 1 && dp_ctx[0] <= 8 && (int64_t)dp_ctx.size() == 6 + dp_ctx[0],
@@ -412,6 +423,7 @@ void mlp3(int64_t kind, Tensor x_u8, Tensor labels, Tensor order, Tensor counter
   for (int64_t i = 0; i < repeat; ++i)
   {
     const int rc = rla::launch_mlp3(a, (int)kind, st, &clip, &acc, &sgd);
+    check_input_affine(rc, "mlp3", x_scale, x_shift);
     TORCH_CHECK(rc == 0, "fused MLP v3 launch failed (kind ", kind, ", code ", rc, ")");
   }
 }
@@ -450,7 +462,8 @@ void mlp_adam(Tensor params, Tensor grads, Tensor exp_avg, Tensor exp_avg_sq, Te
 }
 
 void mlp_eval(optional<Tensor> x_u8, optional<Tensor> x_f32, Tensor labels, optional<Tensor> index,
-              int64_t B, int64_t L1, int64_t L2, Tensor params, optional<Tensor> logits, Tensor out) {
+              int64_t B, int64_t L1, int64_t L2, Tensor params, optional<Tensor> logits, Tensor out,
+              double x_scale, double x_shift) {
   TORCH_CHECK(rla::mlp_supported((int)L1, (int)L2), "no fused MLP kernel for layer sizes ", L1, "/", L2);
   check_dev(params, "params", at::kFloat);
   TORCH_CHECK(params.numel() == mlp_param_count(L1, L2), "param arena size mismatch");
@@ -480,7 +493,10 @@ void mlp_eval(optional<Tensor> x_u8, optional<Tensor> x_f32, Tensor labels, opti
   a.logits = ptr_or_null<float>(logits, "logits", at::kFloat, B * 10);
   a.out = out.data_ptr<float>();
   a.partials = partials ? 1 : 0;
-  TORCH_CHECK(rla::launch_mlp_eval(a, cur_stream(params)) == 0, "fused MLP eval launch failed");
+  a.x_scale = (float)x_scale; a.x_shift = (float)x_shift;
+  const int rc = rla::launch_mlp_eval(a, cur_stream(params));
+  check_input_affine(rc, "mlp_eval", x_scale, x_shift);
+  TORCH_CHECK(rc == 0, "fused MLP eval launch failed");
 }
 
 // ---- fused BatchNorm(+ReLU)(+residual add) over NHWC bf16 activations --------------
@@ -1125,8 +1141,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("grads"), py::arg("exp_avg"), py::arg("exp_avg_sq"), py::arg("stats"),
         py::arg("accumulate_grad"), py::arg("apply_adam"), py::arg("advance_step"), py::arg("lr"),
         py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"), py::arg("lr_t"),
-        py::arg("adamw"), py::arg("stamps") = py::none());
-  m.def("mlp_eval", &mlp_eval, "fused MNIST-MLP forward + NLL/accuracy");
+        py::arg("adamw"), py::arg("stamps") = py::none(), py::arg("x_scale") = (double)rla::kMLPXScale,
+        py::arg("x_shift") = 0.0);
+  m.def("mlp_eval", &mlp_eval, "fused MNIST-MLP forward + NLL/accuracy (u8 mode: pixel = fma(u8, x_scale, x_shift))",
+        py::arg("x_u8"), py::arg("x_f32"), py::arg("labels"), py::arg("index"), py::arg("B"), py::arg("L1"),
+        py::arg("L2"), py::arg("params"), py::arg("logits"), py::arg("out"),
+        py::arg("x_scale") = (double)rla::kMLPXScale, py::arg("x_shift") = 0.0);
   m.def("mlp3", &mlp3, "fused MNIST-MLP step v3 (pipelined layer 1): kind 0 step, 1 head, 2 tail-grad, "
         "3 tail-adam, 4 prime, 5 step with the in-kernel xGMI exchange, 6 one-launch step (B <= 32), "
         "8 tail-acc (gradient accumulation: a micro-batch inside its window); sgd_momentum: SGD in the tail of 0 / 3",
@@ -1140,7 +1160,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("clip_part") = py::none(), py::arg("clip_max_norm") = 0.0, py::arg("clip_out") = py::none(),
         py::arg("clip_nblk") = -1, py::arg("acc_add") = false, py::arg("acc_rows") = false,
         py::arg("acc_head_row") = py::none(), py::arg("sgd_momentum") = py::none(), py::arg("sgd_dampening") = 0.0,
-        py::arg("sgd_nesterov") = false);
+        py::arg("sgd_nesterov") = false, py::arg("x_scale") = (double)rla::kMLPXScale, py::arg("x_shift") = 0.0);
   m.def("dp_pack_roundtrip", &dp_pack_roundtrip, "packed DP exchange wire form of fp32 pairs, encoded + decoded");
   m.def("mlp3_hand_words", [](int64_t l1, int64_t l2) { return rla::mlp3_hand_words((int)l1, (int)l2); });
   m.def("mlp3_hand_layout", []() {

@@ -3,6 +3,7 @@
 // free of torch types lets the .hip files compile with hipcc alone.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include <stdint.h>
 
 #include <functional>
@@ -159,9 +160,19 @@ void launch_conv1x1_bn_bwd(const uint16_t* dy1, const uint16_t* wt, uint16_t* d,
 // ---------------------------------------------------------------------------
 // Fused MNIST-MLP training step (784 -> L1 -> L2 -> 10, ReLU, log_softmax+NLL).
 // ---------------------------------------------------------------------------
+// The u8 -> bf16 conversion of every MLP kernel: bf16(fmaf((float)u8, x_scale, x_shift)).
+// Defaults (ToTensor alone): kMLPXScale, 0 -- bitwise the former u8 * (1.0f / 255.0f) for
+// every byte.  A single-channel Normalize(mean, std) folds in as x_scale = 1 / (255 std),
+// x_shift = -mean / std.  Padded rows stay zero, not x_shift.
+constexpr float kMLPXScale = (float)(1.0 / 255.0);
+// what every launch accepts: a finite positive scale, a finite shift
+inline bool mlp_input_affine_ok(float x_scale, float x_shift) {
+  return x_scale > 0.f && x_scale <= FLT_MAX && x_shift >= -FLT_MAX && x_shift <= FLT_MAX;  // NaN fails every test
+}
+
 struct MLPStepArgs {
   // input: either a uint8 dataset gathered through `order` (GPU-resident data,
-  // pixels scaled by 1/255 in-kernel) or a dense fp32 batch [B, 784].
+  // pixels mapped by fmaf(u8, x_scale, x_shift) in-kernel) or a dense fp32 batch [B, 784].
   const uint8_t* x_u8;      // [N_data, 784] or null
   const float* x_f32;       // [B, 784] or null
   const int64_t* labels;    // [N_data] (u8 mode) or [B] (f32 mode)
@@ -186,6 +197,7 @@ struct MLPStepArgs {
   // v2 (two-kernel) step only:
   uint16_t* shadow;         // bf16 weight shadows (row-major copy + W2^T + W3^T), see mlp_shadow_layout
   uint16_t* dh1t;           // scratch [L1, round_up(B, 32)] bf16: dH1^T handed from head to W1 kernel
+  float x_scale, x_shift;   // u8 mode: pixel = fmaf(u8, x_scale, x_shift) (x_f32 mode ignores them)
 };
 
 // bf16 shadow layout (elements): [0, np) row-major copy of the fp32 arena,
@@ -221,6 +233,7 @@ struct MLPEvalArgs {
   float* out;               // [2]: += sum of NLL, += correct count
                             // (partials: [ceil(B/32), 2] per-32-row-chunk sums, overwritten)
   int partials;
+  float x_scale, x_shift;   // u8 mode: pixel = fmaf(u8, x_scale, x_shift) (x_f32 mode ignores them)
 };
 
 // v3 (cross-step pipelined layer 1, resident uint8 dataset only); see mlp_step3.hip.
@@ -275,6 +288,9 @@ struct MLP3Args {
   // into last_step (mlp3_hand_layout); nullptr (two-launch kinds only): nothing is counted.
   unsigned long long* hand;
   int64_t hand_spin;
+  // pixel = fmaf(u8, x_scale, x_shift) wherever a kernel gathers a batch (appended: every
+  // other field keeps its kernarg offset)
+  float x_scale, x_shift;
 };
 enum MLP3Kind { kMLP3Step = 0, kMLP3Head = 1, kMLP3TailGrad = 2, kMLP3TailAdam = 3, kMLP3Prime = 4,
                 kMLP3StepDP = 5, kMLP3Step1 = 6, kMLP3Step1DP = 7, kMLP3TailAcc = 8 };
@@ -341,7 +357,8 @@ struct MLP3Sgd {
 // Returns 0, or a negative code before any launch: -8 misplaced clip arguments, -10 MLP3Acc
 // flags on a kind other than TailGrad / TailAcc (or rows without a row source), -11 TailAcc
 // with clip arguments, -12 MLP3Sgd on a kind other than Step / TailAdam (or momentum without
-// a velocity buffer).
+// a velocity buffer), -13 a non-finite or non-positive x_scale or a non-finite x_shift, -14
+// Step1DP with a pixel map other than the default (StepDP serves a normalised dataset).
 int launch_mlp3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip* clip = nullptr,
                 const MLP3Acc* acc = nullptr, const MLP3Sgd* sgd = nullptr);
 
@@ -350,7 +367,8 @@ int mlp3_h1_copies(int L1);  // H1pre copies per ring slot (mlp_step3.hip H1Copi
 // the packed DP exchange's wire form of fp32 pairs, encoded and decoded (tests)
 int dp_pack_roundtrip(const float* x, float* y, int64_t n, int tag, hipStream_t stream);
 
-// returns 0 on success, -1 if (L1, L2) has no compiled instantiation
+// returns 0 on success, -1 if (L1, L2) has no compiled instantiation, -13 (before any launch,
+// u8 mode) for a non-finite or non-positive x_scale or a non-finite x_shift
 int launch_mlp_train_step(const MLPStepArgs& a, hipStream_t stream);
 int launch_mlp_eval(const MLPEvalArgs& a, hipStream_t stream);
 bool mlp_supported(int L1, int L2);

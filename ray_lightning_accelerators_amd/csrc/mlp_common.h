@@ -123,5 +123,20 @@ __device__ __forceinline__ void u8x16_to_bf16(const uint4 v, bf16x8& lo, bf16x8&
   }
 }
 
+// The same with the pixel map as two run-time scalars: bf16(fmaf(u8, x_scale, x_shift)) --
+// ToTensor (x_scale = 1/255, x_shift = 0: bitwise the product above for every byte) with an
+// optional single-channel Normalize folded in (kernels.h kMLPXScale).
+__device__ __forceinline__ void u8x16_to_bf16(const uint4 v, bf16x8& lo, bf16x8& hi, float x_scale,
+                                              float x_shift) {
+  const uint32_t wd[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    lo[j] = (__bf16)fmaf((float)((wd[0] >> (8 * j)) & 0xffu), x_scale, x_shift);
+    lo[4 + j] = (__bf16)fmaf((float)((wd[1] >> (8 * j)) & 0xffu), x_scale, x_shift);
+    hi[j] = (__bf16)fmaf((float)((wd[2] >> (8 * j)) & 0xffu), x_scale, x_shift);
+    hi[4 + j] = (__bf16)fmaf((float)((wd[3] >> (8 * j)) & 0xffu), x_scale, x_shift);
+  }
+}
+
 }  // namespace mlp
 }  // namespace rla

@@ -113,12 +113,14 @@ __device__ __forceinline__ bf16x4 tr_read(const __bf16* p) {
 
 // -------------------------------------------------------------------------
 // Phase: stage the batch chunk's rows into LDS as bf16 (u8 pixels / 255, or
-// fp32 features), zero the K padding, fetch labels.
+// fp32 features), zero the K padding, fetch labels.  NORM (u8 only): the pixel map is
+// fmaf(u8, x_scale, x_shift) -- a dataset with a Normalize (kernels.h kMLPXScale); its own
+// instances, so the default ones keep the constant product and the registers they had.
 // -------------------------------------------------------------------------
-template <int BC, int L1, bool U8>
+template <int BC, int L1, bool U8, bool NORM = false>
 __device__ __forceinline__ void stage_inputs(const Smem& s, const uint8_t* x_u8, const float* x_f32,
                                              const int64_t* labels, const int64_t* idx, int row0,
-                                             int nvalid) {
+                                             int nvalid, float x_scale, float x_shift) {
   const int tid = threadIdx.x;
   for (int i = tid; i < BC * L1; i += kThreads) s.acc1[i] = 0.f;
   if constexpr (U8) {
@@ -135,10 +137,20 @@ __device__ __forceinline__ void stage_inputs(const Smem& s, const uint8_t* x_u8,
       constexpr float inv255 = 1.0f / 255.0f;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        lo[j] = (__bf16)((float)((wds[0] >> (8 * j)) & 0xffu) * inv255);
-        lo[4 + j] = (__bf16)((float)((wds[1] >> (8 * j)) & 0xffu) * inv255);
-        hi[j] = (__bf16)((float)((wds[2] >> (8 * j)) & 0xffu) * inv255);
-        hi[4 + j] = (__bf16)((float)((wds[3] >> (8 * j)) & 0xffu) * inv255);
+        if constexpr (NORM) {
+          lo[j] = (__bf16)fmaf((float)((wds[0] >> (8 * j)) & 0xffu), x_scale, x_shift);
+          lo[4 + j] = (__bf16)fmaf((float)((wds[1] >> (8 * j)) & 0xffu), x_scale, x_shift);
+          hi[j] = (__bf16)fmaf((float)((wds[2] >> (8 * j)) & 0xffu), x_scale, x_shift);
+          hi[4 + j] = (__bf16)fmaf((float)((wds[3] >> (8 * j)) & 0xffu), x_scale, x_shift);
+        } else {
+          lo[j] = (__bf16)((float)((wds[0] >> (8 * j)) & 0xffu) * inv255);
+          lo[4 + j] = (__bf16)((float)((wds[1] >> (8 * j)) & 0xffu) * inv255);
+          hi[j] = (__bf16)((float)((wds[2] >> (8 * j)) & 0xffu) * inv255);
+          hi[4 + j] = (__bf16)((float)((wds[3] >> (8 * j)) & 0xffu) * inv255);
+        }
+      }
+      if constexpr (NORM) {
+        if (r >= nvalid) { lo = zero8(); hi = zero8(); }  // padded rows stay zero, not x_shift
       }
       __bf16* dst = s.X + r * kXS + cc * 16;
       *reinterpret_cast<bf16x8*>(dst) = lo;
@@ -513,7 +525,7 @@ __device__ __forceinline__ void backward(const Smem& s, const GradSink& sink, fl
   RLA_STAMP(s, 9);
 }
 
-template <int BC, int L1, int L2, bool U8>
+template <int BC, int L1, int L2, bool U8, bool NORM = false>
 __global__ __launch_bounds__(kThreads) void mlp_train_kernel(MLPStepArgs a) {
   using C = Cfg<BC, L1, L2>;
   __shared__ __attribute__((aligned(16))) char smem[C::total];
@@ -543,7 +555,7 @@ __global__ __launch_bounds__(kThreads) void mlp_train_kernel(MLPStepArgs a) {
   for (int c = 0; c < nchunks; ++c) {
     const int row0 = c * BC;
     const int nvalid = min(BC, a.B - row0);
-    stage_inputs<BC, L1, U8>(s, a.x_u8, a.x_f32, a.labels, idx, row0, nvalid);
+    stage_inputs<BC, L1, U8, NORM>(s, a.x_u8, a.x_f32, a.labels, idx, row0, nvalid, a.x_scale, a.x_shift);
     __syncthreads();
     RLA_STAMP(s, 1);
     forward<BC, L1, L2>(s, a.params);
@@ -577,7 +589,7 @@ __global__ __launch_bounds__(kThreads) void mlp_train_kernel(MLPStepArgs a) {
 // workgroups, one wave of the chip).  ``partials`` mode writes each chunk's
 // (sum NLL, #correct) to out[2c..2c+1] -- no atomics, so the epoch's sums are
 // reduced deterministically by the caller; otherwise one atomic pair per block.
-template <int BC, int L1, int L2, bool U8>
+template <int BC, int L1, int L2, bool U8, bool NORM = false>
 __global__ __launch_bounds__(kThreads) void mlp_eval_kernel(MLPEvalArgs a) {
   using C = Cfg<BC, L1, L2>;
   __shared__ __attribute__((aligned(16))) char smem[C::total];
@@ -587,7 +599,7 @@ __global__ __launch_bounds__(kThreads) void mlp_eval_kernel(MLPEvalArgs a) {
   for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
     const int row0 = c * BC;
     const int nvalid = min(BC, a.B - row0);
-    stage_inputs<BC, L1, U8>(s, a.x_u8, a.x_f32, a.labels, a.index, row0, nvalid);
+    stage_inputs<BC, L1, U8, NORM>(s, a.x_u8, a.x_f32, a.labels, a.index, row0, nvalid, a.x_scale, a.x_shift);
     __syncthreads();
     forward<BC, L1, L2>(s, a.params);
     float l = 0.f, k = 0.f;
@@ -625,6 +637,9 @@ __global__ __launch_bounds__(kThreads) void mlp_eval_kernel(MLPEvalArgs a) {
   }
 }
 
+// a pixel map other than ToTensor's: the NORM instances
+inline bool input_normalized(float x_scale, float x_shift) { return x_scale != kMLPXScale || x_shift != 0.f; }
+
 template <int BC, int L1, int L2>
 constexpr bool fits() {
   return Cfg<BC, L1, L2>::total + 256 <= 160 * 1024;
@@ -633,15 +648,18 @@ constexpr bool fits() {
 template <int L1, int L2>
 int dispatch_train(const MLPStepArgs& a, hipStream_t stream) {
   const bool u8 = a.x_u8 != nullptr;
+  const bool norm = u8 && input_normalized(a.x_scale, a.x_shift);
   const bool big = a.B > 32;
   if constexpr (fits<64, L1, L2>()) {
     if (big) {
-      if (u8) hipLaunchKernelGGL((mlp_train_kernel<64, L1, L2, true>), dim3(1), dim3(kThreads), 0, stream, a);
+      if (norm) hipLaunchKernelGGL((mlp_train_kernel<64, L1, L2, true, true>), dim3(1), dim3(kThreads), 0, stream, a);
+      else if (u8) hipLaunchKernelGGL((mlp_train_kernel<64, L1, L2, true>), dim3(1), dim3(kThreads), 0, stream, a);
       else hipLaunchKernelGGL((mlp_train_kernel<64, L1, L2, false>), dim3(1), dim3(kThreads), 0, stream, a);
       return 0;
     }
   }
-  if (u8) hipLaunchKernelGGL((mlp_train_kernel<32, L1, L2, true>), dim3(1), dim3(kThreads), 0, stream, a);
+  if (norm) hipLaunchKernelGGL((mlp_train_kernel<32, L1, L2, true, true>), dim3(1), dim3(kThreads), 0, stream, a);
+  else if (u8) hipLaunchKernelGGL((mlp_train_kernel<32, L1, L2, true>), dim3(1), dim3(kThreads), 0, stream, a);
   else hipLaunchKernelGGL((mlp_train_kernel<32, L1, L2, false>), dim3(1), dim3(kThreads), 0, stream, a);
   return 0;
 }
@@ -653,7 +671,9 @@ int dispatch_eval(const MLPEvalArgs& a, hipStream_t stream) {
   // partials: one block per chunk (every chunk owns its output pair); atomics: a
   // grid-stride over at most one block per CU
   const int grid = a.partials ? nchunks : (nchunks < 256 ? nchunks : 256);
-  if (u8) hipLaunchKernelGGL((mlp_eval_kernel<32, L1, L2, true>), dim3(grid), dim3(kThreads), 0, stream, a);
+  if (u8 && input_normalized(a.x_scale, a.x_shift))
+    hipLaunchKernelGGL((mlp_eval_kernel<32, L1, L2, true, true>), dim3(grid), dim3(kThreads), 0, stream, a);
+  else if (u8) hipLaunchKernelGGL((mlp_eval_kernel<32, L1, L2, true>), dim3(grid), dim3(kThreads), 0, stream, a);
   else hipLaunchKernelGGL((mlp_eval_kernel<32, L1, L2, false>), dim3(grid), dim3(kThreads), 0, stream, a);
   return 0;
 }
@@ -673,6 +693,7 @@ bool mlp_supported(int L1, int L2) {
 }
 
 int launch_mlp_train_step(const MLPStepArgs& a, hipStream_t stream) {
+  if (a.x_u8 && !mlp_input_affine_ok(a.x_scale, a.x_shift)) return -13;
 #define RLA_CASE(a1, a2) if (a.L1 == a1 && a.L2 == a2) return dispatch_train<a1, a2>(a, stream);
   RLA_MLP_SHAPES(RLA_CASE)
 #undef RLA_CASE
@@ -680,6 +701,7 @@ int launch_mlp_train_step(const MLPStepArgs& a, hipStream_t stream) {
 }
 
 int launch_mlp_eval(const MLPEvalArgs& a, hipStream_t stream) {
+  if (a.x_u8 && !mlp_input_affine_ok(a.x_scale, a.x_shift)) return -13;
   if (a.B <= 0) return 0;
 #define RLA_CASE(a1, a2) if (a.L1 == a1 && a.L2 == a2) return dispatch_eval<a1, a2>(a, stream);
   RLA_MLP_SHAPES(RLA_CASE)

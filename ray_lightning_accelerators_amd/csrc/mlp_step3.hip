@@ -171,7 +171,8 @@ __device__ __forceinline__ void gather_tile(const MLP3Args& a, int kt, int64_t o
   __bf16* dst = reinterpret_cast<__bf16*>(a.xring) + (dst_slot * kTiles + kt) * (int64_t)Bp * 16;
   for (int b = tid; b < Bp; b += nthreads) {
     bf16x8 lo = zero8(), hi = zero8();
-    if (b < B) u8x16_to_bf16(*reinterpret_cast<const uint4*>(a.x_u8 + idx[b] * kD + kt * 16), lo, hi);
+    if (b < B)
+      u8x16_to_bf16(*reinterpret_cast<const uint4*>(a.x_u8 + idx[b] * kD + kt * 16), lo, hi, a.x_scale, a.x_shift);
     *reinterpret_cast<bf16x8*>(dst + b * 16) = lo;
     *reinterpret_cast<bf16x8*>(dst + b * 16 + 8) = hi;
   }
@@ -1838,7 +1839,8 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
       for (int b = tid; b < Bp; b += NT) a.yring[slot * Bp + b] = b < B ? (int)a.labels[idx[b]] : -1;
     for (int b = tid; b < Bp; b += NT) {
       bf16x8 lo = zero8(), hi = zero8();
-      if (b < B) u8x16_to_bf16(*reinterpret_cast<const uint4*>(a.x_u8 + idx[b] * kD + kt * 16), lo, hi);
+      if (b < B)
+        u8x16_to_bf16(*reinterpret_cast<const uint4*>(a.x_u8 + idx[b] * kD + kt * 16), lo, hi, a.x_scale, a.x_shift);
       *reinterpret_cast<bf16x8*>(sXn + b * kXSS) = lo;
       *reinterpret_cast<bf16x8*>(sXn + b * kXSS + 8) = hi;
       *reinterpret_cast<bf16x8*>(xr_next + b * 16) = lo;
@@ -2053,7 +2055,12 @@ __device__ __forceinline__ void one_wait_acks(const MLP3Args& a, const int64_t* 
 // PROBE: the phase stamps (scripts/dp_phase_probe.py, mlp_phase_probe.py) exist only in
 // the probe instances, which dispatch3 picks when a.stamps is set; in the production
 // instances no stamp, no branch on a.stamps and no exec mask saved around one is compiled.
-template <int L1, int L2, int DPP, int NW = 8, bool PROBE = false>
+// NORM: the next batch's pixels go through fmaf(u8, a.x_scale, a.x_shift) (a dataset with a
+// Normalize) and the two scalars join the kernarg batch; the default instances keep the
+// constant u8 * (1/255) and never read them -- two more pinned SGPRs cost every instance two
+// to seven further SGPR spills across the head pass (profiles/r17_real_mnist), so the
+// datasets without a Normalize run the instruction stream they ran before.
+template <int L1, int L2, int DPP, int NW = 8, bool PROBE = false, bool NORM = false>
 __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args ka) {
   constexpr bool DP = DPP >= 0;
   using C = typename One<L1, L2>::C;
@@ -2090,6 +2097,7 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args ka) {
                  "+s"(a.n_batches), "+s"(a.B), "+s"(a.advance_step), "+s"(a.lr), "+s"(a.beta1), "+s"(a.beta2),
                  "+s"(a.eps), "+s"(a.weight_decay), "+s"(a.adamw), "+s"(g_dp_err));
   if constexpr (DP) asm volatile("" : "+s"(g_dp_gen));
+  if constexpr (NORM) asm volatile("" : "+s"(a.x_scale), "+s"(a.x_shift));  // same request: nothing waited yet
   a.counters = (int64_t*)g_counters, a.hand = (unsigned long long*)g_hand, a.lr_ptr = (const float*)g_lr_ptr;
   a.params = (float*)g_params, a.exp_avg = (float*)g_exp_avg, a.exp_avg_sq = (float*)g_exp_avg_sq;
   a.shadow = (uint16_t*)g_shadow, a.h1pre = (int*)g_h1pre, a.yring = (int*)g_yring;
@@ -2271,7 +2279,10 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args ka) {
         yn = (int)*reinterpret_cast<const int64_t*>(raw + 1024 + 8 * xb);
       }
       bf16x8 lo = zero8(), hi = zero8();
-      if (xb < B) u8x16_to_bf16(xn, lo, hi);
+      if (xb < B) {
+        if constexpr (NORM) u8x16_to_bf16(xn, lo, hi, a.x_scale, a.x_shift);
+        else u8x16_to_bf16(xn, lo, hi);
+      }
       *reinterpret_cast<bf16x8*>(sXn + xb * kXSS) = lo;
       *reinterpret_cast<bf16x8*>(sXn + xb * kXSS + 8) = hi;
       __bf16* nx = XR + ((slot ^ 1) * kTiles + kt) * tile_elems + xb * 16;
@@ -2400,8 +2411,15 @@ template <int L1, int L2>
 int dispatch3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip& clip, const MLP3Acc& acc,
               const MLP3Sgd& sgd) {
   constexpr int kOneGrid = 1 + kTiles + One<L1, L2>::NSMALL;
+  // a pixel map other than ToTensor's: the NORM instance of the one-launch step (world size 1)
+  const bool norm = a.x_scale != kMLPXScale || a.x_shift != 0.f;
   if (kind == kMLP3Step1) {
     if (a.B > 32 || !a.hand || kOneGrid > 256) return -5;
+    if (norm) {
+      if (a.stamps) return -9;  // no probe instance
+      hipLaunchKernelGGL((mlp3_one_kernel<L1, L2, -1, 8, false, true>), dim3(kOneGrid), dim3(kThreads), 0, stream, a);
+      return 0;
+    }
     if (a.stamps) {
       if constexpr (kProbePlain<L1, L2>)
         hipLaunchKernelGGL((mlp3_one_kernel<L1, L2, -1, 8, true>), dim3(kOneGrid), dim3(kThreads), 0, stream, a);
@@ -2413,6 +2431,7 @@ int dispatch3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip& c
     return 0;
   }
   if (kind == kMLP3Step1DP) {
+    if (norm) return -14;  // no NORM instance with an exchange: the two-launch StepDP serves it
     // granule exchange only (the flag protocols stay on the two-launch StepDP)
     if (a.B > 32 || !a.hand || kOneGrid > kDpMaxBlocks || a.dp_world < 1 || a.dp_world > kXgmiMaxRanks ||
         !a.dp_gen || !a.dp_err || a.dp_proto < 0 || a.dp_proto > 2)
@@ -2516,6 +2535,7 @@ MLP3AdamCacheLayout mlp3_adam_cache_layout() { return {kHandAdamStep, kHandAdamB
 int launch_mlp3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip* clip_in, const MLP3Acc* acc_in,
                 const MLP3Sgd* sgd_in) {
   if (a.B > kBMax || a.B < 1) return -2;
+  if (!mlp_input_affine_ok(a.x_scale, a.x_shift)) return -13;
   // SGD belongs to the two kinds whose tail applies the optimizer outside the one-launch
   // kernel and the in-kernel exchange
   MLP3Sgd sgd{0, 0.f, 0.f, 0};

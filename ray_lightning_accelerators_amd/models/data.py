@@ -1,4 +1,6 @@
-"""Synthetic, MNIST-shaped data (no downloads are possible on this platform).
+"""MNIST-shaped data: a synthetic generator (no downloads are possible on this platform)
+and a reader of real MNIST's IDX files (``read_idx`` / ``IdxMNIST``) with the two tensor
+transforms that go with them (``Normalize`` / ``Compose``).
 
 ``synthetic_mnist`` produces uint8 28x28 images of a *learnable but noisy*
 10-class task (overlapping class-conditional blob prototypes, per-sample
@@ -10,10 +12,12 @@ in the dataset's ``__getitem__`` on CPU or inside the fused kernel on GPU.
 """
 from __future__ import annotations
 
+import gzip
 import math
 import os
+import struct
 import tempfile
-from typing import Optional, Tuple
+from typing import Callable, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -130,8 +134,8 @@ def _generate(n: int, seed: int, noise: float, jitter: int, blob_sd: float = 0.8
     return (res.clamp(0, 1) * 255).round().to(torch.uint8).reshape(n, IMG * IMG), labels
 
 
-def _synthetic_mnist_from_spec(n: int, seed: int, train: bool) -> "SyntheticMNIST":
-    return SyntheticMNIST(n, seed, train)
+def _synthetic_mnist_from_spec(n: int, seed: int, train: bool, transform=None) -> "SyntheticMNIST":
+    return SyntheticMNIST(n, seed, train, transform=transform)
 
 
 class SyntheticMNIST(Dataset):
@@ -141,10 +145,12 @@ class SyntheticMNIST(Dataset):
     data module that carries it to a worker ships ~100 bytes instead of 47 MB
     (measured: 70 ms per Tune trial, profiles/r3_tune), and the worker loads the
     arrays from its process memo / the disk cache.  Modified arrays (replaced or
-    changed in place) pickle by value."""
+    changed in place) pickle by value.  ``transform`` (e.g. ``Normalize``) is applied to the
+    float image in ``__getitem__`` and travels with the spec."""
 
-    def __init__(self, n: int = 60000, seed: int = 0, train: bool = True):
+    def __init__(self, n: int = 60000, seed: int = 0, train: bool = True, transform: Optional[Callable] = None):
         self._spec = (n, seed, train)
+        self.transform = transform
         self.images, self.targets = synthetic_mnist(n, seed=seed if train else seed + 1)
         self._stamp = self._fingerprint()
 
@@ -153,14 +159,140 @@ class SyntheticMNIST(Dataset):
 
     def __reduce__(self):
         if getattr(self, "_stamp", None) is not None and self._fingerprint() == self._stamp:
-            return _synthetic_mnist_from_spec, self._spec
+            return _synthetic_mnist_from_spec, (*self._spec, self.transform)
         return super().__reduce__()
 
     def __len__(self) -> int:
         return self.targets.numel()
 
     def __getitem__(self, i):
-        return self.images[i].view(1, IMG, IMG).float() / 255.0, int(self.targets[i])
+        x = self.images[i].view(1, IMG, IMG).float() / 255.0
+        if self.transform is not None:
+            x = self.transform(x)
+        return x, int(self.targets[i])
+
+
+# ---------------------------------------------------------------------------
+# Real MNIST: the IDX files as distributed (and as torchvision lays them out)
+# ---------------------------------------------------------------------------
+IDX_IMAGES, IDX_LABELS = 0x00000803, 0x00000801  # unsigned byte, 3 / 1 dimensions
+
+
+def read_idx(path: str) -> torch.Tensor:
+    """One MNIST IDX file, plain or ``.gz``: images (magic 0x00000803, ``n x 28 x 28``) as
+    uint8 ``[n, 28, 28]``, labels (magic 0x00000801) as uint8 ``[n]``.  Any other magic or
+    image size, a truncated file and trailing bytes raise ``ValueError``."""
+    opener = gzip.open if str(path).endswith(".gz") else open
+    with opener(path, "rb") as f:
+        raw = f.read()
+    if len(raw) < 8:
+        raise ValueError(f"{path}: truncated IDX header ({len(raw)} bytes)")
+    magic, n = struct.unpack(">II", raw[:8])
+    if magic == IDX_LABELS:
+        head, shape = 8, (n,)
+    elif magic == IDX_IMAGES:
+        if len(raw) < 16:
+            raise ValueError(f"{path}: truncated IDX header ({len(raw)} bytes)")
+        rows, cols = struct.unpack(">II", raw[8:16])
+        if (rows, cols) != (IMG, IMG):
+            raise ValueError(f"{path}: images are {rows} x {cols}, expected {IMG} x {IMG}")
+        head, shape = 16, (n, IMG, IMG)
+    else:
+        raise ValueError(f"{path}: bad IDX magic 0x{magic:08x} (expected 0x{IDX_IMAGES:08x} images or "
+                         f"0x{IDX_LABELS:08x} labels)")
+    want = head + math.prod(shape)
+    if len(raw) != want:
+        raise ValueError(f"{path}: {len(raw)} bytes, the header announces {want} "
+                         f"({'truncated' if len(raw) < want else 'over-long'} file)")
+    return torch.from_numpy(np.frombuffer(raw, dtype=np.uint8, offset=head).reshape(shape).copy())
+
+
+def idx_files(root: str, train: bool = True) -> Optional[Tuple[str, str]]:
+    """(images, labels) paths of one MNIST split under ``root``: torchvision's
+    ``<root>/MNIST/raw/`` first, then ``root`` itself; plain before ``.gz``.  None when
+    either file is missing."""
+    stem = "train" if train else "t10k"
+    for d in (os.path.join(str(root), "MNIST", "raw"), str(root)):
+        found = []
+        for name in (f"{stem}-images-idx3-ubyte", f"{stem}-labels-idx1-ubyte"):
+            hit = next((os.path.join(d, name + ext) for ext in ("", ".gz")
+                        if os.path.isfile(os.path.join(d, name + ext))), None)
+            if hit is None:
+                break
+            found.append(hit)
+        if len(found) == 2:
+            return found[0], found[1]
+    return None
+
+
+class IdxMNIST(Dataset):
+    """Real MNIST from its IDX files, in torchvision's layout: ``.data`` uint8 ``[N, 28, 28]``,
+    ``.targets`` int64 ``[N]``, ``.transform`` / ``.target_transform``.  ``__getitem__``
+    yields ``(float [1, 28, 28] = u8 / 255, int)`` -- ToTensor is built in -- and then applies
+    ``transform`` (tensor callables such as ``Normalize``)."""
+
+    def __init__(self, root: str, train: bool = True, transform: Optional[Callable] = None,
+                 target_transform: Optional[Callable] = None):
+        files = idx_files(root, train)
+        if files is None:
+            stem = "train" if train else "t10k"
+            raise FileNotFoundError(f"no {stem}-images-idx3-ubyte[.gz] / {stem}-labels-idx1-ubyte[.gz] under "
+                                    f"{os.path.join(str(root), 'MNIST', 'raw')} or {root}")
+        self.root, self.train = str(root), bool(train)
+        self.transform, self.target_transform = transform, target_transform
+        self.data = read_idx(files[0])
+        labels = read_idx(files[1])
+        if self.data.dim() != 3 or labels.dim() != 1:
+            raise ValueError(f"{files[0]} / {files[1]}: expected an image file and a label file")
+        if self.data.size(0) != labels.numel():
+            raise ValueError(f"{files[0]} holds {self.data.size(0)} images, {files[1]} {labels.numel()} labels")
+        self.targets = labels.to(torch.int64)
+
+    def __len__(self) -> int:
+        return self.targets.numel()
+
+    def __getitem__(self, i):
+        x = self.data[i].view(1, IMG, IMG).float() / 255.0
+        y = int(self.targets[i])
+        if self.transform is not None:
+            x = self.transform(x)
+        if self.target_transform is not None:
+            y = self.target_transform(y)
+        return x, y
+
+
+class Normalize:
+    """``(x - mean) / std`` per channel of a float tensor ``[C, H, W]`` (torchvision's
+    ``transforms.Normalize`` for tensors; torchvision is not a dependency)."""
+
+    def __init__(self, mean: Sequence[float], std: Sequence[float]):
+        self.mean = tuple(float(v) for v in (mean if isinstance(mean, (list, tuple)) else (mean,)))
+        self.std = tuple(float(v) for v in (std if isinstance(std, (list, tuple)) else (std,)))
+        if any(not (s > 0.0 and math.isfinite(s)) for s in self.std):
+            raise ValueError(f"Normalize: std must be finite and > 0, got {self.std}")
+
+    def __call__(self, x: torch.Tensor) -> torch.Tensor:
+        mean = torch.tensor(self.mean, dtype=x.dtype).view(-1, 1, 1)
+        std = torch.tensor(self.std, dtype=x.dtype).view(-1, 1, 1)
+        return (x - mean) / std
+
+    def __repr__(self) -> str:
+        return f"Normalize(mean={self.mean}, std={self.std})"
+
+
+class Compose:
+    """Apply ``transforms`` in order (torchvision's ``transforms.Compose``)."""
+
+    def __init__(self, transforms: Sequence[Callable]):
+        self.transforms = list(transforms)
+
+    def __call__(self, x):
+        for t in self.transforms:
+            x = t(x)
+        return x
+
+    def __repr__(self) -> str:
+        return f"Compose({self.transforms!r})"
 
 
 class RandomDataset(Dataset):

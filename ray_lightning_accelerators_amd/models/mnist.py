@@ -27,8 +27,18 @@ The optimizer may be a fused single-group ``torch.optim.Adam``, ``AdamW`` or ``S
 step and the in-kernel exchange included.  SGD (momentum, dampening, Nesterov, weight decay)
 is applied by the tail kernel: head / tail at world size 1, else -- and under clipping or
 accumulation -- head / tail(grad | acc) / [allreduce] / [norm partials] / tail(sgd); never
-one launch, never the in-kernel exchange.  ``optimizer.state_dict()`` stays torch's.  Batches the
-resident path cannot serve (e.g. user transforms) use a one-launch fp32-input
+one launch, never the in-kernel exchange.  ``optimizer.state_dict()`` stays torch's.
+
+Datasets the resident path serves (``_u8_source``; ``Subset`` / ``random_split`` chains of
+them included): ``.images`` uint8 ``[N, 784]`` with tensor ``.targets`` (``SyntheticMNIST``),
+and the torchvision layout -- ``.data`` uint8 ``[N, 28, 28]`` or ``[N, 784]`` with ``.targets``
+(``models.data.IdxMNIST`` over real MNIST's IDX files, or torchvision's own ``MNIST``).  Their
+``transform`` may be nothing, ``ToTensor`` and one single-channel ``Normalize(mean, std)``
+(bare or in a ``Compose``; matched by class name, so torchvision's objects count): the
+normalisation becomes one FMA in the kernels' u8 -> bf16 conversion
+(``ops.fused_mlp.input_affine``), for training and for ``eval_epoch``.  A dataset other than
+ours must convert with ``ToTensor`` first; ``target_transform`` must be None.  Batches the
+resident path cannot serve (any other transform, other datasets) use a one-launch fp32-input
 kernel; CPU / unsupported shapes use the ordinary autograd path.
 """
 from __future__ import annotations
@@ -46,7 +56,7 @@ from ..lightning import LightningModule
 from ..lightning.metrics import Accuracy
 from ..lightning.sampling import deterministic_sampler, sampler_order
 from ..ops import fused_mlp
-from .data import SyntheticMNIST
+from .data import IdxMNIST, SyntheticMNIST
 
 
 class LightningMNISTClassifier(LightningModule):
@@ -128,8 +138,44 @@ class LightningMNISTClassifier(LightningModule):
         return d
 
 
+def _transform_chain(t) -> list:
+    """A transform as a flat list: None -> [], a ``Compose`` (anything with ``.transforms``)
+    -> its items, flattened."""
+    if t is None:
+        return []
+    if hasattr(t, "transforms"):
+        return [u for item in t.transforms for u in _transform_chain(item)]
+    return [t]
+
+
+def _resident_normalize(transform, to_tensor_built_in: bool):
+    """``(True, normalize)`` when the kernels' u8 -> bf16 conversion reproduces ``transform``
+    -- ``normalize`` is None (ToTensor alone) or ``(mean, std)`` of one single-channel
+    ``Normalize`` -- else ``(False, None)``.  Items are matched by class name.  A dataset
+    that hands out raw images (``to_tensor_built_in`` False) must convert with ``ToTensor``
+    first."""
+    chain = _transform_chain(transform)
+    names = [type(t).__name__ for t in chain]
+    if not to_tensor_built_in and (not names or names[0] != "ToTensor"):
+        return False, None
+    rest = [t for t, n in zip(chain, names) if n != "ToTensor"]
+    if not rest:
+        return True, None
+    if len(rest) != 1 or type(rest[0]).__name__ != "Normalize" or not hasattr(rest[0], "mean") \
+            or not hasattr(rest[0], "std"):
+        return False, None
+    try:
+        return True, fused_mlp.normalize_pair((rest[0].mean, rest[0].std))
+    except (TypeError, ValueError):  # several channels, std <= 0, non-finite
+        return False, None
+
+
 def _u8_source(dataset):
-    """Find (images_u8 [N,784], targets, index_map) behind a dataset (Subset chains allowed)."""
+    """Find (images_u8 [N,784], targets, index_map, normalize) behind a dataset (Subset chains
+    allowed), or None when the resident path cannot reproduce it.  Accepted: ``.images`` uint8
+    ``[N, 784]`` with tensor ``.targets``; ``.data`` uint8 ``[N, 28, 28]`` / ``[N, 784]`` with
+    ``.targets`` (tensor or list).  ``normalize``: None, or ``(mean, std)`` of the dataset's
+    single-channel ``Normalize`` (``_resident_normalize`` has the transform rules)."""
     idx_map = None
     ds = dataset
     while isinstance(ds, Subset):
@@ -138,10 +184,41 @@ def _u8_source(dataset):
         ds = ds.dataset
     images = getattr(ds, "images", None)
     targets = getattr(ds, "targets", None)
-    if isinstance(images, torch.Tensor) and images.dtype == torch.uint8 and images.dim() == 2 \
-            and images.size(1) == 784 and isinstance(targets, torch.Tensor):
-        return images, targets, idx_map
-    return None
+    ours = True  # ToTensor is part of our datasets' __getitem__
+    if not isinstance(images, torch.Tensor):
+        images = getattr(ds, "data", None)
+        ours = isinstance(ds, (IdxMNIST, SyntheticMNIST))
+        if isinstance(images, torch.Tensor) and images.dtype == torch.uint8 and images.dim() == 3 \
+                and tuple(images.shape[1:]) == (28, 28) and images.is_contiguous():
+            images = images.view(images.size(0), 784)
+        if isinstance(targets, (list, tuple)):
+            try:
+                targets = torch.as_tensor(targets, dtype=torch.int64)
+            except (TypeError, ValueError):
+                return None
+    if not (isinstance(images, torch.Tensor) and images.dtype == torch.uint8 and images.dim() == 2
+            and images.size(1) == 784 and isinstance(targets, torch.Tensor)):
+        return None
+    if getattr(ds, "target_transform", None) is not None:
+        return None
+    ok, normalize = _resident_normalize(getattr(ds, "transform", None), ours)
+    if not ok:
+        return None
+    return images, targets, idx_map, normalize
+
+
+def _transforms_of(dataset):
+    """(transform, target_transform) objects of the dataset behind a Subset chain."""
+    ds = dataset
+    while isinstance(ds, Subset):
+        ds = ds.dataset
+    return getattr(ds, "transform", None), getattr(ds, "target_transform", None)
+
+
+def _same_storage(a: Optional[torch.Tensor], b: Optional[torch.Tensor]) -> bool:
+    """The same host images (a ``.data`` dataset is viewed as [N, 784] anew at every look)."""
+    return a is not None and b is not None and (
+        a is b or (a.data_ptr() == b.data_ptr() and a.shape == b.shape and a.dtype == b.dtype))
 
 
 # the sampler-order helpers live in lightning/sampling.py (shared with the
@@ -200,6 +277,7 @@ class FusedMNISTStep:
         self.lr_tensor = torch.full((1,), self.lr_val, device=dev)
         self.stats = torch.zeros(64, 4, device=dev)
         self._u8 = None
+        self._normalize = None  # the training dataset's Normalize (mean, std), folded into the kernels
         self._order = None
         self._epoch_key = None
         self.eng = None  # v3 pipelined engine (resident-data mode), bound to the arena
@@ -245,7 +323,7 @@ class FusedMNISTStep:
                              clip_norm=self.clip_norm, accumulate=self.accumulate, **hyper)
         eng.set_step(self.gs.step)
         eng.lr_tensor = self.lr_tensor  # LR schedulers update one device scalar
-        eng.attach_dataset(self._u8, self._labels)
+        eng.attach_dataset(self._u8, self._labels, normalize=self._normalize)
         self.eng = eng
         return eng
 
@@ -256,8 +334,12 @@ class FusedMNISTStep:
         the GPU sat idle at the epoch start."""
         cache = self.__dict__.setdefault("_src_cache", {})
         ent = cache.get(id(dataset))
-        if ent is None or ent[0] is not dataset:
-            ent = cache[id(dataset)] = (dataset, _u8_source(dataset))
+        # the answer holds for the transforms it was derived from: a ``transform`` assigned to
+        # the same dataset object later is looked at again (another Normalize, or none the
+        # kernels can reproduce)
+        tf = _transforms_of(dataset)
+        if ent is None or ent[0] is not dataset or ent[2][0] is not tf[0] or ent[2][1] is not tf[1]:
+            ent = cache[id(dataset)] = (dataset, _u8_source(dataset), tf)
         return ent[1]
 
     def make_epoch_batches(self, dl, n_batches: int):
@@ -265,11 +347,17 @@ class FusedMNISTStep:
         src = self._source(dl.dataset)
         if src is None or dl.batch_size is None:
             return None
-        images, targets, idx_map = src
+        images, targets, idx_map, normalize = src
         if self._u8 is None:
             self._u8_host = images
             self._u8 = images.to(self.dev).contiguous()
             self._labels = targets.to(self.dev, torch.int64).contiguous()
+            self._normalize = normalize
+        elif normalize != self._normalize:
+            # the loader's transform changed: the engine re-primes and re-captures under the new map
+            self._normalize = normalize
+            if self.eng is not None:
+                self.eng.attach_dataset(self._u8, self._labels, normalize=normalize)
         pre = getattr(self, "_prefetched", None)
         self._prefetched = None
         ep = getattr(dl.sampler, "epoch", None)
@@ -585,7 +673,7 @@ class FusedMNISTStep:
                 and t.forward is LightningMNISTClassifier.forward)
 
     def _resident(self, images: torch.Tensor, targets: torch.Tensor):
-        if self._u8 is not None and images is getattr(self, "_u8_host", None):
+        if self._u8 is not None and _same_storage(images, getattr(self, "_u8_host", None)):
             return self._u8, self._labels  # validation split of the training dataset
         cache = self.__dict__.setdefault("_eval_sets", {})
         key = id(images)
@@ -604,7 +692,8 @@ class FusedMNISTStep:
         src = self._source(dl.dataset)
         if src is None or dl.batch_size is None or n_batches <= 0:
             return None
-        images, targets, idx_map = src
+        images, targets, idx_map, normalize = src
+        x_scale, x_shift = fused_mlp.input_affine(normalize)  # the validation dataset's own transform
         B = int(dl.batch_size)
         key = (id(dl), id(images), int(n_batches))
         cached = self.__dict__.setdefault("_eval_orders", {}).get(key)
@@ -635,7 +724,7 @@ class FusedMNISTStep:
         n = nb * B
         part = torch.empty((n + 31) // 32, 2, device=self.dev)
         fused_mlp.mlp_eval(self.arena.data[: self.np], L1=self.L1, L2=self.L2, B=n, labels=labels, out=part,
-                           x_u8=u8, index=order_dev)
+                           x_u8=u8, index=order_dev, x_scale=x_scale, x_shift=x_shift)
         tot = part.sum(0) / n
         return {"val_loss": tot[0], "val_accuracy": tot[1]}
 

@@ -11,6 +11,7 @@ Parameter arena layout (== ``nn.Linear`` state_dict order of
 from __future__ import annotations
 
 import math
+import struct
 from typing import Dict, Optional, Sequence, Tuple
 
 import torch
@@ -48,11 +49,87 @@ def mlp_unpack(flat: torch.Tensor, L1: int, L2: int) -> Dict[str, torch.Tensor]:
     return out
 
 
-def _gather_batch(x_u8, x_f32, labels, order, cursor, B, index=None):
+def _f32(v: float) -> float:
+    """``v`` rounded once to fp32 (returned as a Python float).  No tensor is built: the
+    launch wrappers call this per launch."""
+    v = float(v)
+    try:
+        return struct.unpack("f", struct.pack("f", v))[0]
+    except OverflowError:  # finite, beyond fp32: what the C cast gives
+        return math.copysign(math.inf, v)
+
+
+# the kernels' default u8 -> bf16 map (csrc/kernels.h kMLPXScale): ToTensor alone
+X_SCALE_DEFAULT = _f32(1.0 / 255.0)
+
+
+def normalize_pair(normalize) -> Optional[Tuple[float, float]]:
+    """``(mean, std)`` of a single-channel ``Normalize`` as two floats (each given as a scalar,
+    a one-element sequence or tensor); None stays None.  More than one channel, ``std <= 0``
+    or a non-finite value raises."""
+    if normalize is None:
+        return None
+
+    def scalar(v, name):
+        if isinstance(v, torch.Tensor):
+            v = v.reshape(-1).tolist()
+        if isinstance(v, (list, tuple)):
+            if len(v) != 1:
+                raise ValueError(f"{name} must be one value (single-channel Normalize), got {v!r}")
+            v = v[0]
+        return float(v)
+
+    mean, std = normalize
+    mean, std = scalar(mean, "mean"), scalar(std, "std")
+    if not (math.isfinite(std) and std > 0.0):
+        raise ValueError(f"Normalize: std must be finite and > 0, got {std}")
+    if not math.isfinite(mean):
+        raise ValueError(f"Normalize: mean must be finite, got {mean}")
+    return mean, std
+
+
+def input_affine(normalize=None) -> Tuple[float, float]:
+    """``(x_scale, x_shift)`` of the kernels' u8 -> bf16 conversion
+    ``bf16(fmaf(u8, x_scale, x_shift))`` -- the one place that derives them.  ``None``:
+    ToTensor alone, ``(float32(1/255), 0.0)``, bitwise the kernels' former ``u8 * (1/255)``.
+    ``(mean, std)`` (``normalize_pair``): ``float32(1 / (255 std))``, ``float32(-mean / std)``,
+    each computed in float64 and rounded once."""
+    pair = normalize_pair(normalize)
+    if pair is None:
+        return X_SCALE_DEFAULT, 0.0
+    mean, std = pair
+    scale, shift = _f32(1.0 / (255.0 * std)), _f32(-mean / std) + 0.0  # (+ 0.0: mean 0 gives +0, not -0)
+    if not (math.isfinite(scale) and scale > 0.0 and math.isfinite(shift)):
+        raise ValueError(f"Normalize({mean}, {std}) leaves the fp32 range (scale {scale}, shift {shift})")
+    return scale, shift
+
+
+def check_input_affine(x_scale: float, x_shift: float) -> Tuple[float, float]:
+    """What every launch accepts (the kernels' own rule, csrc/kernels.h): a finite positive
+    fp32 scale and a finite fp32 shift."""
+    sc, sh = _f32(x_scale), _f32(x_shift)
+    if not (math.isfinite(sc) and sc > 0.0 and math.isfinite(sh)):
+        raise ValueError(f"x_scale must be finite and > 0 and x_shift finite, got {x_scale}, {x_shift}")
+    return sc, sh
+
+
+def u8_to_input(x_u8: torch.Tensor, x_scale: float = X_SCALE_DEFAULT, x_shift: float = 0.0) -> torch.Tensor:
+    """The kernels' pixel map in fp32 FMA semantics: ``float32(u8 * x_scale + x_shift)``, the
+    product and sum exact in float64 (8 + 24 significant bits) and rounded once.  The
+    kernels round this value to bf16."""
+    return (x_u8.double() * float(x_scale) + float(x_shift)).float()
+
+
+def _gather_batch(x_u8, x_f32, labels, order, cursor, B, index=None, x_scale=X_SCALE_DEFAULT, x_shift=0.0):
     if x_u8 is not None:
         if index is None:
             index = order[cursor * B:(cursor + 1) * B]
-        x = x_u8.index_select(0, index).float() / 255.0
+        rows = x_u8.index_select(0, index)
+        if x_scale == X_SCALE_DEFAULT and x_shift == 0.0:
+            x = rows.float() / 255.0  # ToTensor alone: the reference as it always was (equal after bf16 rounding)
+        else:
+            # a Normalize: the FMA, rounded to bf16 as the kernels store it (xring / LDS)
+            x = u8_to_input(rows, x_scale, x_shift).to(torch.bfloat16).float()
         y = labels.index_select(0, index)
     else:
         x = x_f32.reshape(B, IN_FEATURES).float()
@@ -92,25 +169,30 @@ def mlp_train_step(
     lr_tensor: Optional[torch.Tensor] = None,
     adamw: bool = False,
     stamps: Optional[torch.Tensor] = None,
+    x_scale: float = X_SCALE_DEFAULT,
+    x_shift: float = 0.0,
 ) -> None:
     """One training micro-step of the MNIST MLP over a flat parameter arena.
 
     u8 mode (``x_u8`` = GPU-resident uint8 dataset [N, 784]): the batch is
     ``order[cursor*B:(cursor+1)*B]`` with ``cursor = counters[1]``, which the
     step advances (mod ``n_batches``) -- so a captured hipGraph replays
-    successive batches.  ``counters[0]`` is the optimizer step t.
+    successive batches.  ``counters[0]`` is the optimizer step t.  A pixel enters the
+    network as ``fmaf(u8, x_scale, x_shift)`` (``input_affine``); ``x_f32`` mode ignores both.
     """
+    if x_u8 is not None:
+        x_scale, x_shift = check_input_affine(x_scale, x_shift)
     if use_native(params):
         require().mlp_train_step(
             x_u8, x_f32, labels, order, counters, int(n_batches), int(B), int(L1), int(L2),
             params, grads, exp_avg, exp_avg_sq, stats, bool(accumulate_grad), bool(apply_adam),
             bool(advance_step), float(lr), float(betas[0]), float(betas[1]), float(eps),
-            float(weight_decay), lr_tensor, bool(adamw), stamps,
+            float(weight_decay), lr_tensor, bool(adamw), stamps, float(x_scale), float(x_shift),
         )
         return
     # ---- fp32 reference ----
     cursor = int(counters[1].item()) if (counters is not None and x_u8 is not None) else 0
-    x, y = _gather_batch(x_u8, x_f32, labels, order, cursor, B)
+    x, y = _gather_batch(x_u8, x_f32, labels, order, cursor, B, x_scale=x_scale, x_shift=x_shift)
     with torch.enable_grad():
         leaf = params.detach().clone().requires_grad_(True)
         p = mlp_unpack(leaf, L1, L2)
@@ -240,8 +322,9 @@ def mlp3_h1_health(x_rows: torch.Tensor, w1_bf16: torch.Tensor) -> Tuple[int, in
     as the kernels classify them (csrc/mlp_step3.hip ``h1_check``): fp32 partial
     sums over 16 pixels of bf16 operands; non-finite = NaN or Inf, saturated =
     finite and beyond +-32 (what the fixed-point conversion clamps).  Pure torch, on
-    the CPU: the oracle of the health counters.  ``x_rows``: [B, 784] pixels in
-    [0, 1] (real batch rows only), ``w1_bf16``: [L1, 784]."""
+    the CPU: the oracle of the health counters.  ``x_rows``: [B, 784] pixels as they
+    enter layer 1 -- in [0, 1], or normalised (``u8_to_input``) -- real batch rows only,
+    ``w1_bf16``: [L1, 784]."""
     xt = x_rows.detach().cpu().to(torch.bfloat16).double().view(x_rows.size(0), W1_TILES, 16)
     wt = w1_bf16.detach().cpu().to(torch.bfloat16).double().view(w1_bf16.size(0), W1_TILES, 16)
     part = torch.einsum("bti,mti->tbm", xt, wt).float()  # fp32 MFMA partials
@@ -328,6 +411,8 @@ def mlp3_launch(
     sgd_momentum: Optional[float] = None,
     sgd_dampening: float = 0.0,
     sgd_nesterov: bool = False,
+    x_scale: float = X_SCALE_DEFAULT,
+    x_shift: float = 0.0,
 ) -> None:
     """One v3 launch (GPU only; ``repeat``: that many identical launches back to back
     from one C++ loop -- every step's state lives on the device).  ``kind``: MLP3_STEP (head + fused tail, world size 1),
@@ -371,7 +456,16 @@ def mlp3_launch(
     coefficient) as given, ``sgd_dampening`` and ``sgd_nesterov``.  ``exp_avg`` is then the
     velocity (torch's ``momentum_buffer``, 16-byte aligned; may be None when the momentum is 0,
     and is never touched then) and ``exp_avg_sq`` is unused (None).  The first optimizer step
-    (``counters[0] <= 1`` after the head's advance) sets the velocity to the gradient."""
+    (``counters[0] <= 1`` after the head's advance) sets the velocity to the gradient.
+
+    ``x_scale`` / ``x_shift`` (``input_affine``): every gather of a batch (head, PRIME, the
+    tails' and the one-launch step's look-ahead) stores ``bf16(fmaf(u8, x_scale, x_shift))``;
+    padded rows stay zero.  Non-finite values or a scale <= 0 raise before any launch.
+    MLP3_STEP1 runs its Normalize instance for any other map than the default; MLP3_STEP1_DP
+    has none (MLP3_STEP_DP serves a normalised dataset) and raises."""
+    x_scale, x_shift = check_input_affine(x_scale, x_shift)
+    if kind == MLP3_STEP1_DP and (x_scale, x_shift) != (X_SCALE_DEFAULT, 0.0):
+        raise ValueError("mlp3_launch: MLP3_STEP1_DP has no Normalize instance -- use MLP3_STEP_DP")
     if sgd_momentum is not None:
         if kind not in (MLP3_STEP, MLP3_TAIL_ADAM):
             raise ValueError(f"mlp3_launch: SGD arguments belong to MLP3_STEP / MLP3_TAIL_ADAM, not kind {kind}")
@@ -405,6 +499,7 @@ def mlp3_launch(
         clip_part, float(clip_max_norm), clip_out, -1 if clip_nblk is None else int(clip_nblk),
         bool(acc_add), bool(acc_rows), acc_head_row,
         None if sgd_momentum is None else float(sgd_momentum), float(sgd_dampening), bool(sgd_nesterov),
+        float(x_scale), float(x_shift),
     )
 
 
@@ -436,15 +531,21 @@ def mlp_eval(
     x_f32: Optional[torch.Tensor] = None,
     index: Optional[torch.Tensor] = None,
     logits: Optional[torch.Tensor] = None,
+    x_scale: float = X_SCALE_DEFAULT,
+    x_shift: float = 0.0,
 ) -> None:
     """Forward only.  ``out`` [2]: out[0] += sum NLL, out[1] += #correct.  ``out``
     [ceil(B/32), 2]: per-32-row-chunk (sum NLL, #correct), overwritten -- the GPU
     kernel then runs one workgroup per chunk and the caller's ``out.sum(0)`` is
-    deterministic.  Optional log-probs into ``logits``."""
+    deterministic.  Optional log-probs into ``logits``.  u8 mode reads a pixel as
+    ``fmaf(u8, x_scale, x_shift)`` (``input_affine``)."""
+    if x_u8 is not None:
+        x_scale, x_shift = check_input_affine(x_scale, x_shift)
     if use_native(params):
-        require().mlp_eval(x_u8, x_f32, labels, index, int(B), int(L1), int(L2), params, logits, out)
+        require().mlp_eval(x_u8, x_f32, labels, index, int(B), int(L1), int(L2), params, logits, out,
+                           float(x_scale), float(x_shift))
         return
-    x, y = _gather_batch(x_u8, x_f32, labels, None, 0, B, index=index)
+    x, y = _gather_batch(x_u8, x_f32, labels, None, 0, B, index=index, x_scale=x_scale, x_shift=x_shift)
     with torch.no_grad():
         logp = F.log_softmax(_reference_forward(mlp_unpack(params, L1, L2), x), dim=1)
         nll = F.nll_loss(logp, y, reduction="none")

@@ -5,10 +5,11 @@ run for ``MNISTClassifier`` (SURVEY.md §3.5 "one training step"; reference
 ``ray_lightning/tests/utils.py`` / ``examples/ray_ddp_example.py`` model),
 re-designed for MI355X instead of translating PL's DDP loop:
 
-* the dataset is resident in HBM as uint8 (MNIST is uint8; ToTensor's /255 is
-  fused into the kernel), and each rank's DistributedSampler shard for the
-  current AND the next epoch is an index list on the device, so a step needs
-  NO host->device copy and no host sync at epoch boundaries;
+* the dataset is resident in HBM as uint8 (MNIST is uint8; ToTensor's /255 and an
+  optional single-channel ``Normalize(mean, std)`` are one FMA in the kernels' u8 -> bf16
+  conversion: ``set_data`` / ``attach_dataset(normalize=(mean, std))``), and each rank's
+  DistributedSampler shard for the current AND the next epoch is an index list on the
+  device, so a step needs NO host->device copy and no host sync at epoch boundaries;
 * parameters, gradients and Adam state are flat fp32 arenas; the whole model's
   gradient is ONE allreduce bucket (27,882 floats = 109 KiB at the default
   32/64 config -- far below the ~1 MiB where splitting pays on 7 xGMI links);
@@ -266,6 +267,9 @@ class FusedMLPEngine:
         # kernel applies Adam)
         self.one_launch = (self.B <= fused_mlp.ONE_LAUNCH_MAX_B and os.environ.get("RLA_MLP_ONE_LAUNCH") != "0"
                            and clip_norm is None and accumulate == 1 and not self.sgd)
+        # the dataset's Normalize(mean, std) or None, and the kernels' pixel map derived from it
+        self.normalize = None
+        self.x_scale, self.x_shift = fused_mlp.input_affine(None)
         # world size > 1 with the xGMI context: the same one launch, each block
         # exchanging its values with the peers (protocol: self.dp_proto)
         self.dp_proto = "packed"
@@ -293,7 +297,6 @@ class FusedMLPEngine:
         "granule"; "wave" / "all" are two-launch flag protocols).  Collective when
         ``rearm`` (every rank switches together): the region is reset first, because
         a granule left by another protocol could carry a current-looking tag."""
-        n = fused_mlp.mlp_param_count(self.L1, self.L2)
         if name not in fused_mlp.DP_PROTOS and name not in ("wave", "all"):
             raise ValueError(f"unknown data-parallel exchange protocol {name!r}")
         if self.dp_proto == "owner" and name != "owner" and getattr(self, "_stepped_owner", False):
@@ -301,10 +304,7 @@ class FusedMLPEngine:
             self.sync_optimizer_state()
         self._stepped_owner = False
         self.dp_proto = name
-        ctx = self.dp_ctx
-        need = 2 * n if name == "granule" else fused_mlp.DP_AREA_FLOATS
-        self.one_launch_dp = (self.one_launch and ctx is not None and name in fused_mlp.DP_PROTOS
-                              and ctx[2] >= need)
+        self.one_launch_dp = self._one_launch_dp_ok()
         if rearm and self.dp_ctx is not None and self._dp_rearm is not None:
             self._dp_rearm()
         self._drop_graphs()
@@ -466,9 +466,41 @@ class FusedMLPEngine:
         return getattr(self, "_grads_padded", self.grads)
 
     # ------------------------------------------------- host-driven epochs
-    def attach_dataset(self, images_u8: torch.Tensor, labels: torch.Tensor) -> None:
-        """Trainer mode: the dataset is resident, the host supplies each epoch's order."""
+    def _one_launch_dp_ok(self) -> bool:
+        """Whether the in-kernel exchange runs inside the one-launch step.  (A normalised
+        dataset: the one-launch kernel has its Normalize instances at world size 1 only, so
+        the exchange then runs in the two-launch step's tail.)"""
+        ctx, name = self.dp_ctx, self.dp_proto
+        need = 2 * fused_mlp.mlp_param_count(self.L1, self.L2) if name == "granule" else fused_mlp.DP_AREA_FLOATS
+        return (self.one_launch and ctx is not None and name in fused_mlp.DP_PROTOS and ctx[2] >= need
+                and (self.x_scale, self.x_shift) == fused_mlp.input_affine(None))
+
+    def _set_normalize(self, normalize) -> None:
+        """The dataset's single-channel ``Normalize(mean, std)`` (None: ToTensor alone).  A
+        changed pixel map invalidates what was gathered and captured under the old one: the
+        graphs (they bake the two scalars) and the primed batch."""
+        scale, shift = fused_mlp.input_affine(normalize)
+        if (scale, shift) != (self.x_scale, self.x_shift):
+            self._drop_graphs()
+            self._primed = False
+        self.normalize = fused_mlp.normalize_pair(normalize)
+        self.x_scale, self.x_shift = scale, shift
+        if self.one_launch_dp and self.dp_proto == "owner" and getattr(self, "_stepped_owner", False):
+            self.sync_optimizer_state()  # leaving the owner protocol: consolidate the Adam state first
+            self._stepped_owner = False
+        was = self.one_launch_dp
+        self.one_launch_dp = self._one_launch_dp_ok()
+        if was and not self.one_launch_dp:
+            log.warning("fused MLP step: the dataset's Normalize%s takes the data-parallel exchange out of the "
+                        "one-launch step (its Normalize instances exist at world size 1 only): every step now runs "
+                        "as two launches, head + tail with the in-kernel exchange", self.normalize)
+
+    def attach_dataset(self, images_u8: torch.Tensor, labels: torch.Tensor, normalize=None) -> None:
+        """Trainer mode: the dataset is resident, the host supplies each epoch's order.
+        ``normalize``: ``(mean, std)`` of a single-channel ``Normalize`` after ToTensor, folded
+        into the kernels' u8 -> bf16 conversion (``ops.fused_mlp.input_affine``)."""
         assert images_u8.dtype == torch.uint8 and images_u8.dim() == 2 and images_u8.size(1) == 784
+        self._set_normalize(normalize)
         self.x_u8 = images_u8.to(self.device).contiguous()
         self.labels = labels.to(self.device, torch.int64).contiguous()
         self.n_data = self.x_u8.size(0)
@@ -512,9 +544,11 @@ class FusedMLPEngine:
         self._primed = False
 
     # ------------------------------------------------------------------ data
-    def set_data(self, images_u8: torch.Tensor, labels: torch.Tensor, shuffle: bool = True) -> None:
-        """Make the (full) dataset resident on the device; shards are per-rank index lists."""
+    def set_data(self, images_u8: torch.Tensor, labels: torch.Tensor, shuffle: bool = True, normalize=None) -> None:
+        """Make the (full) dataset resident on the device; shards are per-rank index lists.
+        ``normalize``: as ``attach_dataset``."""
         assert images_u8.dtype == torch.uint8 and images_u8.dim() == 2 and images_u8.size(1) == 784
+        self._set_normalize(normalize)
         self.x_u8 = images_u8.to(self.device).contiguous()
         self.labels = labels.to(self.device, torch.int64).contiguous()
         self.shuffle = shuffle
@@ -573,7 +607,8 @@ class FusedMLPEngine:
                     grads=self.grads, exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq, shadow=self.shadow,
                     dh1t=self.dh1t, xring=self.xring, h1pre=self.h1pre, act=self.act, yring=self.yring,
                     head_part=self.head_part, hand=self.hand, lr=self.lr, betas=self.betas,
-                    eps=self.eps, weight_decay=self.wd, lr_tensor=self.lr_tensor, adamw=self.adamw)
+                    eps=self.eps, weight_decay=self.wd, lr_tensor=self.lr_tensor, adamw=self.adamw,
+                    x_scale=self.x_scale, x_shift=self.x_shift)
 
     def _sgd_kw(self) -> dict:
         """The SGD arguments of the launch that applies the optimizer (MLP3_STEP /
@@ -679,6 +714,7 @@ class FusedMLPEngine:
             exp_avg_sq=self.exp_avg_sq, stats=self._head_row if acc else self.stats, accumulate_grad=micro > 0,
             apply_adam=fused, advance_step=closing, lr=self.lr,
             betas=self.betas, eps=self.eps, weight_decay=self.wd, lr_tensor=self.lr_tensor, adamw=self.adamw,
+            x_scale=self.x_scale, x_shift=self.x_shift,
         )
         c[2] = cursor
         c[3] = int(c[3]) ^ 1
