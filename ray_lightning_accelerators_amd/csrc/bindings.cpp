@@ -243,7 +243,7 @@ void mlp3(int64_t kind, Tensor x_u8, Tensor labels, Tensor order, Tensor counter
           optional<Tensor> hand, int64_t dp_proto, bool dp_loop, int64_t repeat, optional<Tensor> clip_part,
           double clip_max_norm, optional<Tensor> clip_out, int64_t clip_nblk, bool acc_add, bool acc_rows,
           optional<Tensor> acc_head_row, optional<double> sgd_momentum, double sgd_dampening, bool sgd_nesterov,
-          double x_scale, double x_shift) {
+          double x_scale, double x_shift, optional<int64_t> last_rows) {
   TORCH_CHECK(kind >= 0 && kind <= 8, "mlp3: bad kind ", kind);
   // SGD: refused here, before any launch, wherever it does not belong
   rla::MLP3Sgd sgd{0, 0.f, 0.f, 0};
@@ -312,6 +312,10 @@ void mlp3(int64_t kind, Tensor x_u8, Tensor labels, Tensor order, Tensor counter
   a.counters = counters.data_ptr<int64_t>();
   a.n_batches = n_batches;
   a.B = (int)B; a.L1 = (int)L1; a.L2 = (int)L2;
+  // valid rows of the epoch's last batch (None: a full one); launch_mlp3 refuses what is
+  // outside [1, B] or on a kind that cannot run a short batch (-15)
+  const int64_t lr_rows = last_rows.has_value() ? *last_rows : B;
+  a.last_rows = (int)std::max<int64_t>(-1, std::min<int64_t>(lr_rows, B + 1));
   a.params = params.data_ptr<float>();
   a.grads = grads.data_ptr<float>();
   a.exp_avg = has_m ? exp_avg_o->data_ptr<float>() : nullptr;
@@ -424,6 +428,9 @@ void mlp3(int64_t kind, Tensor x_u8, Tensor labels, Tensor order, Tensor counter
   {
     const int rc = rla::launch_mlp3(a, (int)kind, st, &clip, &acc, &sgd);
     check_input_affine(rc, "mlp3", x_scale, x_shift);
+    TORCH_CHECK_VALUE(rc != -15, "mlp3: last_rows must be in [1, B = ", B, "] and equal B on the one-launch and "
+                      "exchange kinds (5, 6, 7), got last_rows = ", lr_rows, " on kind ", kind,
+                      " (code -15, nothing was launched)");
     TORCH_CHECK(rc == 0, "fused MLP v3 launch failed (kind ", kind, ", code ", rc, ")");
   }
 }
@@ -1160,7 +1167,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("clip_part") = py::none(), py::arg("clip_max_norm") = 0.0, py::arg("clip_out") = py::none(),
         py::arg("clip_nblk") = -1, py::arg("acc_add") = false, py::arg("acc_rows") = false,
         py::arg("acc_head_row") = py::none(), py::arg("sgd_momentum") = py::none(), py::arg("sgd_dampening") = 0.0,
-        py::arg("sgd_nesterov") = false, py::arg("x_scale") = (double)rla::kMLPXScale, py::arg("x_shift") = 0.0);
+        py::arg("sgd_nesterov") = false, py::arg("x_scale") = (double)rla::kMLPXScale, py::arg("x_shift") = 0.0,
+        py::arg("last_rows") = py::none());
   m.def("dp_pack_roundtrip", &dp_pack_roundtrip, "packed DP exchange wire form of fp32 pairs, encoded + decoded");
   m.def("mlp3_hand_words", [](int64_t l1, int64_t l2) { return rla::mlp3_hand_words((int)l1, (int)l2); });
   m.def("mlp3_hand_layout", []() {

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <float.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include <functional>
@@ -246,6 +247,11 @@ struct MLP3Args {
                             // [10] launch sequence number of the one-launch step (counters of >= 16)
   int64_t n_batches;
   int B, L1, L2;
+  // valid rows of the epoch's LAST batch (cursor n_batches - 1), in [1, B]; B: no short batch.
+  // Two-launch family and PRIME only (the one-launch and exchange kinds never read it).  It
+  // sits in the four bytes of padding the struct always had here, so every other field keeps
+  // its kernarg offset and the struct its size.
+  int last_rows;
   float* params;
   float* grads;
   float* exp_avg;
@@ -292,6 +298,8 @@ struct MLP3Args {
   // other field keeps its kernarg offset)
   float x_scale, x_shift;
 };
+static_assert(offsetof(MLP3Args, params) == 64 && offsetof(MLP3Args, last_rows) == 60,
+              "last_rows fills the padding in front of params");
 enum MLP3Kind { kMLP3Step = 0, kMLP3Head = 1, kMLP3TailGrad = 2, kMLP3TailAdam = 3, kMLP3Prime = 4,
                 kMLP3StepDP = 5, kMLP3Step1 = 6, kMLP3Step1DP = 7, kMLP3TailAcc = 8 };
 int64_t mlp3_hand_words(int L1, int L2);  // int64 words of the one-launch step's hand-off buffer
@@ -358,7 +366,9 @@ struct MLP3Sgd {
 // flags on a kind other than TailGrad / TailAcc (or rows without a row source), -11 TailAcc
 // with clip arguments, -12 MLP3Sgd on a kind other than Step / TailAdam (or momentum without
 // a velocity buffer), -13 a non-finite or non-positive x_scale or a non-finite x_shift, -14
-// Step1DP with a pixel map other than the default (StepDP serves a normalised dataset).
+// Step1DP with a pixel map other than the default (StepDP serves a normalised dataset), -15
+// last_rows outside [1, B], or last_rows != B on Step1 / Step1DP / StepDP (a short last batch
+// runs on the two-launch family: Head, Step, TailGrad, TailAcc, TailAdam, and on PRIME).
 int launch_mlp3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip* clip = nullptr,
                 const MLP3Acc* acc = nullptr, const MLP3Sgd* sgd = nullptr);
 

@@ -58,6 +58,18 @@
 // runs as one launch or with the in-kernel exchange; AdamW is `adamw` of MLP3Args on
 // every route.
 //
+// Short last batch (MLP3Args::last_rows; the two-launch family -- head, every tail -- and
+// PRIME): the batch at epoch cursor n_batches - 1 holds last_rows <= B valid rows, every other
+// cursor B (batch_rows, from the device cursor).  Whoever GATHERS a batch (the head launch's
+// gather blocks, PRIME) uses the rows of the batch it gathers: rows past them get zero pixels
+// and label -1, exactly as rows >= B always did, and their `order` slots are never read.
+// Whoever CONSUMES it scales by its rows: the head's 1 / rows in dZ and its stats row, the
+// tails' multi-block stats.  Nothing else changes -- the head masks rows with a label < 0, a
+// head block past the batch's end contributes (0, 0, 0), and zero rows add nothing to any
+// MFMA sum -- so a short batch of r rows is the computation of an engine with B = r.  The
+// one-launch kernel and the exchange kinds never read the field; launch_mlp3 refuses a short
+// batch there (-15) and the engine runs the two steps that touch it as head + tail.
+//
 // Device state (graph-replay safe): counters[0] optimizer step, [1] cursor of
 // the NEXT batch, [2] cursor the last head consumed, [3] ring slot the next head
 // reads, [4] which of the two `order` epoch buffers counters[1] indexes.
@@ -158,26 +170,47 @@ struct H1Copies {
   static constexpr int G = L1 <= 64 ? 2 : 1;
 };
 
+// Valid rows of the batch at epoch cursor `cursor` (two-launch family and PRIME only): the
+// epoch's last batch may be short (MLP3Args::last_rows, a drop_last=False loader with a
+// remainder); every other batch has B rows.  Decided from the device cursor the caller
+// already holds, so a captured graph replays it at any position.  One select over two kernel
+// arguments fetched together (launch_mlp3 admits last_rows in [1, B] only): a short-circuit
+// test of last_rows first made the compiler fetch n_batches behind a branch, two dependent
+// scalar round trips in the tail's prologue.
+__device__ __forceinline__ int batch_rows(const MLP3Args& a, int64_t cursor) {
+  const int last = a.last_rows, full = a.B;
+  const int64_t nb = a.n_batches;
+  return cursor == nb - 1 ? last : full;
+}
+
+// Mean NLL of a multi-block head's `rows` valid rows, as the tail files it.  A short batch of
+// at most 32 rows takes the one-block head's form (sum * (1 / rows)), so its stats row has
+// the bits an engine of batch size `rows` writes; a full batch (B > 32) divides, as ever.
+__device__ __forceinline__ float tail_mean_loss(float sum, int rows) {
+  return rows > kHeadRows ? sum / (float)rows : sum * (1.f / (float)rows);
+}
+
 // Gather one 16-pixel tile of batch (ob, cursor) as bf16 rows into xring slot
-// `dst_slot` (rows >= B zero); block kt == 0 also stages that batch's labels
-// into yring (-1 for padded rows), so no kernel chases the sample index on
-// its critical path.  Runs as extra workgroups of the head launch (for the
+// `dst_slot` (rows at or past the batch's valid rows zero); block kt == 0 also stages that
+// batch's labels into yring (-1 for padded rows), so no kernel chases the sample index on
+// its critical path.  Slots of `order` past the valid rows are never read.  Runs as extra workgroups of the head launch (for the
 // NEXT batch, concurrently with the head's serial chain) or in PRIME.
 __device__ __forceinline__ void gather_tile(const MLP3Args& a, int kt, int64_t ob, int64_t cursor,
                                             int64_t dst_slot, int nthreads) {
   const int tid = threadIdx.x;
   const int B = a.B, Bp = (B + 31) / 32 * 32;
+  const int rows = batch_rows(a, cursor);
   const int64_t* idx = a.order + ob * a.order_stride + cursor * B;
   __bf16* dst = reinterpret_cast<__bf16*>(a.xring) + (dst_slot * kTiles + kt) * (int64_t)Bp * 16;
   for (int b = tid; b < Bp; b += nthreads) {
     bf16x8 lo = zero8(), hi = zero8();
-    if (b < B)
+    if (b < rows)
       u8x16_to_bf16(*reinterpret_cast<const uint4*>(a.x_u8 + idx[b] * kD + kt * 16), lo, hi, a.x_scale, a.x_shift);
     *reinterpret_cast<bf16x8*>(dst + b * 16) = lo;
     *reinterpret_cast<bf16x8*>(dst + b * 16 + 8) = hi;
   }
   if (kt == 0)
-    for (int b = tid; b < Bp; b += nthreads) a.yring[dst_slot * Bp + b] = b < B ? (int)a.labels[idx[b]] : -1;
+    for (int b = tid; b < Bp; b += nthreads) a.yring[dst_slot * Bp + b] = b < rows ? (int)a.labels[idx[b]] : -1;
 }
 
 // Step state read through the constant address space (scalar loads, lgkmcnt): a
@@ -466,7 +499,9 @@ __device__ __forceinline__ void head_body(const MLP3Args& a, char* smem, RepPre*
       for (int i = tid; i < BC * L1 / 4; i += kThreads) z[i] = make_uint4(0u, 0u, 0u, 0u);
     }
   }
-  const float invB = 1.f / (float)a.B;
+  // the loss scale (the one-launch step never meets a short batch and keeps the kernel
+  // argument; the two-launch head sets it from its batch's valid rows where it is first used)
+  float invB = 1.f / (float)a.B;
   constexpr int KS2 = L1 / 32, KS3 = C::KS3, KSH = C::KSH;
   constexpr int MT = C::MT;
   // Wave work maps (8 waves).  Layer 2 / dH2: wave w owns output column tiles
@@ -564,6 +599,10 @@ __device__ __forceinline__ void head_body(const MLP3Args& a, char* smem, RepPre*
     if (tid < NBIAS) sBias[tid] = bias_v;
     if (tid < BC) sY[tid] = yok ? (slot ? y1 : y0) : -1;
     __syncthreads();  // sBias ready
+    // the valid rows of the batch this head consumes: derived here, where the ring slot has
+    // already made every wave wait for the counters, so no load above waits for the cursor,
+    // and far ahead of the softmax that uses it
+    if constexpr (!REP) invB = 1.f / (float)batch_rows(a, cursor);
 
     // ---- H1 = relu(H1pre + b1); H1pre chunk is contiguous in fragment order ----
     {
@@ -1593,7 +1632,7 @@ __device__ __forceinline__ void tail_head_stats(const MLP3Args& a, const int64_t
   }
   const int64_t t = cn[0];
   float* st = a.stats + (int)((t - 1) % (a.stats_ring > 0 ? a.stats_ring : 1)) * 4;
-  st[0] = l / (float)a.B;
+  st[0] = tail_mean_loss(l, batch_rows(a, cn[2]));  // cn[2]: the cursor the head consumed
   st[1] = k;
   st[2] = n;
   st[3] = (float)t;
@@ -1613,7 +1652,7 @@ __device__ __forceinline__ void tail_acc_stats(const MLP3Args& a, const MLP3Acc&
       k += a.head_part[cb * 4 + 1];
       n += a.head_part[cb * 4 + 2];
     }
-    l = l / (float)a.B;
+    l = tail_mean_loss(l, batch_rows(a, a.counters[kCnt + 2]));  // the cursor the head consumed
   } else {
     l = acc.head_row[0];
     k = acc.head_row[1];
@@ -1835,11 +1874,12 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
     }
   } else {  // PRIME: no head ran, gather the pending batch here
     const int64_t* idx = a.order + cn[4] * a.order_stride + cn[1] * B;
+    const int rows_next = batch_rows(a, cn[1]);  // valid rows of the batch PRIME gathers
     if (kt == 0)
-      for (int b = tid; b < Bp; b += NT) a.yring[slot * Bp + b] = b < B ? (int)a.labels[idx[b]] : -1;
+      for (int b = tid; b < Bp; b += NT) a.yring[slot * Bp + b] = b < rows_next ? (int)a.labels[idx[b]] : -1;
     for (int b = tid; b < Bp; b += NT) {
       bf16x8 lo = zero8(), hi = zero8();
-      if (b < B)
+      if (b < rows_next)
         u8x16_to_bf16(*reinterpret_cast<const uint4*>(a.x_u8 + idx[b] * kD + kt * 16), lo, hi, a.x_scale, a.x_shift);
       *reinterpret_cast<bf16x8*>(sXn + b * kXSS) = lo;
       *reinterpret_cast<bf16x8*>(sXn + b * kXSS + 8) = hi;
@@ -1936,6 +1976,11 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
       unsigned* dst = h1 + (int64_t)((mt * TN1 + ct) * 4) * 64 + lane;
 #pragma unroll
       for (int i = 0; i < 4; ++i) atomicAdd(dst + i * 64, f32_to_fixed(d[i]));
+      // (rows [last_rows, B) of a short batch are zero rows like those past B: a finite weight
+      // gives them the partial 0, which is never counted.  They are classified as real rows
+      // only under a non-finite weight, when the batch's real rows are counted anyway: taking
+      // the row count from the cursor here, even on the reporting path alone, cost the step
+      // 0.2 us, profiles/r18_short_batch)
       h1_check(health, d, mt * 16 + 4 * g, B);
     }
     h1_report(a, health, t_step);  // the head advanced it; PRIME: the current counter
@@ -2536,6 +2581,9 @@ int launch_mlp3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip*
                 const MLP3Sgd* sgd_in) {
   if (a.B > kBMax || a.B < 1) return -2;
   if (!mlp_input_affine_ok(a.x_scale, a.x_shift)) return -13;
+  // a short last batch exists in the two-launch family and PRIME only
+  if (a.last_rows < 1 || a.last_rows > a.B) return -15;
+  if (a.last_rows != a.B && (kind == kMLP3Step1 || kind == kMLP3Step1DP || kind == kMLP3StepDP)) return -15;
   // SGD belongs to the two kinds whose tail applies the optimizer outside the one-launch
   // kernel and the in-kernel exchange
   MLP3Sgd sgd{0, 0.f, 0.f, 0};

@@ -28,6 +28,11 @@ step and the in-kernel exchange included.  SGD (momentum, dampening, Nesterov, w
 is applied by the tail kernel: head / tail at world size 1, else -- and under clipping or
 accumulation -- head / tail(grad | acc) / [allreduce] / [norm partials] / tail(sgd); never
 one launch, never the in-kernel exchange.  ``optimizer.state_dict()`` stays torch's.
+The short last batch of a ``drop_last=False`` loader (PyTorch's default) stays on the HIP path
+as well: it is the epoch's last step, over its own rows (``begin_epoch(last_rows=r)``: mean
+loss and gradient over ``r`` rows, a stats row that counts ``r``), run as head / tail where the
+other steps are one launch; ``eval_epoch`` weighs a partial validation batch like a full one,
+as the eager loop does.  Only the in-kernel exchange still drops it (one warning).
 
 Datasets the resident path serves (``_u8_source``; ``Subset`` / ``random_split`` chains of
 them included): ``.images`` uint8 ``[N, 784]`` with tensor ``.targets`` (``SyntheticMNIST``),
@@ -366,13 +371,23 @@ class FusedMNISTStep:
         else:
             order = self._epoch_order(dl.sampler, idx_map)
         B = dl.batch_size
-        nb = min(n_batches, order.numel() // B if dl.drop_last else -(-order.numel() // B))
-        nb = min(nb, order.numel() // B)
+        full, rem = divmod(order.numel(), B)
+        nb = min(n_batches, full if dl.drop_last else -(-order.numel() // B))
+        # the short last batch of a drop_last=False loader is the epoch's last step: its
+        # ``rem`` rows train on the HIP path (FusedMLPEngine.begin_epoch(last_rows=...)); a
+        # limit_train_batches that stops before it leaves only full batches
+        last_rows = rem if (nb > full and rem) else None
         if nb <= 0:
             return None
+        eng = self._engine(B)
+        if last_rows is not None and eng.dp_ctx is not None:
+            # the in-kernel exchange has no short batch: the engine drops it (and says so once)
+            eng.begin_epoch(order, nb, checked=True, last_rows=last_rows)
+            nb = eng.n_batches
+        else:
+            eng.begin_epoch(order[: (nb - 1) * B + (last_rows or B)], nb, checked=True, last_rows=last_rows)
         self._B = B
         self._nb = nb
-        self._engine(B).begin_epoch(order[: nb * B], nb, checked=True)
         return [("__rla_resident__", i) for i in range(nb)]
 
     def _epoch_order(self, sampler, idx_map):
@@ -653,7 +668,7 @@ class FusedMNISTStep:
                 rows[n1:].copy_(eng.stats[: k - n1])
         last = rows[-1]
         loss = last[0]
-        acc = last[1] / last[2]  # every step counts B > 0 rows
+        acc = last[1] / last[2]  # every step counts > 0 rows (B, or a short last batch's)
         # neither tensor is written again before the deferred log flush: no snapshot copy
         loss._rla_fresh = acc._rla_fresh = True
         self.model.log("ptl/train_loss", loss)
@@ -685,10 +700,12 @@ class FusedMNISTStep:
         """One validation pass over the resident dataset in ONE launch (a workgroup
         per 32 samples, per-chunk partial sums reduced deterministically).
         Returns ``{"val_loss", "val_accuracy"}`` device scalars -- the mean over the
-        ``n_batches`` equal-size batches, which is exactly what the eager
+        ``n_batches`` batches of their per-batch means, which is what the eager
         validation_step + validation_epoch_end produce -- or None when the loader
         cannot be served from the resident data (the Trainer then runs the
-        per-batch loop)."""
+        per-batch loop).  The short last batch of a ``drop_last=False`` loader (``r`` rows)
+        weighs like a full one there, ``(S_full / B + S_last / r) / n_batches``: a second
+        launch over its ``r`` samples gives ``S_last``."""
         src = self._source(dl.dataset)
         if src is None or dl.batch_size is None or n_batches <= 0:
             return None
@@ -705,27 +722,37 @@ class FusedMNISTStep:
             order = _sampler_order(dl.sampler)
             if idx_map is not None:
                 order = idx_map[order]
-            full = order.numel() // B
-            if full < n_batches and order.numel() % B:
-                return None  # a partial last batch: eager weights it like a full one
-            nb = min(int(n_batches), full)
+            full, rem = divmod(order.numel(), B)
+            total = full if dl.drop_last else full + (1 if rem else 0)
+            nb = min(int(n_batches), total)
             if nb <= 0:
                 return None
-            order = order[: nb * B]
+            last = rem if nb > full else 0  # rows of a partial last batch inside the limit
+            nb -= 1 if last else 0  # nb: the full batches
+            order = order[: nb * B + last]
             assert int(order.max()) < images.size(0) and int(order.min()) >= 0  # the kernel trusts indices
-            cached = (order.to(self.dev), nb, dl, images)
+            cached = (order.to(self.dev), nb, dl, images, last)
             # reuse only an order that cannot change between epochs (a deterministic
             # sampler): a shuffled sampler is re-drawn every call, as eager iteration
             # does (same subset under limit_val_batches, same global-RNG draws)
             if _deterministic_sampler(dl.sampler):
                 self._eval_orders[key] = cached
-        order_dev, nb = cached[0], cached[1]
+        order_dev, nb, last = cached[0], cached[1], cached[4]
         u8, labels = self._resident(images, targets)
         n = nb * B
-        part = torch.empty((n + 31) // 32, 2, device=self.dev)
-        fused_mlp.mlp_eval(self.arena.data[: self.np], L1=self.L1, L2=self.L2, B=n, labels=labels, out=part,
-                           x_u8=u8, index=order_dev, x_scale=x_scale, x_shift=x_shift)
-        tot = part.sum(0) / n
+        kw = dict(L1=self.L1, L2=self.L2, labels=labels, x_u8=u8, x_scale=x_scale, x_shift=x_shift)
+        tot = None
+        if n:
+            part = torch.empty((n + 31) // 32, 2, device=self.dev)
+            fused_mlp.mlp_eval(self.arena.data[: self.np], B=n, out=part, index=order_dev[:n], **kw)
+            tot = part.sum(0) / n
+            if not last:
+                return {"val_loss": tot[0], "val_accuracy": tot[1]}
+        # the partial batch's own per-batch mean, then the mean over the nb + 1 batches
+        part = torch.empty((last + 31) // 32, 2, device=self.dev)
+        fused_mlp.mlp_eval(self.arena.data[: self.np], B=last, out=part, index=order_dev[n:], **kw)
+        short = part.sum(0) / last
+        tot = short if tot is None else (tot * nb + short) / (nb + 1)
         return {"val_loss": tot[0], "val_accuracy": tot[1]}
 
     def check(self, blocking: bool = True) -> None:

@@ -120,6 +120,17 @@ def u8_to_input(x_u8: torch.Tensor, x_scale: float = X_SCALE_DEFAULT, x_shift: f
     return (x_u8.double() * float(x_scale) + float(x_shift)).float()
 
 
+def check_last_rows(last_rows, B: int, what: str) -> int:
+    """Valid rows of an epoch's last batch: None means a full one, else an integer in [1, B]
+    (the kernels' rule, csrc/kernels.h: launch_mlp3 answers -15 for anything else)."""
+    if last_rows is None:
+        return int(B)
+    if isinstance(last_rows, bool) or int(last_rows) != last_rows or not 1 <= int(last_rows) <= int(B):
+        raise ValueError(f"{what}: last_rows must be an integer in [1, B = {int(B)}], got {last_rows!r} "
+                         "(nothing was launched)")
+    return int(last_rows)
+
+
 def _gather_batch(x_u8, x_f32, labels, order, cursor, B, index=None, x_scale=X_SCALE_DEFAULT, x_shift=0.0):
     if x_u8 is not None:
         if index is None:
@@ -171,6 +182,7 @@ def mlp_train_step(
     stamps: Optional[torch.Tensor] = None,
     x_scale: float = X_SCALE_DEFAULT,
     x_shift: float = 0.0,
+    last_rows: Optional[int] = None,
 ) -> None:
     """One training micro-step of the MNIST MLP over a flat parameter arena.
 
@@ -179,9 +191,16 @@ def mlp_train_step(
     step advances (mod ``n_batches``) -- so a captured hipGraph replays
     successive batches.  ``counters[0]`` is the optimizer step t.  A pixel enters the
     network as ``fmaf(u8, x_scale, x_shift)`` (``input_affine``); ``x_f32`` mode ignores both.
+    ``last_rows`` (u8 mode, the fp32 reference only): the batch at cursor ``n_batches - 1``
+    holds that many rows, ``order[cursor*B : cursor*B + last_rows]``; loss and gradient are
+    their mean and the stats row counts them (None or ``B``: every batch is full).
     """
     if x_u8 is not None:
         x_scale, x_shift = check_input_affine(x_scale, x_shift)
+    last_rows = check_last_rows(last_rows, B, "mlp_train_step")
+    if last_rows != int(B) and (x_u8 is None or use_native(params)):
+        raise ValueError("mlp_train_step: a short last batch (last_rows < B) exists in the u8-mode fp32 reference "
+                         "and in the mlp3 kernels (mlp3_launch) only")
     if use_native(params):
         require().mlp_train_step(
             x_u8, x_f32, labels, order, counters, int(n_batches), int(B), int(L1), int(L2),
@@ -192,7 +211,9 @@ def mlp_train_step(
         return
     # ---- fp32 reference ----
     cursor = int(counters[1].item()) if (counters is not None and x_u8 is not None) else 0
-    x, y = _gather_batch(x_u8, x_f32, labels, order, cursor, B, x_scale=x_scale, x_shift=x_shift)
+    rows = last_rows if (x_u8 is not None and cursor == int(n_batches) - 1) else int(B)
+    index = order[cursor * B:cursor * B + rows] if rows != int(B) else None
+    x, y = _gather_batch(x_u8, x_f32, labels, order, cursor, B, index=index, x_scale=x_scale, x_shift=x_shift)
     with torch.enable_grad():
         leaf = params.detach().clone().requires_grad_(True)
         p = mlp_unpack(leaf, L1, L2)
@@ -222,7 +243,7 @@ def mlp_train_step(
             slot = (t - 1) % max(ring, 1)
             correct = (logp.argmax(dim=1) == y).sum().float()
             stats.view(-1, 4)[slot] = torch.stack(
-                [loss.detach(), correct, torch.tensor(float(B)), torch.tensor(float(t))])
+                [loss.detach(), correct, torch.tensor(float(rows)), torch.tensor(float(t))])
 
 
 def mlp_shadow_layout(L1: int, L2: int) -> Dict[str, int]:
@@ -413,6 +434,7 @@ def mlp3_launch(
     sgd_nesterov: bool = False,
     x_scale: float = X_SCALE_DEFAULT,
     x_shift: float = 0.0,
+    last_rows: Optional[int] = None,
 ) -> None:
     """One v3 launch (GPU only; ``repeat``: that many identical launches back to back
     from one C++ loop -- every step's state lives on the device).  ``kind``: MLP3_STEP (head + fused tail, world size 1),
@@ -462,8 +484,22 @@ def mlp3_launch(
     tails' and the one-launch step's look-ahead) stores ``bf16(fmaf(u8, x_scale, x_shift))``;
     padded rows stay zero.  Non-finite values or a scale <= 0 raise before any launch.
     MLP3_STEP1 runs its Normalize instance for any other map than the default; MLP3_STEP1_DP
-    has none (MLP3_STEP_DP serves a normalised dataset) and raises."""
+    has none (MLP3_STEP_DP serves a normalised dataset) and raises.
+
+    ``last_rows`` (None: ``B``): valid rows of the batch at epoch cursor ``n_batches - 1`` -- the
+    short last batch of a ``drop_last=False`` loader; every other cursor holds ``B`` rows.  The
+    kernels decide from the device cursor: whoever gathers that batch (the head launch's gather
+    blocks, PRIME) reads ``order[cursor*B : cursor*B + last_rows]`` only and stages zero pixels
+    and label -1 beyond; whoever consumes it (head, tails) scales loss and gradient by
+    ``1 / last_rows`` and files the stats row ``(mean NLL, #correct, last_rows, step)``.
+    ``order`` keeps the stride ``n_batches * B``; its padding slots are never read.  Outside
+    ``[1, B]``, or below ``B`` on MLP3_STEP1 / MLP3_STEP1_DP / MLP3_STEP_DP (which have no short
+    batch): ValueError before any launch (launch_mlp3's code -15)."""
     x_scale, x_shift = check_input_affine(x_scale, x_shift)
+    last_rows = check_last_rows(last_rows, B, "mlp3_launch")
+    if last_rows != int(B) and kind in (MLP3_STEP1, MLP3_STEP1_DP, MLP3_STEP_DP):
+        raise ValueError(f"mlp3_launch: last_rows = {last_rows} < B = {int(B)} on kind {kind}: the one-launch step "
+                         "and the in-kernel exchange have no short batch (nothing was launched)")
     if kind == MLP3_STEP1_DP and (x_scale, x_shift) != (X_SCALE_DEFAULT, 0.0):
         raise ValueError("mlp3_launch: MLP3_STEP1_DP has no Normalize instance -- use MLP3_STEP_DP")
     if sgd_momentum is not None:
@@ -499,7 +535,7 @@ def mlp3_launch(
         clip_part, float(clip_max_norm), clip_out, -1 if clip_nblk is None else int(clip_nblk),
         bool(acc_add), bool(acc_rows), acc_head_row,
         None if sgd_momentum is None else float(sgd_momentum), float(sgd_dampening), bool(sgd_nesterov),
-        float(x_scale), float(x_shift),
+        float(x_scale), float(x_shift), int(last_rows),
     )
 
 

@@ -37,6 +37,13 @@ re-designed for MI355X instead of translating PL's DDP loop:
   applied by SGD instances of the tail kernel: head -> tail at world size 1, else (and
   under ``clip_norm`` / ``accumulate``) head -> tail(grad | acc) -> [allreduce] -> [norm
   partials] -> tail(sgd); never one launch, never ``dp_context``;
+* ``begin_epoch(..., last_rows=r)``: the epoch's last batch holds ``r <= B`` rows (the short
+  last batch of a ``drop_last=False`` loader).  The two-launch kernels and PRIME decide from
+  the device cursor which batch that is; every route that is two or more launches just passes
+  ``last_rows``.  A one-launch engine runs the two steps that touch the short batch --
+  position ``n_batches - 2`` gathers it, ``n_batches - 1`` consumes it -- as head + tail,
+  eagerly (its captured graphs hold one-launch steps and stop before them).  With a
+  ``dp_context`` the short batch is dropped, with one warning;
 * the step's device work can be captured into a hipGraph (``capture``): batch
   cursor, step counter, ring slot and epoch buffer live on the device, so
   replays advance by themselves.
@@ -289,6 +296,8 @@ class FusedMLPEngine:
         self._host_epochs = False
         self.x_u8 = self.labels = self.order = None
         self.n_batches = 0
+        # valid rows of the epoch's last batch (begin_epoch(last_rows=...)); B: every batch is full
+        self.last_rows = self.B
         self.refresh_shadow()
 
     # ------------------------------------------------- exchange protocol
@@ -506,22 +515,45 @@ class FusedMLPEngine:
         self.n_data = self.x_u8.size(0)
         self._host_epochs = True
 
-    def begin_epoch(self, order: torch.Tensor, n_batches: int, checked: bool = False) -> None:
-        """Load one epoch's sample order ([n_batches * B] indices) and re-prime.
+    def begin_epoch(self, order: torch.Tensor, n_batches: int, checked: bool = False,
+                    last_rows: Optional[int] = None) -> None:
+        """Load one epoch's sample order and re-prime: ``n_batches * B`` indices, or with
+        ``last_rows`` (the short last batch of a ``drop_last=False`` loader, 1 <= last_rows <= B)
+        ``(n_batches - 1) * B + last_rows``.  The short batch is one optimizer step (one
+        micro-batch under ``accumulate``) whose loss and gradient are the mean over its rows
+        and whose stats row counts them.  With the in-kernel exchange (``dp_context``) it is
+        dropped, with one warning: that route has no short batch.
 
         Both order buffers get the same list, so the last step's look-ahead
         gather wraps into valid indices; the next ``begin_epoch`` re-primes."""
-        order = order.reshape(-1)[: n_batches * self.B]
-        assert n_batches >= 1 and order.numel() == n_batches * self.B
+        n_batches = int(n_batches)
+        last_rows = fused_mlp.check_last_rows(last_rows, self.B, "begin_epoch")
+        if last_rows != self.B and self.dp_ctx is not None:
+            if not getattr(self, "_short_drop_warned", False):
+                self._short_drop_warned = True
+                log.warning("fused MLP step: the in-kernel data-parallel exchange (dp_context) has no short batch "
+                            "-- its owner protocol shards the Adam state over every step -- so the last batch of "
+                            "%d rows (batch size %d) is dropped each epoch; the allreduce route trains on it",
+                            last_rows, self.B)
+            n_batches, last_rows = n_batches - 1, self.B
+        n_real = (n_batches - 1) * self.B + last_rows
+        order = order.reshape(-1)[:n_real]
+        assert n_batches >= 1 and order.numel() == n_real
         # the kernels trust indices (a host order is checked without a device sync;
         # ``checked``: the caller already did)
         if not checked or order.device.type != "cpu":
             assert int(order.max()) < self.n_data and int(order.min()) >= 0
-        if self.order is None or self.order.size(1) != order.numel() or self.n_batches != int(n_batches):
-            # the captured graph bakes the order pointer and n_batches: only a new
+        if last_rows != self.B:
+            # padded to the stride n_batches * B with a valid index (the kernels never read it)
+            order = torch.cat([order, order[:1].expand(self.B - last_rows)])
+        if (self.order is None or self.order.size(1) != order.numel() or self.n_batches != n_batches
+                or self.last_rows != last_rows):
+            # the captured graph bakes the order pointer, n_batches and last_rows: only a new
             # shape forces a re-capture, a new epoch of the same shape reuses it
-            self.order = torch.empty(2, order.numel(), dtype=torch.int64, device=self.device)
+            if self.order is None or self.order.size(1) != order.numel():
+                self.order = torch.empty(2, order.numel(), dtype=torch.int64, device=self.device)
             self._drop_graphs()
+        self.last_rows = last_rows
         if order.device.type == "cpu" and self.native:
             # staged through a pinned buffer: an async H2D copy instead of a blocking
             # pageable one; the previous epoch's copy must be done before reuse
@@ -555,6 +587,7 @@ class FusedMLPEngine:
         self.n_data = self.x_u8.size(0)
         per_rank = int(math.ceil(self.n_data / self.world_size))
         self.n_batches = per_rank // self.B
+        self.last_rows = self.B  # this mode drops the remainder
         if self.n_batches < 1:
             raise ValueError("dataset shard smaller than one batch")
         self.order = torch.empty(2, self.n_batches * self.B, dtype=torch.int64, device=self.device)
@@ -608,7 +641,14 @@ class FusedMLPEngine:
                     dh1t=self.dh1t, xring=self.xring, h1pre=self.h1pre, act=self.act, yring=self.yring,
                     head_part=self.head_part, hand=self.hand, lr=self.lr, betas=self.betas,
                     eps=self.eps, weight_decay=self.wd, lr_tensor=self.lr_tensor, adamw=self.adamw,
-                    x_scale=self.x_scale, x_shift=self.x_shift)
+                    x_scale=self.x_scale, x_shift=self.x_shift, last_rows=self.last_rows)
+
+    def _short_pos(self, pos: int) -> bool:
+        """Whether the step at epoch position ``pos`` touches the epoch's short last batch:
+        position ``n_batches - 2`` gathers it, ``n_batches - 1`` consumes it (with one or two
+        batches per epoch, every step does).  The one-launch kernel has no short batch, so an
+        engine that runs one launch per step runs these two as head + tail."""
+        return self.last_rows != self.B and pos >= self.n_batches - 2
 
     def _sgd_kw(self) -> dict:
         """The SGD arguments of the launch that applies the optimizer (MLP3_STEP /
@@ -684,8 +724,13 @@ class FusedMLPEngine:
                                       clip_part=self.clip_part, clip_max_norm=self.clip_norm,
                                       clip_out=self.clip_out, **self._sgd_kw(), **kw)
             elif self.world_size == 1 and not self.dp_loop:
-                kind = fused_mlp.MLP3_STEP1 if self.one_launch else fused_mlp.MLP3_STEP
-                fused_mlp.mlp3_launch(kind, stats=self.stats, **self._sgd_kw(), **kw)
+                # a captured graph of one-launch steps is replayed before the short batch only
+                # (_graph_ok); an eager step is placed by step_in_epoch
+                one = self.one_launch and (graph_pos is not None or not self._short_pos(self.step_in_epoch))
+                if one:  # never meets the short batch: every batch it gathers or consumes is full
+                    fused_mlp.mlp3_launch(fused_mlp.MLP3_STEP1, stats=self.stats, **{**kw, "last_rows": self.B})
+                else:
+                    fused_mlp.mlp3_launch(fused_mlp.MLP3_STEP, stats=self.stats, **self._sgd_kw(), **kw)
             elif self.dp_ctx is not None:
                 kind = fused_mlp.MLP3_STEP1_DP if self.one_launch_dp else fused_mlp.MLP3_STEP_DP
                 fused_mlp.mlp3_launch(kind, stats=self.stats, grad_scale=1.0 / self.dp_ctx[0],
@@ -714,7 +759,7 @@ class FusedMLPEngine:
             exp_avg_sq=self.exp_avg_sq, stats=self._head_row if acc else self.stats, accumulate_grad=micro > 0,
             apply_adam=fused, advance_step=closing, lr=self.lr,
             betas=self.betas, eps=self.eps, weight_decay=self.wd, lr_tensor=self.lr_tensor, adamw=self.adamw,
-            x_scale=self.x_scale, x_shift=self.x_shift,
+            x_scale=self.x_scale, x_shift=self.x_shift, last_rows=self.last_rows,
         )
         c[2] = cursor
         c[3] = int(c[3]) ^ 1
@@ -814,7 +859,7 @@ class FusedMLPEngine:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, stream=s):
                 for i in range(n):
-                    self._device_step(i if K > 1 else None)
+                    self._device_step(i)  # K == 1: only marks the step as captured
             return g
 
         try:
@@ -842,6 +887,11 @@ class FusedMLPEngine:
             full = self.n_batches // self.accumulate * self.accumulate
             if self.step_in_epoch % self.accumulate != 0 or self.step_in_epoch + k > full:
                 return False
+        if (self.last_rows != self.B and self.one_launch and self.world_size == 1 and not self.dp_loop
+                and self._short_pos(self.step_in_epoch + k - 1)):
+            # the graph holds one-launch steps: the two steps that gather and consume the
+            # epoch's short last batch run eagerly, as head + tail
+            return False
         return (self._graph is not None and self._primed and remaining >= k
                 and self.step_in_epoch + k <= self.n_batches)
 
