@@ -116,6 +116,136 @@ void sgd_step(Tensor p, Tensor g, optional<Tensor> buf, optional<Tensor> p_bf16,
   rla::launch_sgd(a, cur_stream(p));
 }
 
+// Chunk table of the *_groups_step kernels: `table` is the device copy the kernel walks,
+// `table_host` the same rows on the CPU, checked here row by row before every launch
+// (ops.optim.build_group_table makes both).  Returns the row count.
+int64_t check_group_table(const Tensor& table, const Tensor& table_host, const Tensor& p, int64_t ngroups) {
+  TORCH_CHECK(ngroups >= 1 && ngroups <= rla::kOptMaxGroups, "param groups: ", ngroups,
+              " groups, the kernel takes 1 to ", rla::kOptMaxGroups);
+  check_dev(table, "table", at::kLong);
+  TORCH_CHECK(table.device() == p.device(), "table must be on ", p.device(), ", not ", table.device());
+  TORCH_CHECK(table.dim() == 2 && table.size(1) == 3, "table must be [nchunks, 3]");
+  TORCH_CHECK(table_host.device().is_cpu() && table_host.scalar_type() == at::kLong && table_host.is_contiguous() &&
+                  table_host.sizes() == table.sizes(),
+              "table_host must be the table's rows as a contiguous int64 CPU tensor");
+  const int64_t rows = table.size(0), n = p.numel();
+  const int64_t* r = table_host.data_ptr<int64_t>();
+  for (int64_t i = 0; i < rows; ++i, r += 3) {
+    TORCH_CHECK(r[2] >= 0 && r[2] < ngroups, "table row ", i, ": group index ", r[2], " is not below the group count ",
+                ngroups);
+    TORCH_CHECK(r[0] >= 0 && r[0] % 4 == 0, "table row ", i, ": offset ", r[0], " is not a multiple of 4 elements");
+    TORCH_CHECK(r[1] > 0 && r[1] <= rla::kOptGroupChunk, "table row ", i, ": count ", r[1], " is not in [1, ",
+                rla::kOptGroupChunk, "]");
+    TORCH_CHECK(r[0] <= n - r[1], "table row ", i, ": [", r[0], ", ", r[0] + r[1], ") reaches beyond the arena's ", n,
+                " elements");
+  }
+  return rows;
+}
+
+template <class T>
+void check_per_group(const std::vector<T>& v, const char* name, int64_t ngroups) {
+  TORCH_CHECK((int64_t)v.size() == ngroups, name, " has ", v.size(), " entries for ", ngroups, " groups");
+}
+
+void adam_groups_step(Tensor p, Tensor g, Tensor m, Tensor v, optional<Tensor> p_bf16, Tensor table,
+                      Tensor table_host, std::vector<double> lr, std::vector<double> beta1,
+                      std::vector<double> beta2, std::vector<double> eps, std::vector<double> weight_decay,
+                      std::vector<bool> adamw, std::vector<bool> maximize, double grad_scale,
+                      optional<Tensor> step, std::vector<int64_t> host_step, optional<Tensor> lr_t) {
+  check_dev(p, "param", at::kFloat);
+  check_dev(g, "grad", at::kFloat);
+  check_dev(m, "exp_avg", at::kFloat);
+  check_dev(v, "exp_avg_sq", at::kFloat);
+  check_aligned(p, "param", 16);
+  check_aligned(g, "grad", 16);
+  check_aligned(m, "exp_avg", 16);
+  check_aligned(v, "exp_avg_sq", 16);
+  const int64_t n = p.numel();
+  TORCH_CHECK(g.numel() == n && m.numel() == n && v.numel() == n, "adam arena size mismatch");
+  TORCH_CHECK(g.device() == p.device() && m.device() == p.device() && v.device() == p.device(),
+              "adam arenas must be on one device");
+  const int64_t G = (int64_t)lr.size();
+  const int64_t rows = check_group_table(table, table_host, p, G);
+  check_per_group(beta1, "beta1", G);
+  check_per_group(beta2, "beta2", G);
+  check_per_group(eps, "eps", G);
+  check_per_group(weight_decay, "weight_decay", G);
+  check_per_group(adamw, "adamw", G);
+  check_per_group(maximize, "maximize", G);
+  check_per_group(host_step, "host_step", G);
+  const at::hip::HIPGuardMasqueradingAsCUDA guard(p.device());
+  rla::AdamGroupsArgs a{};
+  a.p = p.data_ptr<float>();
+  a.g = g.data_ptr<float>();
+  a.m = m.data_ptr<float>();
+  a.v = v.data_ptr<float>();
+  a.p_bf16 = ptr_or_null<uint16_t>(p_bf16, "param_bf16", at::kBFloat16, n);
+  if (a.p_bf16) check_aligned(*p_bf16, "param_bf16", 8);
+  a.n = n;
+  a.table = table.data_ptr<int64_t>();
+  a.grad_scale = (float)grad_scale;
+  a.ngroups = (int)G;
+  a.step_ptr = ptr_or_null<const int64_t>(step, "step", at::kLong, G);
+  a.lr_ptr = ptr_or_null<const float>(lr_t, "lr", at::kFloat, G);
+  for (int64_t i = 0; i < G; ++i) {
+    TORCH_CHECK(a.step_ptr || host_step[i] >= 1, "adam: step must be >= 1 (group ", i, ")");
+    rla::AdamGroupHyper& h = a.h[i];
+    h.lr = (float)lr[i]; h.beta1 = (float)beta1[i]; h.beta2 = (float)beta2[i]; h.eps = (float)eps[i];
+    h.weight_decay = (float)weight_decay[i];
+    h.adamw = adamw[i]; h.maximize = maximize[i];
+    h.host_step = host_step[i];
+  }
+  TORCH_CHECK(rla::launch_adam_groups(a, rows, cur_stream(p)) == 0, "adam_groups launch failed");
+}
+
+void sgd_groups_step(Tensor p, Tensor g, optional<Tensor> buf, optional<Tensor> p_bf16, Tensor table,
+                     Tensor table_host, std::vector<double> lr, std::vector<double> momentum,
+                     std::vector<double> dampening, std::vector<double> weight_decay, std::vector<bool> nesterov,
+                     std::vector<bool> maximize, double grad_scale, optional<Tensor> step,
+                     std::vector<int64_t> host_step, optional<Tensor> lr_t) {
+  check_dev(p, "param", at::kFloat);
+  check_dev(g, "grad", at::kFloat);
+  check_aligned(p, "param", 16);
+  check_aligned(g, "grad", 16);
+  const int64_t n = p.numel();
+  TORCH_CHECK(g.numel() == n, "sgd arena size mismatch");
+  TORCH_CHECK(g.device() == p.device(), "sgd arenas must be on one device");
+  const int64_t G = (int64_t)lr.size();
+  const int64_t rows = check_group_table(table, table_host, p, G);
+  check_per_group(momentum, "momentum", G);
+  check_per_group(dampening, "dampening", G);
+  check_per_group(weight_decay, "weight_decay", G);
+  check_per_group(nesterov, "nesterov", G);
+  check_per_group(maximize, "maximize", G);
+  check_per_group(host_step, "host_step", G);
+  const at::hip::HIPGuardMasqueradingAsCUDA guard(p.device());
+  rla::SGDGroupsArgs a{};
+  a.p = p.data_ptr<float>();
+  a.g = g.data_ptr<float>();
+  a.buf = ptr_or_null<float>(buf, "momentum_buffer", at::kFloat, n);
+  if (a.buf) {
+    check_aligned(*buf, "momentum_buffer", 16);
+    TORCH_CHECK(buf->device() == p.device(), "sgd arenas must be on one device");
+  }
+  a.p_bf16 = ptr_or_null<uint16_t>(p_bf16, "param_bf16", at::kBFloat16, n);
+  if (a.p_bf16) check_aligned(*p_bf16, "param_bf16", 8);
+  a.n = n;
+  a.table = table.data_ptr<int64_t>();
+  a.grad_scale = (float)grad_scale;
+  a.ngroups = (int)G;
+  a.step_ptr = ptr_or_null<const int64_t>(step, "step", at::kLong, G);
+  a.lr_ptr = ptr_or_null<const float>(lr_t, "lr", at::kFloat, G);
+  for (int64_t i = 0; i < G; ++i) {
+    TORCH_CHECK(momentum[i] == 0.0 || a.buf != nullptr, "sgd: momentum needs a buffer (group ", i, ")");
+    rla::SGDGroupHyper& h = a.h[i];
+    h.lr = (float)lr[i]; h.momentum = (float)momentum[i]; h.dampening = (float)dampening[i];
+    h.weight_decay = (float)weight_decay[i];
+    h.nesterov = nesterov[i]; h.maximize = maximize[i];
+    h.host_step = host_step[i];
+  }
+  TORCH_CHECK(rla::launch_sgd_groups(a, rows, cur_stream(p)) == 0, "sgd_groups launch failed");
+}
+
 void multi_copy(Tensor table, double scale, bool accumulate) {
   check_dev(table, "table", at::kLong);
   TORCH_CHECK(table.dim() == 2 && table.size(1) == 4, "table must be [nchunks, 4]");
@@ -1137,6 +1267,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "gfx950 HIP kernels of ray_lightning_accelerators_amd";
   m.def("adam_step", &adam_step, "fused Adam over a flat fp32 arena");
   m.def("sgd_step", &sgd_step, "fused SGD (momentum/nesterov/wd) over a flat fp32 arena");
+  m.def("adam_groups_step", &adam_groups_step, "fused Adam over interleaved param groups via a chunk table");
+  m.def("sgd_groups_step", &sgd_groups_step, "fused SGD over interleaved param groups via a chunk table");
+  m.attr("OPT_MAX_GROUPS") = rla::kOptMaxGroups;
+  m.attr("OPT_GROUP_CHUNK") = rla::kOptGroupChunk;
   m.def("multi_copy", &multi_copy, "multi-tensor copy/scale/cast via a chunk table");
   m.def("scale_", &scale_, "in-place scale of an fp32 arena");
   m.def("sumsq", &sumsq, "sum of squares of an fp32 arena");

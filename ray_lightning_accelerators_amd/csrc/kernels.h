@@ -38,8 +38,61 @@ struct SGDArgs {
   const float* lr_ptr;
 };
 
+// Param groups that interleave in the arena (sgd_groups_kernel / adam_groups_kernel): ONE
+// launch walks a device chunk table of 3 x int64 rows {arena element offset, element count,
+// group index}, one workgroup per row.  A row lies inside one group, starts on a multiple of
+// 4 elements and holds at most kOptGroupChunk of them; elements that no row covers are
+// neither read nor written.  Each group's hyper-parameters travel by value; its step counter
+// and learning rate are read from step_ptr[group] / lr_ptr[group] when those are given.
+constexpr int kOptMaxGroups = 8;
+constexpr int kOptGroupChunk = 16384;
+
+struct AdamGroupHyper {
+  float lr, beta1, beta2, eps, weight_decay;
+  int adamw, maximize;
+  int64_t host_step;  // used when step_ptr is null
+};
+
+struct SGDGroupHyper {
+  float lr, momentum, dampening, weight_decay;
+  int nesterov, maximize;
+  int64_t host_step;
+};
+
+struct AdamGroupsArgs {
+  float* p;
+  const float* g;
+  float* m;
+  float* v;
+  uint16_t* p_bf16;         // optional, arena-shaped
+  int64_t n;                // elements of p: no row may reach beyond it
+  const int64_t* table;     // device [rows, 3]
+  float grad_scale;
+  int ngroups;
+  const int64_t* step_ptr;  // device [ngroups] (already incremented) or null
+  const float* lr_ptr;      // device [ngroups] or null
+  AdamGroupHyper h[kOptMaxGroups];
+};
+
+struct SGDGroupsArgs {
+  float* p;
+  const float* g;
+  float* buf;               // arena-shaped; may be null when no group has momentum
+  uint16_t* p_bf16;
+  int64_t n;
+  const int64_t* table;
+  float grad_scale;
+  int ngroups;
+  const int64_t* step_ptr;
+  const float* lr_ptr;
+  SGDGroupHyper h[kOptMaxGroups];
+};
+
 void launch_adam(const AdamArgs& a, hipStream_t stream);
 void launch_sgd(const SGDArgs& a, hipStream_t stream);
+// -1: ngroups outside [1, kOptMaxGroups]; rows <= 0 launches nothing
+int launch_adam_groups(const AdamGroupsArgs& a, int64_t rows, hipStream_t stream);
+int launch_sgd_groups(const SGDGroupsArgs& a, int64_t rows, hipStream_t stream);
 void launch_multi_copy(const int64_t* table, int64_t nchunks, float scale, int accumulate,
                        hipStream_t stream);
 void launch_scale(float* x, int64_t n, float s, hipStream_t stream);

@@ -154,6 +154,153 @@ void launch_sgd(const SGDArgs& a, hipStream_t stream) {
 }
 
 // ---------------------------------------------------------------------------
+// Param groups that interleave in the arena (weight decay on conv / linear weights, none
+// on norm parameters and biases: 108 alternating runs on ResNet-50).  One launch walks a
+// chunk table, in multi_copy's idiom: each workgroup owns one row {arena offset, count,
+// group} and runs adam_elem / sgd_elem over it with that group's hyper-parameters, called
+// exactly as the float4 bodies of adam_kernel / sgd_kernel call them, so a row's result has
+// the bits a single-group launch over the same 4-aligned range gives (arena rows are whole
+// float4s; those kernels' scalar tails are contracted into other fmas than their bodies).
+// Elements no row covers (arena members of no group) are never touched.
+// ---------------------------------------------------------------------------
+struct GroupRow {
+  int64_t off, n;
+  int group;
+  bool ok;
+};
+
+// The binding validated a host copy of the table before the launch; a row of the device
+// copy that disagrees with those checks is skipped by its whole workgroup.
+__device__ __forceinline__ GroupRow group_row(const int64_t* __restrict__ table, int64_t numel, int ngroups) {
+  const int64_t* row = table + (int64_t)blockIdx.x * 3;
+  GroupRow r;
+  r.off = row[0];
+  r.n = row[1];
+  const int64_t gi = row[2];
+  r.ok = gi >= 0 && gi < ngroups && r.off >= 0 && (r.off & 3) == 0 && r.n > 0 && r.n <= kOptGroupChunk &&
+         r.off <= numel - r.n;
+  r.group = r.ok ? __builtin_amdgcn_readfirstlane((int)gi) : 0;
+  return r;
+}
+
+__global__ __launch_bounds__(kOptThreads) void adam_groups_kernel(AdamGroupsArgs ga) {
+  const GroupRow r = group_row(ga.table, ga.n, ga.ngroups);
+  if (!r.ok) return;  // uniform over the workgroup: nobody reaches the barrier below
+  const AdamGroupHyper& h = ga.h[r.group];
+  AdamArgs a{};
+  a.p = ga.p + r.off;
+  a.g = ga.g + r.off;
+  a.m = ga.m + r.off;
+  a.v = ga.v + r.off;
+  a.p_bf16 = ga.p_bf16 ? ga.p_bf16 + r.off : nullptr;
+  a.n = r.n;
+  a.lr = h.lr; a.beta1 = h.beta1; a.beta2 = h.beta2; a.eps = h.eps;
+  a.weight_decay = h.weight_decay; a.grad_scale = ga.grad_scale;
+  a.adamw = h.adamw; a.maximize = h.maximize;
+  a.step_ptr = ga.step_ptr ? ga.step_ptr + r.group : nullptr;
+  a.host_step = h.host_step;
+  a.lr_ptr = ga.lr_ptr ? ga.lr_ptr + r.group : nullptr;
+  __shared__ float s_lr, s_step_size, s_bc2_sqrt;
+  adam_scalars(a, &s_lr, &s_step_size, &s_bc2_sqrt);
+  const float lr = s_lr, step_size = s_step_size, bc2_sqrt = s_bc2_sqrt;
+  const int64_t n4 = a.n >> 2;
+  F4* p4 = reinterpret_cast<F4*>(a.p);
+  const F4* g4 = reinterpret_cast<const F4*>(a.g);
+  F4* m4 = reinterpret_cast<F4*>(a.m);
+  F4* v4 = reinterpret_cast<F4*>(a.v);
+  for (int64_t i = threadIdx.x; i < n4; i += blockDim.x) {
+    F4 p = p4[i], m = m4[i], v = v4[i];
+    const F4 g = g4[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      p.v[k] = adam_elem(p.v[k], g.v[k] * a.grad_scale, m.v[k], v.v[k], lr, step_size, bc2_sqrt, a);
+    p4[i] = p; m4[i] = m; v4[i] = v;
+    if (a.p_bf16) {
+      uint2 packed;
+      packed.x = (uint32_t)f2bf_bits(p.v[0]) | ((uint32_t)f2bf_bits(p.v[1]) << 16);
+      packed.y = (uint32_t)f2bf_bits(p.v[2]) | ((uint32_t)f2bf_bits(p.v[3]) << 16);
+      reinterpret_cast<uint2*>(a.p_bf16)[i] = packed;
+    }
+  }
+  // scalar tail of a row whose count is no multiple of 4 (arena rows always are)
+  for (int64_t i = (n4 << 2) + threadIdx.x; i < a.n; i += blockDim.x) {
+    float m = a.m[i], v = a.v[i];
+    const float p = adam_elem(a.p[i], a.g[i] * a.grad_scale, m, v, lr, step_size, bc2_sqrt, a);
+    a.p[i] = p; a.m[i] = m; a.v[i] = v;
+    if (a.p_bf16) a.p_bf16[i] = f2bf_bits(p);
+  }
+}
+
+__global__ __launch_bounds__(kOptThreads) void sgd_groups_kernel(SGDGroupsArgs ga) {
+  const GroupRow r = group_row(ga.table, ga.n, ga.ngroups);
+  if (!r.ok) return;
+  const SGDGroupHyper& h = ga.h[r.group];
+  SGDArgs a{};
+  a.p = ga.p + r.off;
+  a.g = ga.g + r.off;
+  a.buf = ga.buf ? ga.buf + r.off : nullptr;
+  a.p_bf16 = ga.p_bf16 ? ga.p_bf16 + r.off : nullptr;
+  a.n = r.n;
+  a.lr = h.lr;
+  // a group with momentum but no buffer cannot come from the binding; it steps without momentum
+  a.momentum = a.buf ? h.momentum : 0.f;
+  a.dampening = h.dampening;
+  a.weight_decay = h.weight_decay; a.grad_scale = ga.grad_scale;
+  a.nesterov = h.nesterov; a.maximize = h.maximize;
+  __shared__ float s_lr;
+  __shared__ int s_first;
+  if (threadIdx.x == 0) {
+    const int64_t t = ga.step_ptr ? ga.step_ptr[r.group] : h.host_step;
+    s_lr = ga.lr_ptr ? ga.lr_ptr[r.group] : a.lr;
+    s_first = (t <= 1) ? 1 : 0;
+  }
+  __syncthreads();
+  const float lr = s_lr;
+  const bool first = s_first != 0;
+  const int64_t n4 = a.n >> 2;
+  F4* p4 = reinterpret_cast<F4*>(a.p);
+  const F4* g4 = reinterpret_cast<const F4*>(a.g);
+  F4* b4 = reinterpret_cast<F4*>(a.buf);
+  for (int64_t i = threadIdx.x; i < n4; i += blockDim.x) {
+    F4 p = p4[i];
+    const F4 g = g4[i];
+    // momentum 0: the velocity under this row is neither loaded nor stored
+    F4 b = (a.momentum != 0.f) ? b4[i] : F4{{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) p.v[k] = sgd_elem(p.v[k], g.v[k] * a.grad_scale, b.v[k], first, lr, a);
+    p4[i] = p;
+    if (a.momentum != 0.f) b4[i] = b;
+    if (a.p_bf16) {
+      uint2 packed;
+      packed.x = (uint32_t)f2bf_bits(p.v[0]) | ((uint32_t)f2bf_bits(p.v[1]) << 16);
+      packed.y = (uint32_t)f2bf_bits(p.v[2]) | ((uint32_t)f2bf_bits(p.v[3]) << 16);
+      reinterpret_cast<uint2*>(a.p_bf16)[i] = packed;
+    }
+  }
+  for (int64_t i = (n4 << 2) + threadIdx.x; i < a.n; i += blockDim.x) {
+    float b = (a.momentum != 0.f) ? a.buf[i] : 0.f;
+    const float p = sgd_elem(a.p[i], a.g[i] * a.grad_scale, b, first, lr, a);
+    a.p[i] = p;
+    if (a.momentum != 0.f) a.buf[i] = b;
+    if (a.p_bf16) a.p_bf16[i] = f2bf_bits(p);
+  }
+}
+
+int launch_adam_groups(const AdamGroupsArgs& a, int64_t rows, hipStream_t stream) {
+  if (a.ngroups < 1 || a.ngroups > kOptMaxGroups) return -1;
+  if (rows <= 0) return 0;
+  hipLaunchKernelGGL(adam_groups_kernel, dim3((unsigned)rows), dim3(kOptThreads), 0, stream, a);
+  return 0;
+}
+
+int launch_sgd_groups(const SGDGroupsArgs& a, int64_t rows, hipStream_t stream) {
+  if (a.ngroups < 1 || a.ngroups > kOptMaxGroups) return -1;
+  if (rows <= 0) return 0;
+  hipLaunchKernelGGL(sgd_groups_kernel, dim3((unsigned)rows), dim3(kOptThreads), 0, stream, a);
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
 // Multi-tensor copy / scale / cast (bucket flatten, unflatten, bf16 compress).
 //
 // `table` holds one 4 x int64 row per chunk: {src_addr, dst_addr, numel, dtypes}

@@ -237,14 +237,18 @@ class LightningResNet50(LightningModule):
     (forward, backward, DDP bucket all-reduce, fused SGD) in one hipGraph and
     replays it (``lightning/graph_step.py``); with the resident synthetic set the
     batches are gathered on the device inside that graph.  Parameters are
-    channels_last (NHWC convolutions on MFMA, no per-use weight re-layout)."""
+    channels_last (NHWC convolutions on MFMA, no per-use weight re-layout).
+
+    ``config["no_decay_norm_bias"] = True``: weight decay on the ``dim > 1`` parameters
+    only, none on BatchNorm parameters and biases (two param groups)."""
 
     hip_graph_step = True
 
     def __init__(self, config: Optional[dict] = None):
         super().__init__()
         cfg = dict(lr=0.1, momentum=0.9, weight_decay=5e-5, batch_size=64, num_classes=1000,
-                   image_size=224, n_train=512, n_val=0, fused_bn=True, num_workers=0)
+                   image_size=224, n_train=512, n_val=0, fused_bn=True, num_workers=0,
+                   no_decay_norm_bias=False)
         cfg.update(config or {})
         self.cfg = cfg
         self.model = resnet50(cfg["num_classes"], fused_bn=cfg["fused_bn"]).to(memory_format=torch.channels_last)
@@ -276,6 +280,12 @@ class LightningResNet50(LightningModule):
             self.log("val_acc", torch.stack([o["val_acc"] for o in outputs]).mean())
 
     def configure_optimizers(self):
+        if self.cfg["no_decay_norm_bias"]:
+            # two groups that alternate in the arena (108 runs): stepped by one table-driven launch
+            params = list(self.parameters())
+            groups = [{"params": [p for p in params if p.dim() > 1], "weight_decay": self.cfg["weight_decay"]},
+                      {"params": [p for p in params if p.dim() <= 1], "weight_decay": 0.0}]
+            return torch.optim.SGD(groups, lr=self.cfg["lr"], momentum=self.cfg["momentum"])
         return torch.optim.SGD(self.parameters(), lr=self.cfg["lr"], momentum=self.cfg["momentum"],
                                weight_decay=self.cfg["weight_decay"])
 

@@ -62,6 +62,7 @@ def use_native(t: torch.Tensor) -> bool:
 
 
 from .optim import fused_adam_, fused_sgd_, multi_copy, build_copy_table, scale_, sumsq  # noqa: E402
+from .optim import build_group_table, fused_adam_groups_, fused_sgd_groups_  # noqa: E402
 from .fused_mlp import (  # noqa: E402
     mlp_param_count,
     mlp_supported,
@@ -80,6 +81,9 @@ __all__ = [
     "use_native",
     "fused_adam_",
     "fused_sgd_",
+    "build_group_table",
+    "fused_adam_groups_",
+    "fused_sgd_groups_",
     "multi_copy",
     "build_copy_table",
     "scale_",

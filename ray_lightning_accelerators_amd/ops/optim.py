@@ -129,6 +129,176 @@ def fused_sgd_(
             p_bf16.copy_(p)
 
 
+MAX_OPT_GROUPS = 8  # csrc/kernels.h kOptMaxGroups
+GROUP_CHUNK_ELEMS = 16384  # csrc/kernels.h kOptGroupChunk
+
+
+def build_group_table(arena_offsets: Sequence[Tuple[int, int]], group_of_param: Sequence[Optional[int]],
+                      device=None, chunk: int = GROUP_CHUNK_ELEMS, align: int = 4) -> torch.Tensor:
+    """Chunk table of :func:`fused_sgd_groups_` / :func:`fused_adam_groups_`: int64
+    ``[rows, 3]``, one row ``(arena element offset, element count, group index)`` per chunk.
+
+    ``arena_offsets`` are the arena's ``(offset, numel)`` per member in arena order
+    (``ParamArena.offsets``: every offset a multiple of ``align``), ``group_of_param`` each
+    member's group index, or ``None`` for a member of no group.  A chunk is a run of
+    consecutive members of one group, the alignment pad after each member included, cut into
+    pieces of at most ``chunk`` elements; members of no group are covered by no row.
+
+    Built once per optimizer, never inside a graph capture.  On a GPU the table is copied
+    through pinned memory; the host rows stay attached (``table._rla_host``), and the
+    bindings check them before every launch."""
+    if len(arena_offsets) != len(group_of_param):
+        raise ValueError("build_group_table: one group index (or None) per arena member")
+    if chunk <= 0 or chunk % align:
+        raise ValueError(f"build_group_table: chunk must be a positive multiple of {align}")
+    rows: List[List[int]] = []
+    run_start = run_end = 0
+    run_group: Optional[int] = None
+
+    def flush():
+        if run_group is not None:
+            for off, cnt in iter_chunks(run_end - run_start, chunk):
+                rows.append([run_start + off, cnt, run_group])
+
+    prev_end = 0
+    for (off, n), grp in zip(arena_offsets, group_of_param):
+        if off % align or off < prev_end:
+            raise ValueError("build_group_table: arena offsets must be aligned and ascending")
+        end = off + (n + align - 1) // align * align
+        prev_end = end
+        grp = None if grp is None or grp < 0 else int(grp)
+        if grp is not None and grp == run_group and off == run_end:
+            run_end = end
+            continue
+        flush()
+        run_start, run_end, run_group = off, end, grp
+    flush()
+    host = torch.tensor(rows, dtype=torch.int64).reshape(-1, 3)
+    dev = torch.device(device if device is not None else "cpu")
+    if dev.type != "cuda":
+        return host
+    pinned = host.pin_memory()
+    table = pinned.to(dev, non_blocking=True)
+    table._rla_pinned = pinned
+    table._rla_host = host
+    return table
+
+
+def _table_host(table: torch.Tensor) -> torch.Tensor:
+    host = getattr(table, "_rla_host", None)
+    # a table that build_group_table did not make: one device read (not capturable)
+    return host if host is not None else table.detach().cpu()
+
+
+def _group_steps(steps, ngroups: int) -> Tuple[Optional[torch.Tensor], List[int]]:
+    if isinstance(steps, torch.Tensor):
+        return steps, [0] * ngroups
+    steps = [int(s) for s in steps]
+    if len(steps) != ngroups:
+        raise ValueError(f"{len(steps)} step counters for {ngroups} param groups")
+    return None, steps
+
+
+def _check_groups(groups: Sequence[dict]) -> int:
+    if not 1 <= len(groups) <= MAX_OPT_GROUPS:
+        raise RuntimeError(f"param groups: {len(groups)} groups, the kernel takes 1 to {MAX_OPT_GROUPS}")
+    return len(groups)
+
+
+def _reference_rows(table: torch.Tensor, ngroups: int, numel: int) -> List[List[int]]:
+    rows = _table_host(table).tolist()
+    for i, (off, cnt, grp) in enumerate(rows):
+        if not 0 <= grp < ngroups:
+            raise RuntimeError(f"table row {i}: group index {grp} is not below the group count {ngroups}")
+        if off < 0 or cnt <= 0 or off + cnt > numel:
+            raise RuntimeError(f"table row {i}: [{off}, {off + cnt}) reaches beyond the arena's {numel} elements")
+    return rows
+
+
+def fused_adam_groups_(
+    p: torch.Tensor,
+    g: torch.Tensor,
+    m: torch.Tensor,
+    v: torch.Tensor,
+    table: torch.Tensor,
+    groups: Sequence[dict],
+    *,
+    steps,
+    grad_scale: float = 1.0,
+    lr_tensor: Optional[torch.Tensor] = None,
+    p_bf16: Optional[torch.Tensor] = None,
+) -> None:
+    """One Adam/AdamW step of every param group in ONE launch, for groups that interleave
+    in the arena.  ``p``, ``g``, ``m``, ``v`` (and ``p_bf16``) are whole arena-shaped
+    buffers, ``table`` is :func:`build_group_table`'s, ``groups[i]`` holds group ``i``'s
+    ``lr``, ``betas``, ``eps``, ``weight_decay``, ``adamw``, ``maximize``.
+
+    ``steps``: the 1-based step number of each group AFTER this update, a list of ints or
+    a device int64 ``[G]`` tensor; ``lr_tensor``: a device fp32 ``[G]`` tensor that
+    overrides the groups' ``lr`` (graph replay).  Elements that no table row covers are
+    neither read nor written.  Alignment contract as :func:`fused_adam_`.  On the CPU (or
+    with ``RLA_DISABLE_NATIVE=1``) :func:`fused_adam_` runs over each row's slice."""
+    G = _check_groups(groups)
+    step_t, host_steps = _group_steps(steps, G)
+    if use_native(p):
+        require().adam_groups_step(
+            p, g, m, v, p_bf16, table, _table_host(table),
+            [float(h["lr"]) for h in groups], [float(h["betas"][0]) for h in groups],
+            [float(h["betas"][1]) for h in groups], [float(h["eps"]) for h in groups],
+            [float(h["weight_decay"]) for h in groups], [bool(h.get("adamw", False)) for h in groups],
+            [bool(h.get("maximize", False)) for h in groups], float(grad_scale), step_t, host_steps, lr_tensor,
+        )
+        return
+    ts = [int(s) for s in step_t.tolist()] if step_t is not None else host_steps
+    lrs = [float(x) for x in lr_tensor.tolist()] if lr_tensor is not None else [float(h["lr"]) for h in groups]
+    for off, cnt, grp in _reference_rows(table, G, p.numel()):
+        h = groups[grp]
+        s = slice(off, off + cnt)
+        fused_adam_(p[s], g[s], m[s], v[s], lr=lrs[grp], betas=tuple(h["betas"]), eps=h["eps"],
+                    weight_decay=h["weight_decay"], grad_scale=grad_scale, adamw=bool(h.get("adamw", False)),
+                    maximize=bool(h.get("maximize", False)), step=ts[grp],
+                    p_bf16=p_bf16[s] if p_bf16 is not None else None)
+
+
+def fused_sgd_groups_(
+    p: torch.Tensor,
+    g: torch.Tensor,
+    buf: Optional[torch.Tensor],
+    table: torch.Tensor,
+    groups: Sequence[dict],
+    *,
+    steps,
+    grad_scale: float = 1.0,
+    lr_tensor: Optional[torch.Tensor] = None,
+    p_bf16: Optional[torch.Tensor] = None,
+) -> None:
+    """One SGD step of every param group in ONE launch (see :func:`fused_adam_groups_`).
+    ``groups[i]``: ``lr``, ``momentum``, ``dampening``, ``weight_decay``, ``nesterov``,
+    ``maximize``.  ``buf`` is one arena-shaped velocity buffer (``None`` when no group has
+    momentum); under a group with ``momentum == 0`` it is neither read nor written."""
+    G = _check_groups(groups)
+    step_t, host_steps = _group_steps(steps, G)
+    if use_native(p):
+        require().sgd_groups_step(
+            p, g, buf, p_bf16, table, _table_host(table),
+            [float(h["lr"]) for h in groups], [float(h.get("momentum", 0.0)) for h in groups],
+            [float(h.get("dampening", 0.0)) for h in groups], [float(h.get("weight_decay", 0.0)) for h in groups],
+            [bool(h.get("nesterov", False)) for h in groups], [bool(h.get("maximize", False)) for h in groups],
+            float(grad_scale), step_t, host_steps, lr_tensor,
+        )
+        return
+    ts = [int(s) for s in step_t.tolist()] if step_t is not None else host_steps
+    lrs = [float(x) for x in lr_tensor.tolist()] if lr_tensor is not None else [float(h["lr"]) for h in groups]
+    for off, cnt, grp in _reference_rows(table, G, p.numel()):
+        h = groups[grp]
+        s = slice(off, off + cnt)
+        mom = float(h.get("momentum", 0.0))
+        fused_sgd_(p[s], g[s], buf[s] if mom != 0 else None, lr=lrs[grp], momentum=mom,
+                   dampening=float(h.get("dampening", 0.0)), weight_decay=float(h.get("weight_decay", 0.0)),
+                   nesterov=bool(h.get("nesterov", False)), maximize=bool(h.get("maximize", False)),
+                   grad_scale=grad_scale, step=ts[grp], p_bf16=p_bf16[s] if p_bf16 is not None else None)
+
+
 _DT = {torch.float32: 0, torch.bfloat16: 1}
 CHUNK_ELEMS = 16384
 

@@ -8,18 +8,41 @@ slice the group covers.  Optimizer state lives in arena-shaped buffers and is
 exposed through ``optimizer.state[p]`` as per-parameter views, so
 ``optimizer.state_dict()`` keeps torch's exact format (Lightning checkpoint
 ``optimizer_states``).
+
+Param groups that interleave in the arena (the arena is in ``model.parameters()``
+order, so "weight decay on weights, none on norm parameters and biases" alternates
+108 times on ResNet-50) are stepped through a chunk table instead: one launch for
+ALL groups, each chunk with its own group's hyper-parameters
+(``ops.optim.fused_sgd_groups_`` / ``fused_adam_groups_``).  Optimizers whose
+groups are all contiguous arena ranges keep the per-group launches.
 """
 from __future__ import annotations
 
+import logging
 import types
 from typing import Callable, List, Optional
 
 import torch
 
-from ..ops.optim import fused_adam_, fused_sgd_
+from ..ops.optim import (MAX_OPT_GROUPS, build_group_table, fused_adam_, fused_adam_groups_, fused_sgd_,
+                         fused_sgd_groups_)
 from .arena import ParamArena
 
+log = logging.getLogger(__name__)
+
 SUPPORTED = (torch.optim.Adam, torch.optim.AdamW, torch.optim.SGD)
+_logged = set()
+
+
+def _refuse(why: str) -> bool:
+    if why not in _logged:
+        _logged.add(why)
+        log.info(f"optimizer not fused onto the parameter arena: {why}")
+    return False
+
+
+def _all_contiguous(opt: torch.optim.Optimizer, arena: ParamArena) -> bool:
+    return all(arena.contiguous_range(g["params"]) is not None for g in opt.param_groups)
 
 
 def can_fuse(opt: torch.optim.Optimizer, arena: ParamArena) -> bool:
@@ -28,10 +51,22 @@ def can_fuse(opt: torch.optim.Optimizer, arena: ParamArena) -> bool:
     for g in opt.param_groups:
         if g.get("amsgrad") or g.get("differentiable"):
             return False
-        if arena.contiguous_range(g["params"]) is None:
-            return False
         if isinstance(opt, torch.optim.SGD) and g.get("momentum", 0) == 0 and g.get("dampening", 0) != 0:
             return False
+    if _all_contiguous(opt, arena):
+        return True
+    # groups that interleave in the arena: disjoint sets of arena members, any order
+    seen = set()
+    for g in opt.param_groups:
+        for p in g["params"]:
+            if arena.index_of(p) is None:
+                return _refuse("a param group holds a parameter outside the arena")
+            if id(p) in seen:
+                return _refuse("a parameter is in two param groups")
+            seen.add(id(p))
+    if len(opt.param_groups) > MAX_OPT_GROUPS:
+        return _refuse(f"{len(opt.param_groups)} param groups interleave in the arena, the grouped kernel "
+                       f"takes {MAX_OPT_GROUPS}")
     return True
 
 
@@ -61,6 +96,87 @@ class _GroupState:
             self.lr_host = lr
 
 
+class _TableGroupState(_GroupState):
+    """One group of an optimizer stepped through the chunk table: no arena range of its
+    own (``start`` 0: the state buffers are arena-shaped and shared by all groups), its
+    device scalars are one-element slices of the plan's ``[G]`` tensors."""
+
+    def __init__(self, plan: "_TablePlan", kind: str):
+        self.start, self.end = 0, plan.arena.numel
+        self.kind = kind
+        if kind == "adam":
+            self.m, self.v = plan.m, plan.v
+        else:
+            self.buf = plan.buf
+        self.step = 0
+        self.step_t = self.lr_t = None
+        self.lr_host = None
+
+
+class _TablePlan:
+    """Chunk table, shared state buffers and ``[G]`` device scalars of one optimizer whose
+    groups interleave in the arena; built once, at fuse time."""
+
+    def __init__(self, opt: torch.optim.Optimizer, arena: ParamArena, kind: str):
+        if torch.cuda.is_available() and arena.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("fuse_optimizer: the chunk table cannot be built inside a graph capture")
+        self.arena, self.kind = arena, kind
+        group_of = [None] * len(arena.params)
+        for gi, g in enumerate(opt.param_groups):
+            for p in g["params"]:
+                group_of[arena.index_of(p)] = gi
+        self.table = build_group_table(arena.offsets, group_of, device=arena.device)
+        dev = arena.device
+        self.m = self.v = self.buf = None
+        if kind == "adam":
+            self.m = torch.zeros(arena.numel, device=dev)
+            self.v = torch.zeros(arena.numel, device=dev)
+        elif any(g.get("momentum", 0) != 0 for g in opt.param_groups):
+            self.buf = torch.zeros(arena.numel, device=dev)
+        self.step_all: Optional[torch.Tensor] = None  # [G] int64, advanced by ONE add_
+        self.lr_all: Optional[torch.Tensor] = None    # [G] fp32
+        self.groups = [_TableGroupState(self, kind) for _ in opt.param_groups]
+
+    def enable_device_scalars(self, opt: torch.optim.Optimizer) -> None:
+        if self.step_all is not None:
+            return
+        dev = self.arena.device
+        self.step_all = torch.tensor([gs.step for gs in self.groups], dtype=torch.int64, device=dev)
+        self.lr_all = torch.tensor([float(g["lr"]) for g in opt.param_groups], dtype=torch.float32, device=dev)
+        for i, (g, gs) in enumerate(zip(opt.param_groups, self.groups)):
+            gs.step_t, gs.lr_t = self.step_all[i:i + 1], self.lr_all[i:i + 1]
+            gs.lr_host = float(g["lr"])
+
+    def step(self, opt: torch.optim.Optimizer, scale: float, adamw: bool) -> None:
+        arena, groups = self.arena, self.groups
+        for gs in groups:
+            gs.step += 1
+        steps, lr_t = [gs.step for gs in groups], None
+        if self.step_all is not None:
+            if self.step_all.device.type != "cuda" or not torch.cuda.is_current_stream_capturing():
+                for g, gs in zip(opt.param_groups, groups):
+                    gs.sync_lr(float(g["lr"]))
+            self.step_all.add_(1)
+            # (CPU: never captured -- the host learning rates, in the reference's double precision)
+            steps, lr_t = self.step_all, (self.lr_all if self.lr_all.is_cuda else None)
+        if self.kind == "adam":
+            hyper = [dict(lr=float(g["lr"]), betas=tuple(g["betas"]), eps=g["eps"], weight_decay=g["weight_decay"],
+                          adamw=adamw, maximize=g.get("maximize", False)) for g in opt.param_groups]
+            fused_adam_groups_(arena.data, arena.grad, self.m, self.v, self.table, hyper, steps=steps,
+                               grad_scale=scale, lr_tensor=lr_t, p_bf16=arena.bf16)
+            for g, gs in zip(opt.param_groups, groups):
+                for q in g["params"]:
+                    st = opt.state.get(q)
+                    if st is not None and "step" in st:
+                        st["step"].fill_(float(gs.step))
+        else:
+            hyper = [dict(lr=float(g["lr"]), momentum=g.get("momentum", 0.0), dampening=g.get("dampening", 0.0),
+                          weight_decay=g.get("weight_decay", 0.0), nesterov=g.get("nesterov", False),
+                          maximize=g.get("maximize", False)) for g in opt.param_groups]
+            fused_sgd_groups_(arena.data, arena.grad, self.buf, self.table, hyper, steps=steps, grad_scale=scale,
+                              lr_tensor=lr_t, p_bf16=arena.bf16)
+
+
 def fuse_optimizer(opt: torch.optim.Optimizer, arena: ParamArena,
                    grad_scale_fn: Optional[Callable[[], float]] = None) -> torch.optim.Optimizer:
     """Rebind ``opt.step`` / ``opt.zero_grad`` to fused arena kernels (in place)."""
@@ -69,9 +185,14 @@ def fuse_optimizer(opt: torch.optim.Optimizer, arena: ParamArena,
     kind = "sgd" if isinstance(opt, torch.optim.SGD) else "adam"
     adamw = isinstance(opt, torch.optim.AdamW)
     groups: List[_GroupState] = []
-    for g in opt.param_groups:
-        s, e = arena.contiguous_range(g["params"])
-        gs = _GroupState(arena, s, e, kind)
+    # groups that interleave in the arena: one table-driven launch for all of them
+    plan = None if _all_contiguous(opt, arena) else _TablePlan(opt, arena, kind)
+    for gi, g in enumerate(opt.param_groups):
+        if plan is not None:
+            gs, s = plan.groups[gi], 0
+        else:
+            s, e = arena.contiguous_range(g["params"])
+            gs = _GroupState(arena, s, e, kind)
         groups.append(gs)
         # expose per-param views in torch's state layout
         for p in g["params"]:
@@ -90,6 +211,9 @@ def fuse_optimizer(opt: torch.optim.Optimizer, arena: ParamArena,
                 loss = closure()
         scale = grad_scale_fn() if grad_scale_fn is not None else 1.0
         arena.rebind_all()
+        if plan is not None:
+            plan.step(self, scale, adamw)
+            return loss
         for g, gs in zip(self.param_groups, groups):
             p = arena.data[gs.start:gs.end]
             gr = arena.grad[gs.start:gs.end]
@@ -153,6 +277,9 @@ def fuse_optimizer(opt: torch.optim.Optimizer, arena: ParamArena,
     def enable_device_scalars(self):
         """Step counter and learning rate as device scalars (graph-captured steps:
         ``lightning/graph_step.py``).  The host ``step`` keeps counting too."""
+        if plan is not None:
+            plan.enable_device_scalars(self)
+            return
         for g, gs in zip(self.param_groups, groups):
             if gs.step_t is None:
                 gs.step_t = torch.full((1,), gs.step, dtype=torch.int64, device=arena.device)
@@ -170,6 +297,13 @@ def fuse_optimizer(opt: torch.optim.Optimizer, arena: ParamArena,
                 if st is not None and "step" in st and float(st["step"]) != float(gs.step):
                     st["step"].fill_(float(gs.step))
 
+    def add_param_group(self, param_group):
+        # the launches above were planned for the groups present at fuse time: a group
+        # added later would never be stepped
+        raise RuntimeError("add_param_group on an optimizer fused onto the parameter arena: its launches were "
+                           "planned for the param groups it had when it was fused; add every group before the "
+                           "optimizer is handed to the Trainer (or fuse_optimizer)")
+
     # keep torch's LR-scheduler bookkeeping happy (it wraps optimizer.step)
     step._wrapped_by_lr_sched = True
     orig_step_fn = step
@@ -184,6 +318,7 @@ def fuse_optimizer(opt: torch.optim.Optimizer, arena: ParamArena,
     opt.load_state_dict = types.MethodType(load_state_dict, opt)
     opt.enable_device_scalars = types.MethodType(enable_device_scalars, opt)
     opt.sync_host_state = types.MethodType(sync_host_state, opt)
+    opt.add_param_group = types.MethodType(add_param_group, opt)
     opt._rla_fused = True
     opt._rla_groups = groups
     return opt
