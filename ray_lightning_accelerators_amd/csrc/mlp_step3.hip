@@ -29,6 +29,14 @@
 //             MFMA over the batch from the head's transposes, Adam, bf16 shadow
 //             (row-major + transposed) refresh.
 //
+// One launch (mlp3_one_kernel, B <= 32): every block repeats the head's chain on its own CU
+// and then takes one tail role.  At the narrow widths (RowChain: 32-32, 32-64, 64-64) that
+// replicated chain runs per 16-row MFMA tile -- waves 0-3 row tile 0, waves 4-7 row tile 1,
+// the bf16 shadow weights staged once per block in LDS, every wave its row tile's logits
+// and four rows of the softmax on its own accumulators, four block barriers after H1
+// instead of six; the head kernel below and the wider one-launch widths keep the
+// block-wide phases.
+//
 // World size > 1 splits the tail: GRAD (all gradients -> `grads`, gather
 // X[t+1]) before the allreduce, ADAM (W1 tiles: Adam + the next-step partial;
 // extra blocks: flat Adam over every other parameter) after it.  PRIME computes
@@ -330,6 +338,10 @@ __device__ __forceinline__ void h1_report(const MLP3Args& a, const H1Health& h, 
 // H2^T / dH2^T / dH1^T images at OneLds offsets) for the block's own tail role;
 // no H1pre zeroing (invariant: the slot the tiles accumulate into is zero at a
 // step's start), no state advance (block 0 does it after every block's ack).
+// At the narrow widths (RowChain::fits; the flagship 32-64 among them) REP runs the
+// row-chain form below: weights staged once per block in LDS, every wave its row tile's
+// logits, four block barriers after H1 instead of six.  REP = false never does: the
+// two-launch head is the oracle of the bitwise tests.
 // REP: the one-launch tile's loads of the NEXT batch (pixels of sample `si`, tile
 // `kt`, and its label), issued by head_body right after its acknowledgement (its
 // vmcnt(0) has resolved the sample index; the rest of the head pass reads LDS
@@ -386,6 +398,8 @@ struct PreWave {
 // the kernel prologue instead (rounds 2-4), they were older than the head's loads,
 // and the ack's vmcnt(0) waited for their HBM round trips: every tile block's head
 // pass ended ~1.2 us after block 0's (profiles/r4_dp/dp_phases_wire16.log).
+// The row-chain form (RowChain) keeps the order: its staged weight loads stand where the
+// parent form's fragment loads stood, ahead of the hook, and have returned by the H1 barrier.
 constexpr int kRepHookLoads = 6;
 
 // All-reduce over one 16-lane DPP row (the softmax section's batch row): four
@@ -436,6 +450,73 @@ __device__ __forceinline__ HeadStats head_stats(const float* sZ) {
   }
   return HeadStats{0.f + loss, 0.f + correct, 0.f + cnt};
 }
+
+// Row-chain form of the replicated head pass (REP only; profiles/r20_row_chain).  After H1
+// nothing in layer 2 -> layer 3 -> softmax -> dH2 -> dH1 needs data of the other 16-row MFMA
+// tile.  Waves 0-3 own row tile 0, waves 4-7 row tile 1; member q = w % 4 of a row group owns
+// column tile q of H2 / dH2 (as the parent form's ROW2 map) and, q < TN1, of dH1.  Against
+// the parent form:
+//   weights   the block fetches the bf16 shadows of W2, W3, W3^T and W2^T once (16 bytes per
+//             thread and load, `loads` per thread where every wave fetched its own
+//             `parent_frags` fragments) and parks them in LDS behind the H1 barrier; the
+//             head's load phase is bound by the number of vector loads a CU issues;
+//   layer 3   EVERY wave computes its row tile's logits (redundant MFMAs) and keeps them in
+//             its accumulators, where a 16-lane DPP row is one batch row's 16 class slots:
+//             member q runs the softmax of accumulator row q -- four rows per wave as
+//             before -- with no barrier and no LDS round trip between logits and softmax;
+//   ack       an LDS arrival count behind each wave's wait instead of a barrier of its own;
+//   hand-off  H2 / dH2 go from accumulator to operand layout through the transposed images
+//             the tail roles read anyway (one 8-byte store per tile, read back with the
+//             transposing LDS read); the row-major sH2 is not written.
+// Four block barriers between the H1 barrier and the end of the head pass instead of six.
+// (Two were built and measured first -- every wave running its row tile's whole chain from
+// its own fragments -- and lost to the parent form: profiles/r20_row_chain.)
+// Admitted where no K split exists (L2 < 128), a 4-wave row group has a wave for every
+// column tile, and staging costs a thread no more loads than its fragments did.  Every
+// other width compiles the parent form.
+template <int L1, int L2>
+struct RowChain {
+  using C = Cfg3<32, L1, L2>;
+  using O = Off<L1, L2>;
+  static constexpr int parent_frags = L1 / 32 + 1 + C::KS3 + C::KSH;  // bf16x8 loads per wave, parent form
+  // The staged shadow weights (bf16 elements from One::oWts), rows padded by 8 elements so the
+  // 16 rows of a fragment read start in 16 different bank groups:
+  // W2 [L2][L1 + 8], W3 [kNC][L2 + 8], W3^T [L2][24], W2^T [L1][L2 + 8]
+  static constexpr int S2 = L1 + 8, S3 = L2 + 8, S3T = 24, S2T = L2 + 8;
+  static constexpr int oW2 = 0, oW3 = oW2 + L2 * S2, oW3T = oW3 + kNC * S3, oW2T = oW3T + L2 * S3T;
+  static constexpr int elems = oW2T + L1 * S2T;
+  // 8-element chunks of the four matrices, in that order; chunk -> (shadow offset, LDS offset)
+  static constexpr int N2 = L2 * L1 / 8, N3 = kNC * L2 / 8, N3T = L2 * 2, N2T = L1 * L2 / 8;
+  static constexpr int chunks = N2 + N3 + N3T + N2T;
+  static constexpr int loads = (chunks + kThreads - 1) / kThreads;  // per thread
+  static constexpr bool fits = C::KG3 == 1 && C::KG1 == 1 && C::TN1 <= kWaves / 2 && C::TN2 <= kWaves / 2 &&
+                               C::MT == 2 && loads <= parent_frags;
+  static constexpr size_t bytes = fits ? (size_t)elems * 2 : 0;
+  // clamped: a chunk index past the end loads shadow element 0 and is not stored (-1)
+  __device__ static __forceinline__ int chunk(int ch, int64_t& goff) {
+    int lds = -1;
+    goff = 0;
+    if (ch < N2) {
+      goff = O::W2 + (int64_t)ch * 8;
+      lds = oW2 + ch / (L1 / 8) * S2 + ch % (L1 / 8) * 8;
+    } else if (ch < N2 + N3) {
+      const int c = ch - N2;
+      goff = O::W3 + (int64_t)c * 8;
+      lds = oW3 + c / (L2 / 8) * S3 + c % (L2 / 8) * 8;
+    } else if (ch < N2 + N3 + N3T) {
+      const int c = ch - N2 - N3;
+      goff = O::W3T + (int64_t)c * 8;
+      lds = oW3T + c / 2 * S3T + c % 2 * 8;
+    } else if (ch < chunks) {
+      const int c = ch - N2 - N3 - N3T;
+      goff = O::W2T + (int64_t)c * 8;
+      lds = oW2T + c / (L2 / 8) * S2T + c % (L2 / 8) * 8;
+    }
+    return lds;
+  }
+};
+template <int L1, int L2>
+struct One;
 
 // PROBE = false: every stamp below compiles away (the one-launch production instances)
 template <int BC, int L1, int L2, bool MULTI, bool REP, class Hook = NoHook, bool PROBE = true>
@@ -566,8 +647,26 @@ __device__ __forceinline__ void head_body(const MLP3Args& a, char* smem, RepPre*
     bf16x8 w3tf[NTW2];
     // clamped address + select: the load itself is never conditional
     auto ld8z = [&](bool ok, int64_t off) { const bf16x8 v = ld8(SH + (ok ? off : 0)); return ok ? v : zero8(); };
+    // Row-chain form: the block fetches the bf16 shadows of W2, W3, W3^T and W2^T ONCE, 16
+    // bytes per thread and load (RowChain::loads per thread), in the place of the parent's
+    // fragment loads -- older than the hook's, so the acknowledgement's wait covers them --
+    // and parks them in LDS behind the H1 barrier; the waves read their fragments from there.
+    constexpr bool RC = REP && RowChain<L1, L2>::fits;
+    using R = RowChain<L1, L2>;
+    constexpr int RLD = RC ? R::loads : 1;
+    bf16x8 wst[RLD];
+    int wst_off[RLD];  // LDS element offset of the chunk in the staged weights, -1: none
+    if constexpr (RC) {
 #pragma unroll
-    for (int j = 0; j < NTW2; ++j) {
+      for (int k = 0; k < RLD; ++k) {
+        const int ch = tid + k * kThreads;
+        int64_t goff = 0;
+        wst_off[k] = R::chunk(ch, goff);
+        wst[k] = ld8(SH + goff);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < (RC ? 0 : NTW2); ++j) {
       const int nt = nt_base + kWaves * j;
       const bool ok = l2_active && nt < C::TN2;
 #pragma unroll
@@ -578,7 +677,7 @@ __device__ __forceinline__ void head_body(const MLP3Args& a, char* smem, RepPre*
     const int mt3 = w % MT, kg3 = w / MT;
     bf16x8 w3f[KPG3];
 #pragma unroll
-    for (int i = 0; i < KPG3; ++i)
+    for (int i = 0; i < (RC ? 0 : KPG3); ++i)
       w3f[i] = ld8z(kg3 < KG3 && r16 < kNC, O::W3 + (int64_t)r16 * L2 + (kg3 * KPG3 + i) * 32 + 8 * g);
     // dH1 with a short K (KG1 == 1) and few tiles: one (column, row) tile per wave
     constexpr bool ROW1 = KG1 == 1 && C::TN1 * MT <= kWaves;
@@ -587,7 +686,7 @@ __device__ __forceinline__ void head_body(const MLP3Args& a, char* smem, RepPre*
     const int mt1_base = ROW1 ? w / C::TN1 : 0;
     bf16x8 w2tf[KPG1];
 #pragma unroll
-    for (int i = 0; i < KPG1; ++i)
+    for (int i = 0; i < (RC ? 0 : KPG1); ++i)
       w2tf[i] = ld8z(kg1 < KG1, O::W2T + (int64_t)(ct1 * 16 + r16) * L2 + (kg1 * KPG1 + i) * 32 + 8 * g);
     if constexpr (REP) {
       asm volatile("" ::: "memory");  // the hook's loads stay younger than every load above
@@ -598,6 +697,10 @@ __device__ __forceinline__ void head_body(const MLP3Args& a, char* smem, RepPre*
     // LDS writes last: their waits cover only the earliest loads (in-order vmcnt)
     if (tid < NBIAS) sBias[tid] = bias_v;
     if (tid < BC) sY[tid] = yok ? (slot ? y1 : y0) : -1;
+    // row-chain form: the acknowledgement's arrival count (one per wave), two barriers ahead of its first use
+    unsigned* sArrive = (unsigned*)(smem + C::oMisc);
+    if constexpr (RC)
+      if (tid == 0) *sArrive = 0u;
     __syncthreads();  // sBias ready
     // the valid rows of the batch this head consumes: derived here, where the ring slot has
     // already made every wave wait for the counters, so no load above waits for the cursor,
@@ -642,9 +745,167 @@ __device__ __forceinline__ void head_body(const MLP3Args& a, char* smem, RepPre*
         for (int k = 0; k < 4; ++k) sH1T[(m + k) * C::TS + b] = h[k];
       }
     }
+    __bf16* sWts = (__bf16*)(smem + One<L1, L2>::oWts);  // row-chain form: the staged shadow weights
+    if constexpr (RC) {
+#pragma unroll
+      for (int k = 0; k < RLD; ++k)
+        if (wst_off[k] >= 0) *reinterpret_cast<bf16x8*>(sWts + wst_off[k]) = wst[k];
+    }
     __syncthreads();
     if (stamp_ok) a.stamps[1] = __builtin_amdgcn_s_memrealtime();
     if constexpr (!REP) copy_rows(sH1T, L1, A::H1T, row0);
+
+    if constexpr (RC) {
+      // ================= row-chain form (RowChain): four block barriers from here =================
+      // Wave w: row tile rt = w / 4, member q = w % 4.  Lane (g, r16) of an accumulator holds
+      // rows rt * 16 + 4g + i (i < 4) of column r16 -- so a 16-lane DPP row is one batch row's
+      // 16 class slots, which is what the softmax section wants.
+      // Every LDS image the tail roles read has one writer: H2^T / dH2^T tile (rt, q) member q
+      // (q < TN2), dH1^T tile (rt, q) member q (q < TN1), dZ^T and the stat slots of row
+      // rt * 16 + 4g + q member q.  The parent form's row-major sH2 and the logit slots of sZ
+      // are not written.
+      const int wu = __builtin_amdgcn_readfirstlane(w);  // scalar: the role branches below are not divergent
+      const int rt = wu >> 2, q = wu & 3;
+      const bool colw = q < C::TN2;  // a member with a column tile of H2 / dH2
+      auto wave_sync = [] {  // this wave's LDS writes, visible to its own other lanes
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      };
+      // A operand (rows rt * 16 + r16, k = 8g .. 8g + 7 of K chunk i) from an image [k][TS]
+      auto tr_a = [&](const __bf16* img, int i) {
+        const __bf16* s = img + (i * 32 + 8 * g + (r16 >> 2)) * C::TS + rt * 16 + 4 * (r16 & 3);
+        const bf16x4 lo = tr_read(s), hi = tr_read(s + 4 * C::TS);
+        return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+      };
+      // ---- the wave's weight fragments, from the staged shadows ----
+      bf16x8 rw2f[KS2], rw3tf, rw3f[KS3], rw2tf[KSH];
+      const __bf16 *sW2 = sWts + R::oW2, *sW3 = sWts + R::oW3, *sW3T = sWts + R::oW3T, *sW2T = sWts + R::oW2T;
+      const int nq = (colw ? q : 0) * 16 + r16;  // the wave's H2 / dH2 column
+#pragma unroll
+      for (int ks = 0; ks < KS2; ++ks) rw2f[ks] = ld8(sW2 + nq * R::S2 + ks * 32 + 8 * g);
+      // ---- layer 2: tile (row tile rt, column tile q), as the parent form (ROW2) ----
+      bf16x4 h2 = {(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
+      if (colw) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < KS2; ++ks)
+          acc = mfma16(ld8(sH1 + (rt * 16 + r16) * C::H1S + ks * 32 + 8 * g), rw2f[ks], acc);
+        const float bias = sBias[L1 + nq];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) h2[i] = relu_bf(acc[i] + bias);
+        *reinterpret_cast<bf16x4*>(sH2T + nq * C::TS + rt * 16 + 4 * g) = h2;
+      }
+      // the later fragments, requested here: their LDS round trip passes under the barrier
+#pragma unroll
+      for (int i = 0; i < KS3; ++i) {
+        const bf16x8 v = ld8(sW3 + (r16 < kNC ? r16 : 0) * R::S3 + i * 32 + 8 * g);
+        rw3f[i] = r16 < kNC ? v : zero8();
+      }
+      {
+        const bf16x8 v = ld8(sW3T + nq * R::S3T + (g < 2 ? 8 * g : 0));
+        rw3tf = g < 2 ? v : zero8();
+      }
+#pragma unroll
+      for (int i = 0; i < KSH; ++i)
+        rw2tf[i] = ld8(sW2T + ((q < C::TN1 ? q : 0) * 16 + r16) * R::S2T + i * 32 + 8 * g);
+      __syncthreads();  // H2^T of the row tile comes from its four waves
+      // ---- layer 3 by EVERY wave for its row tile (2 redundant MFMAs instead of a barrier
+      // and an LDS round trip between the logits and the softmax) ----
+      f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int i = 0; i < KS3; ++i) z4 = mfma16(tr_a(sH2T, i), rw3f[i], z4);
+      if (stamp_ok) a.stamps[2] = __builtin_amdgcn_s_memrealtime();  // end of the forward part
+      // ---- acknowledgement: the ordering rule of the parent form (every load of shared
+      // state of every wave has returned: vmcnt(kRepHookLoads) lgkmcnt(0)), without a
+      // barrier of its own: each wave counts itself in behind its wait, and the wave that
+      // finds the other seven already counted adds the block's acknowledgement (further
+      // down, where the count's return value costs no wait of its own).  Nobody spins.
+      asm volatile("" ::: "memory");
+      static_assert(kRepHookLoads < 16, "vmcnt immediate");
+      __builtin_amdgcn_s_waitcnt(0x0070 | kRepHookLoads);
+      asm volatile("" ::: "memory");
+      unsigned arrived = 0u;
+      if (lane == 0) arrived = __hip_atomic_fetch_add(sArrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if (pre->active) {  // as the parent form: the PreWave's fetch of the next batch, behind its own wait
+        if constexpr (PreWave<L1>::hidden) {
+          const int64_t sr = __shfl(pre->si, lane >> 1, 64);
+          dma_lds16(a.x_u8 + pre->si * kD + pre->kt * 16, pre->raw);
+          dma_lds4(reinterpret_cast<const char*>(a.labels + sr) + 4 * (lane & 1), pre->raw + 1024u);
+        } else {
+          pre->xn = *reinterpret_cast<const uint4*>(a.x_u8 + pre->si * kD + pre->kt * 16);
+          pre->yn = a.labels[pre->si];
+        }
+      }
+      // ---- log_softmax / NLL / accuracy / dZ: member q takes accumulator row q of every
+      // lane, i.e. rows rt * 16 + 4g + q -- four rows per wave as in the parent form, read
+      // from the wave's own logits.  Per row the arithmetic of the parent form, bit for bit.
+      {
+        static_assert(kNC <= kStatSlot && kNC == 10, "class slots, row sum below");
+        const int r = rt * 16 + 4 * g + q, j = r16;
+        const int y = sY[r];
+        const bool cls = j < kNC;
+        const float zq = q == 0 ? z4[0] : (q == 1 ? z4[1] : (q == 2 ? z4[2] : z4[3]));
+        const float z = cls ? zq + sBias[L1 + L2 + (cls ? j : 0)] : -INFINITY;
+        const float m = row16_max(z);
+        const int arg = row16_min(cls && z == m ? j : 16);
+        const float zy = __int_as_float(row16_or(cls && j == y ? __float_as_int(z) : 0));
+        const float p = __expf(z - m);
+        if (cls) sZ[r * 16 + j] = p;
+        wave_sync();
+        const float4 pa = ld4(sZ + r * 16), pb = ld4(sZ + r * 16 + 4);
+        const float2 pc = *reinterpret_cast<const float2*>(sZ + r * 16 + 8);
+        if (lane == 0 && arrived == kWaves - 1)  // the last wave in: the block's acknowledgement
+          __hip_atomic_fetch_add(reinterpret_cast<long long*>(a.hand + kHandAck), 1ll, __ATOMIC_RELAXED,
+                                 __HIP_MEMORY_SCOPE_AGENT);
+        __bf16 d = (__bf16)0.f;
+        {
+#pragma clang fp contract(off)
+          float sum = 0.f;
+          sum += pa.x; sum += pa.y; sum += pa.z; sum += pa.w;
+          sum += pb.x; sum += pb.y; sum += pb.z; sum += pb.w;
+          sum += pc.x; sum += pc.y;
+          const float inv = 1.f / sum;
+          if (y >= 0 && cls) d = (__bf16)(fmaf(p, inv, -(j == y ? 1.f : 0.f)) * invB);
+          if (j == 0) {
+            const bool ok = y >= 0;
+            float* st = sZ + r * 16 + kStatSlot;
+            st[0] = ok ? (m + __logf(sum)) - zy : 0.f;
+            st[1] = ok && arg == y ? 1.f : 0.f;
+            st[2] = ok ? 1.f : 0.f;
+          }
+        }
+        sdZ[r * kDZS + j] = d;
+        sdZ[r * kDZS + 16 + j] = (__bf16)0.f;
+        sdZT[j * C::TS + r] = d;
+      }
+      __syncthreads();  // dZ of the row tile comes from its four waves
+      // ---- dH2 = (dZ W3) * (H2 > 0): tile (rt, q), masked by the wave's own H2 registers ----
+      if (colw) {
+        const bf16x8 dz = ld8(sdZ + (rt * 16 + r16) * kDZS + 8 * g);
+        const f32x4 acc = mfma16(dz, rw3tf, f32x4{0.f, 0.f, 0.f, 0.f});
+        bf16x4 t4;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) t4[i] = ((float)h2[i] > 0.f) ? (__bf16)acc[i] : (__bf16)0.f;
+        *reinterpret_cast<bf16x4*>(sDH2T + nq * C::TS + rt * 16 + 4 * g) = t4;
+      }
+      __syncthreads();  // dH2^T of the row tile comes from its four waves
+      // ---- dH1 = (dH2 W2) * (H1 > 0): column tile q of row tile rt ----
+      if (q < C::TN1) {
+        const int mcol = q * 16 + r16;
+        const bf16x4 hv = *reinterpret_cast<const bf16x4*>(sH1T + mcol * C::TS + rt * 16 + 4 * g);
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < KSH; ++i) acc = mfma16(tr_a(sDH2T, i), rw2tf[i], acc);
+        bf16x4 t4;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) t4[i] = ((float)hv[i] > 0.f) ? (__bf16)acc[i] : (__bf16)0.f;
+        *reinterpret_cast<bf16x4*>(sDH1T + mcol * C::TS + rt * 16 + 4 * g) = t4;
+      }
+      __syncthreads();
+      if (stamp_ok) a.stamps[3] = __builtin_amdgcn_s_memrealtime();
+      return;  // REP: the rows' loss stats stay parked in sZ; block 0 reduces and publishes them
+    }
 
     // ---------------- layer 2: H2 = relu(H1 W2^T + b2) ----------------
 #pragma unroll
@@ -2046,9 +2307,12 @@ struct One {
   static constexpr size_t oImg = C::total;
   static constexpr size_t oTile = oImg + (size_t)(2 * L2 + L1) * C::TS * 2;
   static constexpr size_t oRaw = oTile + (size_t)(2 * 32 + L1) * kXSS * 2 + 64;  // PreWave DMA area
-  static constexpr size_t lds = oRaw + kPreRawBytes;
+  static constexpr size_t oWts = oRaw + kPreRawBytes;  // row-chain form: the staged shadow weights
+  static constexpr size_t lds = oWts + RowChain<L1, L2>::bytes;
+  static_assert(oWts % 16 == 0, "bf16x8 reads of the staged weights");
 };
 static_assert(One<128, 256>::lds <= 160 * 1024, "one-launch LDS budget");
+static_assert(RowChain<32, 64>::fits && !RowChain<128, 256>::fits, "row-chain form: the flagship in, the widest out");
 
 // The ordering rule of the hand-off, for the acknowledging side: every load of state that
 // another block overwrites has RETURNED before this block's acknowledgement -- the vector
