@@ -373,7 +373,7 @@ void mlp3(int64_t kind, Tensor x_u8, Tensor labels, Tensor order, Tensor counter
           optional<Tensor> hand, int64_t dp_proto, bool dp_loop, int64_t repeat, optional<Tensor> clip_part,
           double clip_max_norm, optional<Tensor> clip_out, int64_t clip_nblk, bool acc_add, bool acc_rows,
           optional<Tensor> acc_head_row, optional<double> sgd_momentum, double sgd_dampening, bool sgd_nesterov,
-          double x_scale, double x_shift, optional<int64_t> last_rows) {
+          double x_scale, double x_shift, optional<int64_t> last_rows, int64_t lr_mask) {
   TORCH_CHECK(kind >= 0 && kind <= 8, "mlp3: bad kind ", kind);
   // SGD: refused here, before any launch, wherever it does not belong
   rla::MLP3Sgd sgd{0, 0.f, 0.f, 0};
@@ -474,7 +474,12 @@ void mlp3(int64_t kind, Tensor x_u8, Tensor labels, Tensor order, Tensor counter
   a.lr = (float)lr; a.beta1 = (float)beta1; a.beta2 = (float)beta2; a.eps = (float)eps;
   a.weight_decay = (float)weight_decay;
   a.grad_scale = (float)grad_scale;
-  a.lr_ptr = ptr_or_null<const float>(lr_t, "lr", at::kFloat, 1);
+  // the rate ring: lr_mask + 1 floats (a power of two) behind lr_t, entry (step - 1) & lr_mask
+  TORCH_CHECK_VALUE(lr_mask >= 0 && lr_mask < (1 << 20) && (lr_mask & (lr_mask + 1)) == 0,
+                    "mlp3: lr_mask must be 2^k - 1 (a ring of 2^k rates), got ", lr_mask);
+  TORCH_CHECK_VALUE(lr_mask == 0 || (lr_t.has_value() && lr_t->defined()), "mlp3: lr_mask needs the rate ring lr_t");
+  a.lr_ptr = ptr_or_null<const float>(lr_t, "lr", at::kFloat, lr_mask + 1);
+  a.lr_mask = (int)lr_mask;
   a.adamw = adamw;
   a.stamps = ptr_or_null<int64_t>(stamps, "stamps", at::kLong, 16);
   a.x_scale = (float)x_scale; a.x_shift = (float)x_shift;
@@ -511,7 +516,11 @@ void mlp3(int64_t kind, Tensor x_u8, Tensor labels, Tensor order, Tensor counter
                   "the packed / owner protocols need a receive area of ", rla::comm::kDpUnitAreaFloats,
                   " floats (mlp3_dp_area_floats())");
     }
-    TORCH_CHECK(!dp_loop || kind == rla::kMLP3Step1DP, "loopback is a one-launch-step diagnostic");
+    // loopback (diagnostic): one process plays every rank through its own region -- the
+    // one-launch exchange, and the two-launch tail's ring instances (the route a loopback
+    // engine takes in ring mode)
+    TORCH_CHECK(!dp_loop || kind == rla::kMLP3Step1DP || lr_mask != 0,
+                "loopback is a diagnostic of the one-launch step, and of the two-launch exchange under a rate ring");
   }
   // gradient clipping of the ADAM tail: the norm partials (clip_partials over `grads`),
   // the bound and the optional [norm, coef, #clipped, #non-finite] report
@@ -561,6 +570,8 @@ void mlp3(int64_t kind, Tensor x_u8, Tensor labels, Tensor order, Tensor counter
     TORCH_CHECK_VALUE(rc != -15, "mlp3: last_rows must be in [1, B = ", B, "] and equal B on the one-launch and "
                       "exchange kinds (5, 6, 7), got last_rows = ", lr_rows, " on kind ", kind,
                       " (code -15, nothing was launched)");
+    TORCH_CHECK_VALUE(rc != -16, "mlp3: the one-launch exchange (kind 7) has no instance for a rate ring (lr_mask = ",
+                      lr_mask, "): the two-launch exchange step (kind 5) serves it (code -16, nothing was launched)");
     TORCH_CHECK(rc == 0, "fused MLP v3 launch failed (kind ", kind, ", code ", rc, ")");
   }
 }
@@ -1302,7 +1313,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("clip_nblk") = -1, py::arg("acc_add") = false, py::arg("acc_rows") = false,
         py::arg("acc_head_row") = py::none(), py::arg("sgd_momentum") = py::none(), py::arg("sgd_dampening") = 0.0,
         py::arg("sgd_nesterov") = false, py::arg("x_scale") = (double)rla::kMLPXScale, py::arg("x_shift") = 0.0,
-        py::arg("last_rows") = py::none());
+        py::arg("last_rows") = py::none(), py::arg("lr_mask") = 0);
   m.def("dp_pack_roundtrip", &dp_pack_roundtrip, "packed DP exchange wire form of fp32 pairs, encoded + decoded");
   m.def("mlp3_hand_words", [](int64_t l1, int64_t l2) { return rla::mlp3_hand_words((int)l1, (int)l2); });
   m.def("mlp3_hand_layout", []() {

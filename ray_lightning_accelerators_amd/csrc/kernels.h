@@ -323,6 +323,15 @@ struct MLP3Args {
   float lr, beta1, beta2, eps, weight_decay, grad_scale;
   const float* lr_ptr;
   int adamw;
+  // the device learning rate is a ring of lr_mask + 1 floats (a power of two) behind lr_ptr:
+  // a launch that applies the optimizer for optimizer step t (1-based, Adam's bias-correction
+  // count; SGD: the counter behind its first-step rule) reads lr_ptr[(t - 1) & lr_mask].  0:
+  // the single scalar lr_ptr[0].  Nothing on the device writes the ring, so a captured graph
+  // replays correctly at any step.  Launches that apply no optimizer ignore it.  Like
+  // last_rows it sits in four bytes of padding the struct always had (between adamw and
+  // stamps): appended after x_shift it would grow the struct and move the hidden kernel
+  // arguments of every instance; here no field, no hidden argument and no size changes.
+  int lr_mask;
   int64_t* stamps;
   // fused data-parallel tail (kMLP3StepDP): the comm engine's auxiliary peer
   // region (csrc/comm/communicator.h aux_context)
@@ -338,6 +347,8 @@ struct MLP3Args {
   // the task's owner rank, Adam there, all-gather of the fp32 weights)
   int dp_proto;
   // loopback (diagnostic): one process plays all dp_world ranks through its own region
+  // (kMLP3Step1DP's packed / owner protocols, and kMLP3StepDP under a rate ring, lr_mask != 0:
+  // the tail's loopback is compiled into its ring instances; without a ring StepDP refuses it, -3)
   // (every region pointer is this rank's; the block writes every source slot itself)
   int dp_loop;
   // one-launch step (kMLP3Step1): in-launch hand-off words (mlp_step3.hip) and their poll bound.
@@ -353,6 +364,9 @@ struct MLP3Args {
 };
 static_assert(offsetof(MLP3Args, params) == 64 && offsetof(MLP3Args, last_rows) == 60,
               "last_rows fills the padding in front of params");
+static_assert(offsetof(MLP3Args, lr_mask) == offsetof(MLP3Args, adamw) + 4 &&
+                  offsetof(MLP3Args, stamps) == offsetof(MLP3Args, adamw) + 8 && sizeof(MLP3Args) == 368,
+              "lr_mask fills the padding behind adamw");
 enum MLP3Kind { kMLP3Step = 0, kMLP3Head = 1, kMLP3TailGrad = 2, kMLP3TailAdam = 3, kMLP3Prime = 4,
                 kMLP3StepDP = 5, kMLP3Step1 = 6, kMLP3Step1DP = 7, kMLP3TailAcc = 8 };
 int64_t mlp3_hand_words(int L1, int L2);  // int64 words of the one-launch step's hand-off buffer
@@ -421,7 +435,10 @@ struct MLP3Sgd {
 // a velocity buffer), -13 a non-finite or non-positive x_scale or a non-finite x_shift, -14
 // Step1DP with a pixel map other than the default (StepDP serves a normalised dataset), -15
 // last_rows outside [1, B], or last_rows != B on Step1 / Step1DP / StepDP (a short last batch
-// runs on the two-launch family: Head, Step, TailGrad, TailAcc, TailAdam, and on PRIME).
+// runs on the two-launch family: Head, Step, TailGrad, TailAcc, TailAdam, and on PRIME), -16
+// Step1DP with lr_mask != 0 (the one-launch exchange has no schedule instance: StepDP serves
+// a rate ring, as it serves a normalised dataset), -17 an lr_mask that is not 2^k - 1, or one
+// without lr_ptr.
 int launch_mlp3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip* clip = nullptr,
                 const MLP3Acc* acc = nullptr, const MLP3Sgd* sgd = nullptr);
 

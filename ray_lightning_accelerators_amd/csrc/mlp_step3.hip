@@ -1427,6 +1427,7 @@ __device__ __forceinline__ int dp_begin(const MLP3Args& a, uint32_t* sh_gen) {
   return (int)(*sh_gen & 1u);
 }
 
+template <bool LOOP = false>
 __device__ __forceinline__ void dp_signal_and_wait(const MLP3Args& a, uint32_t gen, int slot, int* sh_fail) {
   if (a.dp_lite) {
     // One wave fences (guide's producer/consumer form, system scope): every wave
@@ -1441,7 +1442,7 @@ __device__ __forceinline__ void dp_signal_and_wait(const MLP3Args& a, uint32_t g
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       if (tid < a.dp_world)
-        __hip_atomic_store(dp_flag(a.dp_regions[tid], slot, blk, a.dp_rank), gen, __ATOMIC_RELAXED,
+        __hip_atomic_store(dp_flag(a.dp_regions[tid], slot, blk, LOOP && a.dp_loop ? tid : a.dp_rank), gen, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_SYSTEM);
       if (tid < a.dp_world) {
         uint32_t* f = dp_flag(a.dp_regions[a.dp_rank], slot, blk, tid);
@@ -1469,7 +1470,7 @@ __device__ __forceinline__ void dp_signal_and_wait(const MLP3Args& a, uint32_t g
   const int tid = threadIdx.x, blk = blockIdx.x;
   if (tid == 0) *sh_fail = 0;
   if (tid < a.dp_world)
-    __hip_atomic_store(dp_flag(a.dp_regions[tid], slot, blk, a.dp_rank), gen, __ATOMIC_RELAXED,
+    __hip_atomic_store(dp_flag(a.dp_regions[tid], slot, blk, LOOP && a.dp_loop ? tid : a.dp_rank), gen, __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_SYSTEM);
   __syncthreads();
   if (tid < a.dp_world) {
@@ -1491,9 +1492,12 @@ __device__ __forceinline__ void dp_signal_and_wait(const MLP3Args& a, uint32_t g
   }
 }
 
+// (loopback, LOOP instances with a.dp_loop: every region pointer is this rank's own, and the block writes the
+// source slot of every rank it plays -- the same addresses the peers would write)
+template <bool LOOP = false>
 __device__ __forceinline__ void dp_push1(const MLP3Args& a, int slot, int64_t idx, float v) {
   for (int r = 0; r < a.dp_world; ++r)
-    __builtin_nontemporal_store(v, dp_data(a.dp_regions[r], slot, a.dp_rank, a.dp_stride) + idx);
+    __builtin_nontemporal_store(v, dp_data(a.dp_regions[r], slot, LOOP && a.dp_loop ? r : a.dp_rank, a.dp_stride) + idx);
 }
 
 // ---- tagged granules (dp_lite == 2, default): every value travels as ONE 8-byte
@@ -1508,11 +1512,14 @@ __device__ __forceinline__ unsigned long long* dp_gran(char* region, int slot, i
   return reinterpret_cast<unsigned long long*>(region + kXgmiFlagBytes) + ((int64_t)slot * kXgmiMaxRanks + src) * (stride / 2);
 }
 
+// (LOOP: the two-launch tail's RING instances -- see dp_push1; the one-launch granule
+// protocol has no loopback and its instances keep their code)
+template <bool LOOP = false>
 __device__ __forceinline__ void dp_push_gran(const MLP3Args& a, int slot, int64_t idx, float v, uint32_t gen) {
   const unsigned long long w = ((unsigned long long)gen << 32) | (unsigned long long)__float_as_uint(v);
   for (int r = 0; r < a.dp_world; ++r)
-    __hip_atomic_store(dp_gran(a.dp_regions[r], slot, a.dp_rank, a.dp_stride) + idx, w, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(dp_gran(a.dp_regions[r], slot, LOOP && a.dp_loop ? r : a.dp_rank, a.dp_stride) + idx, w,
+                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // fixed rank-order sum of the W granules of value idx; sets *fail on a poll timeout
@@ -1977,11 +1984,20 @@ struct TailLastArg { using type = MLP3Acc; };
 template <>
 struct TailLastArg<true> { using type = MLP3Sgd; };
 
-template <int L1, int L2, bool ACC = false, int MODE = -1, bool SGD = false>
+// RING: the learning rate is a ring of a.lr_mask + 1 floats and the launch reads the entry of
+// its optimizer step.  Its own instances, chosen in dispatch3 from lr_mask != 0 for the modes
+// that apply the optimizer, as SCHED for the one-launch kernel: as a run-time index in every
+// instance the read cost the two-launch step 0.33 us and the fused Adam tail 6 SGPR spills at
+// its 106-SGPR ceiling (profiles/r21_lr_schedule), so an engine without a ring runs the
+// instruction stream it ran before.  The exchange's loopback diagnostic (a.dp_loop on
+// StepDP) is compiled into the RING instances alone, for the same reason: only a ring takes
+// a loopback engine to this kernel (without one it runs the one-launch exchange).
+template <int L1, int L2, bool ACC = false, int MODE = -1, bool SGD = false, bool RING = false>
 __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, int mode_rt, MLP3Clip clip,
                                                                    typename TailLastArg<SGD>::type last) {
   static_assert(ACC ? (MODE == kGrad || MODE == kAcc) : MODE < 0, "accumulating tails fix their mode");
   static_assert(!(ACC && SGD), "the accumulating tails apply no optimizer");
+  static_assert(!(ACC && RING), "the accumulating tails apply no optimizer");
   MLP3Acc ga{0, 0, nullptr};
   MLP3Sgd sg{0, 0.f, 0.f, 0};
   if constexpr (SGD) sg = last; else ga = last;
@@ -2014,9 +2030,17 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
   // flight -- computed first, they delayed wave 0's loads (and the block) by a
   // full round trip plus the pows.
   const int64_t t_step = cn[0];  // already advanced by the head kernel
-  const float lr_now = a.lr_ptr ? a.lr_ptr[0] : a.lr;
+  // RING: the entry of optimizer step t_step, (t_step - 1) & lr_mask (in bounds for any
+  // counter), requested by the one thread that computes the step's scalars, behind its
+  // block's own loads -- t_step has arrived by then; at the kernel's top the index made every
+  // wave wait for it first.
+  const float lr_top = RING ? 0.f : (a.lr_ptr ? a.lr_ptr[0] : a.lr);
   auto scalars = [&]() {
     if (tid == 0 && do_adam) {
+      const float lr_now = [&]() -> float {
+        if constexpr (RING) return a.lr_ptr[(int)(t_step - 1) & a.lr_mask];
+        else return lr_top;
+      }();
       if constexpr (SGD)
         sh_o = SgdScal{lr_now, sg.momentum, 1.f - sg.dampening, a.weight_decay, sg.nesterov, t_step <= 1 ? 1 : 0};
       else
@@ -2059,7 +2083,7 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
         const uint32_t gen = sh_dgen;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-          if (r.valid[i]) dp_push_gran(a, dslot, r.gi[i], r.v[i], gen);
+          if (r.valid[i]) dp_push_gran<RING>(a, dslot, r.gi[i], r.v[i], gen);
         int fail = 0;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -2068,8 +2092,8 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
       } else {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-          if (r.valid[i]) dp_push1(a, dslot, r.gi[i], r.v[i]);
-        dp_signal_and_wait(a, sh_dgen, dslot, &sh_dfail);
+          if (r.valid[i]) dp_push1<RING>(a, dslot, r.gi[i], r.v[i]);
+        dp_signal_and_wait<RING>(a, sh_dgen, dslot, &sh_dfail);
 #pragma unroll
         for (int i = 0; i < 4; ++i)
           if (r.valid[i]) r.v[i] = dp_sum1(a, dslot, r.gi[i]) * scale;
@@ -2181,7 +2205,7 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
     if (a.dp_lite == 2) {
       const uint32_t gen = sh_dgen;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) dp_push_gran(a, dslot, gidx + i, acc[i], gen);
+      for (int i = 0; i < 4; ++i) dp_push_gran<RING>(a, dslot, gidx + i, acc[i], gen);
       int fail = 0;
 #pragma unroll
       for (int i = 0; i < 4; ++i) acc[i] = dp_sum_gran(a, dslot, gidx + i, gen, &fail) * a.grad_scale;
@@ -2190,9 +2214,9 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
       typedef float v4f __attribute__((ext_vector_type(4)));
       const v4f mine = {acc[0], acc[1], acc[2], acc[3]};
       for (int r = 0; r < a.dp_world; ++r)
-        __builtin_nontemporal_store(mine, reinterpret_cast<v4f*>(dp_data(a.dp_regions[r], dslot, a.dp_rank,
-                                                                         a.dp_stride) + gidx));
-      dp_signal_and_wait(a, sh_dgen, dslot, &sh_dfail);
+        __builtin_nontemporal_store(mine, reinterpret_cast<v4f*>(dp_data(a.dp_regions[r], dslot,
+                                                                         RING && a.dp_loop ? r : a.dp_rank, a.dp_stride) + gidx));
+      dp_signal_and_wait<RING>(a, sh_dgen, dslot, &sh_dfail);
       v4f s = {0.f, 0.f, 0.f, 0.f};
       for (int r = 0; r < a.dp_world; ++r)
         s += __builtin_nontemporal_load(
@@ -2290,7 +2314,7 @@ __global__ __launch_bounds__(64 * (L1 / 16)) void mlp3_tail_kernel(MLP3Args a, i
 //                  and pinned in SGPRs by an empty asm (left to itself the compiler fetched
 //                  the arguments in three to five dependent batches and fetched some of
 //                  them again under register pressure, one scalar round trip each);
-//   state batch    counters[0, 1, 3, 4, kSeq], the four Adam cache words, *lr_ptr (and the
+//   state batch    counters[0, 1, 3, 4, kSeq], the four Adam cache words, *lr_ptr (SCHED: see there; and the
 //                  exchange generation), requested right after it and waited for at the
 //                  top of the hook -- behind the biases, H1pre, labels, weight fragments
 //                  and the small blocks' Adam-state prefetch, which need kernel arguments
@@ -2369,9 +2393,16 @@ __device__ __forceinline__ void one_wait_acks(const MLP3Args& a, const int64_t* 
 // constant u8 * (1/255) and never read them -- two more pinned SGPRs cost every instance two
 // to seven further SGPR spills across the head pass (profiles/r17_real_mnist), so the
 // datasets without a Normalize run the instruction stream they ran before.
-template <int L1, int L2, int DPP, int NW = 8, bool PROBE = false, bool NORM = false>
+// SCHED (world size 1 only): the learning rate is a ring of a.lr_mask + 1 floats and this
+// launch reads entry (t_adam - 1) & lr_mask.  The index needs the step counter, so the rate
+// leaves the state batch: it is requested by a scalar load of its own inside the hook, right
+// behind the state wait, and waited for where Adam's scalars consume it -- behind the wave's
+// last prologue load, so the extra round trip overlaps the head pass.  lr_mask joins the
+// kernarg batch.  The instances without a ring keep their instruction stream, as with NORM.
+template <int L1, int L2, int DPP, int NW = 8, bool PROBE = false, bool NORM = false, bool SCHED = false>
 __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args ka) {
   constexpr bool DP = DPP >= 0;
+  static_assert(!(SCHED && DP), "the rate ring has no instance with an exchange (StepDP serves it)");
   using C = typename One<L1, L2>::C;
   using S = SmallTasks<L1, L2>;
   constexpr int TN1 = L1 / 16, Bp = 32;
@@ -2407,6 +2438,7 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args ka) {
                  "+s"(a.eps), "+s"(a.weight_decay), "+s"(a.adamw), "+s"(g_dp_err));
   if constexpr (DP) asm volatile("" : "+s"(g_dp_gen));
   if constexpr (NORM) asm volatile("" : "+s"(a.x_scale), "+s"(a.x_shift));  // same request: nothing waited yet
+  if constexpr (SCHED) asm volatile("" : "+s"(a.lr_mask));
   a.counters = (int64_t*)g_counters, a.hand = (unsigned long long*)g_hand, a.lr_ptr = (const float*)g_lr_ptr;
   a.params = (float*)g_params, a.exp_avg = (float*)g_exp_avg, a.exp_avg_sq = (float*)g_exp_avg_sq;
   a.shadow = (uint16_t*)g_shadow, a.h1pre = (int*)g_h1pre, a.yring = (int*)g_yring;
@@ -2443,8 +2475,10 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args ka) {
   // corrections below (thread 0) waited vmcnt(0) for it -- i.e. for every prologue
   // prefetch -- before wave 0 issued a single head-pass load (profiles/r4_dp)
   // (as bits: a float select is a VALU select, and the value has to stay an SGPR)
-  uint32_t lr_bits =
-      a.lr_ptr ? ((const __attribute__((address_space(4))) uint32_t*)(a.lr_ptr))[0] : __float_as_uint(a.lr);
+  // (SCHED: the ring entry is requested in the hook, once the state batch has the step)
+  uint32_t lr_bits = 0u;
+  if constexpr (!SCHED)
+    lr_bits = a.lr_ptr ? ((const __attribute__((address_space(4))) uint32_t*)(a.lr_ptr))[0] : __float_as_uint(a.lr);
   float lr_now = 0.f;
   // wave 0 of a tile: row (lane & 31) of X[t] (parked by the previous step) and the
   // sample index of row (lane & 31) of the NEXT batch (its pixels load after the ack)
@@ -2468,9 +2502,13 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args ka) {
     asm volatile(""
                  : "+s"(c0), "+s"(cursor), "+s"(slot), "+s"(ob), "+s"(seq), "+s"(ck_step), "+s"(ck_betas), "+s"(ck_bc1),
                    "+s"(ck_bc2), "+s"(lr_bits), "+s"(dgen));
-    lr_now = __uint_as_float(lr_bits);
+    if constexpr (!SCHED) lr_now = __uint_as_float(lr_bits);
     pre.slot = slot;
     t_adam = a.advance_step ? c0 + 1 : c0;
+    // SCHED: this step's entry of the rate ring -- a scalar load of its own (launch_mlp3
+    // admits a ring with lr_ptr only), in bounds for any counter, waited for below
+    if constexpr (SCHED)
+      lr_bits = ((const __attribute__((address_space(4))) uint32_t*)(a.lr_ptr))[(int)(t_adam - 1) & a.lr_mask];
     int64_t nc = cursor + 1, nob = ob;
     if (nc >= a.n_batches) { nc = 0; nob ^= 1; }
     pre.si = a.order[nob * a.order_stride + nc * B + (xb < B ? xb : 0)];
@@ -2489,6 +2527,10 @@ __global__ __launch_bounds__(kThreads) void mlp3_one_kernel(MLP3Args ka) {
     // kind of step in between, other betas) evaluates the two pow() here, on two lanes:
     // that one launch's first barrier waits for them (profiles/r7_softmax_lanes, variant A).
     if (w == 0 && blk > 0) {
+      if constexpr (SCHED) {  // the wait for the ring entry: the value stays an SGPR
+        asm volatile("" : "+s"(lr_bits));
+        lr_now = __uint_as_float(lr_bits);
+      }
       if (t_adam > 0 && ck_step == t_adam && ck_betas == (int64_t)adam_betas_key(a.beta1, a.beta2)) {
         if (lane == 0)
           adam_scalars_bias(*sh_o, AdamBias{__longlong_as_double(ck_bc1), __longlong_as_double(ck_bc2)}, lr_now,
@@ -2724,6 +2766,16 @@ int dispatch3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip& c
   const bool norm = a.x_scale != kMLPXScale || a.x_shift != 0.f;
   if (kind == kMLP3Step1) {
     if (a.B > 32 || !a.hand || kOneGrid > 256) return -5;
+    if (a.lr_mask != 0) {  // a rate ring: the SCHED instances, plain and NORM
+      if (a.stamps) return -9;  // no probe instance
+      if (norm)
+        hipLaunchKernelGGL((mlp3_one_kernel<L1, L2, -1, 8, false, true, true>), dim3(kOneGrid), dim3(kThreads), 0,
+                           stream, a);
+      else
+        hipLaunchKernelGGL((mlp3_one_kernel<L1, L2, -1, 8, false, false, true>), dim3(kOneGrid), dim3(kThreads), 0,
+                           stream, a);
+      return 0;
+    }
     if (norm) {
       if (a.stamps) return -9;  // no probe instance
       hipLaunchKernelGGL((mlp3_one_kernel<L1, L2, -1, 8, false, true>), dim3(kOneGrid), dim3(kThreads), 0, stream, a);
@@ -2740,6 +2792,7 @@ int dispatch3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip& c
     return 0;
   }
   if (kind == kMLP3Step1DP) {
+    if (a.lr_mask != 0) return -16;  // no SCHED instance with an exchange: the two-launch StepDP serves a ring
     if (norm) return -14;  // no NORM instance with an exchange: the two-launch StepDP serves it
     // granule exchange only (the flag protocols stay on the two-launch StepDP)
     if (a.B > 32 || !a.hand || kOneGrid > kDpMaxBlocks || a.dp_world < 1 || a.dp_world > kXgmiMaxRanks ||
@@ -2802,12 +2855,22 @@ int dispatch3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip& c
     int extra = (int)((nsmall + NT - 1) / NT);
     grid += extra < 64 ? extra : 64;
   }
+  // a rate ring: the RING instances, for the modes that apply the optimizer (the others ignore lr_mask)
+  const bool ring = a.lr_mask != 0 && (mode == kFused || mode == kFusedDP || mode == kAdam);
   if (sgd.enabled) {  // launch_mlp3 admits it for Step / TailAdam only: the same grid, the SGD instance
-    hipLaunchKernelGGL((mlp3_tail_kernel<L1, L2, false, -1, true>), dim3(grid), dim3(NT), 0, stream, a, mode, clip,
-                       sgd);
+    if (ring)
+      hipLaunchKernelGGL((mlp3_tail_kernel<L1, L2, false, -1, true, true>), dim3(grid), dim3(NT), 0, stream, a, mode,
+                         clip, sgd);
+    else
+      hipLaunchKernelGGL((mlp3_tail_kernel<L1, L2, false, -1, true>), dim3(grid), dim3(NT), 0, stream, a, mode, clip,
+                         sgd);
     return 0;
   }
-  if (mode >= 0) hipLaunchKernelGGL((mlp3_tail_kernel<L1, L2>), dim3(grid), dim3(NT), 0, stream, a, mode, clip, acc);
+  if (ring)
+    hipLaunchKernelGGL((mlp3_tail_kernel<L1, L2, false, -1, false, true>), dim3(grid), dim3(NT), 0, stream, a, mode,
+                       clip, acc);
+  else if (mode >= 0)
+    hipLaunchKernelGGL((mlp3_tail_kernel<L1, L2>), dim3(grid), dim3(NT), 0, stream, a, mode, clip, acc);
   return 0;
 }
 
@@ -2848,6 +2911,10 @@ int launch_mlp3(const MLP3Args& a, int kind, hipStream_t stream, const MLP3Clip*
   // a short last batch exists in the two-launch family and PRIME only
   if (a.last_rows < 1 || a.last_rows > a.B) return -15;
   if (a.last_rows != a.B && (kind == kMLP3Step1 || kind == kMLP3Step1DP || kind == kMLP3StepDP)) return -15;
+  // the rate ring: a power of two entries behind lr_ptr; the one-launch exchange has no instance for it
+  if (a.lr_mask < 0 || (a.lr_mask & (a.lr_mask + 1)) != 0 || (a.lr_mask != 0 && !a.lr_ptr)) return -17;
+  if (a.lr_mask != 0 && kind == kMLP3Step1DP) return -16;
+  if (a.dp_loop && kind == kMLP3StepDP && a.lr_mask == 0) return -3;  // the tail's loopback lives in its RING instances
   // SGD belongs to the two kinds whose tail applies the optimizer outside the one-launch
   // kernel and the in-kernel exchange
   MLP3Sgd sgd{0, 0.f, 0.f, 0};

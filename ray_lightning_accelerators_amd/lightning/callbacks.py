@@ -14,7 +14,7 @@ from __future__ import annotations
 import math
 import os
 import re
-from typing import Any, Dict, Optional
+from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 
@@ -319,15 +319,68 @@ class EarlyStopping(Callback):
 
 
 class LearningRateMonitor(Callback):
-    """Logs the learning rate of each optimizer group at every epoch start."""
+    """Logs the learning rate of each optimizer group at every epoch start
+    (``logging_interval=None``), or with ``logging_interval="step"`` the rate each log point
+    (every ``log_every_n_steps``-th global step) ran with; ``history`` then keeps the
+    ``(global step, rate of the first group)`` pairs."""
+
+    def __new__(cls, logging_interval: Optional[str] = None):
+        # the step form has batch hooks; the default must not grow any (a callback with
+        # batch hooks changes how the Trainer dispatches)
+        if cls is LearningRateMonitor and logging_interval == "step":
+            return super().__new__(_StepLearningRateMonitor)
+        return super().__new__(cls)
 
     def __init__(self, logging_interval: Optional[str] = None):
         self.logging_interval = logging_interval
+        self.history: List[Tuple[int, float]] = []
+
+    @staticmethod
+    def _rates(trainer) -> Dict[str, float]:
+        return {f"lr-{type(opt).__name__}" + (f"/pg{j + 1}" if j else ""): g["lr"]
+                for opt in trainer.optimizers for j, g in enumerate(opt.param_groups)}
 
     def on_train_epoch_start(self, trainer, pl_module):
-        for i, opt in enumerate(trainer.optimizers):
-            for j, g in enumerate(opt.param_groups):
-                trainer.logged_metrics[f"lr-{type(opt).__name__}" + (f"/pg{j + 1}" if j else "")] = g["lr"]
+        trainer.logged_metrics.update(self._rates(trainer))
+
+
+class _StepLearningRateMonitor(LearningRateMonitor):
+    """``LearningRateMonitor(logging_interval="step")``.  Per-batch dispatch: the rate is read
+    when the batch starts (the scheduler moves it right after the step) and logged when the
+    step it closed is a log point.  Chunked dispatch (``on_train_chunk_end``; the callback is
+    chunk-aware, so it does not force one dispatch per batch): the Trainer derived the
+    chunk's rates for the fused step, and each log point inside the chunk gets its own."""
+
+    def on_train_epoch_start(self, trainer, pl_module):
+        pass
+
+    def on_train_batch_start(self, trainer, pl_module, batch, batch_idx, dataloader_idx):
+        self._before = (trainer.global_step, self._rates(trainer))
+
+    def on_train_batch_end(self, trainer, pl_module, outputs, batch, batch_idx, dataloader_idx):
+        step0, rates = getattr(self, "_before", (trainer.global_step, None))
+        every = max(1, trainer.log_every_n_steps)
+        if rates and trainer.global_step != step0 and trainer.global_step % every == 0:
+            trainer.logged_metrics.update(rates)
+            self.history.append((trainer.global_step, float(next(iter(rates.values())))))
+
+    def on_train_chunk_end(self, trainer, pl_module, outputs, n_steps, n_samples):
+        rates = getattr(trainer, "_chunk_rates", None)
+        now = self._rates(trainer)
+        if not now:
+            return
+        key = next(iter(now))
+        every = max(1, trainer.log_every_n_steps)
+        points = {}
+        for i in range(n_steps):
+            st = trainer.global_step - n_steps + 1 + i
+            if st % every == 0:
+                # no step-interval scheduler: nothing moved the rate inside the chunk
+                points[st] = {key: rates[i]} if rates is not None else dict(now)
+                self.history.append((st, float(points[st][key])))
+        if points:
+            trainer._lr_log_points = points  # the Trainer files each under its own step
+            trainer.logged_metrics.update(points[max(points)])
 
 
 def _scalar(v: Any) -> float:

@@ -1032,8 +1032,14 @@ class Trainer:
 
         Several steps go out at once (hipGraph replays, no per-batch Python) only
         when nothing observes single batches: no batch hooks (callbacks that
-        implement ``on_train_chunk_end`` are chunk-aware and fine), no
-        step-interval LR scheduler, no fault injection at a given step."""
+        implement ``on_train_chunk_end`` are chunk-aware and fine), no fault
+        injection at a given step, and no step-interval LR scheduler the fused step
+        cannot follow on the device: one that declares ``schedules_lr`` is handed each
+        chunk's rates (``_chunk_lr_schedule``) -- ``ReduceLROnPlateau`` (it reads a metric
+        per step), a scheduler that also cycles the momentum (``OneCycleLR`` / ``CyclicLR``
+        with ``cycle_momentum``: it rewrites ``betas`` / ``momentum`` per step, which a
+        captured graph bakes) and several optimizers or parameter groups still go out per
+        batch."""
         f = self._fused
         if f is None or not hasattr(f, "train_chunk"):
             return 1
@@ -1045,11 +1051,37 @@ class Trainer:
             return 1
         if any(getattr(model, nm, None) is not None for nm in ("on_batch_start", "on_batch_end")):
             return 1
-        if any(s.get("interval", "epoch") == "step" for s in self.lr_schedulers):
+        step_scheds = self._step_schedulers()
+        if step_scheds and (not getattr(f, "schedules_lr", False) or not hasattr(f, "set_lr_schedule")
+                            or any(s.get("reduce_on_plateau") or getattr(s["scheduler"], "cycle_momentum", False)
+                                   for s in step_scheds)
+                            or len(self.optimizers) != 1 or len(self.optimizers[0].param_groups) != 1):
             return 1
         if os.environ.get("RLA_FAULT_STEP") is not None:
             return 1
         return k
+
+    def _step_schedulers(self) -> List[dict]:
+        return [s for s in self.lr_schedulers if s.get("interval", "epoch") == "step"]
+
+    def _chunk_lr_schedule(self, k: int) -> Optional[List[float]]:
+        """The rates of the next ``k`` steps, derived by doing on the host exactly what ``k``
+        per-batch iterations do: step i runs at the group's current rate, then every
+        step-interval scheduler whose ``frequency`` divides ``global_step + i`` steps.  The
+        schedulers, ``param_groups[0]["lr"]`` and the checkpointed scheduler state are
+        afterwards what the per-batch loop leaves behind the chunk's last step.  None: no
+        step-interval scheduler."""
+        scheds = self._step_schedulers()
+        if not scheds:
+            return None
+        group = self.optimizers[0].param_groups[0]
+        rates = []
+        for i in range(1, k + 1):
+            rates.append(float(group["lr"]))
+            for s in scheds:
+                if (self.global_step + i) % s.get("frequency", 1) == 0:
+                    s["scheduler"].step()
+        return rates
 
     def _run_chunked(self, model: LightningModule, n: int, chunk: int, epoch_outputs: List[Any]) -> bool:
         """The epoch's ``n`` resident batches in dispatches of <= ``chunk`` steps.
@@ -1080,6 +1112,11 @@ class Trainer:
                         or (self.max_steps is not None and gs >= self.max_steps)):
                     break
             k = e - b
+            # the chunk's per-step rates (chunks end at validation, max_steps and the epoch
+            # end, so no scheduler is stepped past a stop); chunk-aware callbacks read them
+            self._chunk_rates = self._chunk_lr_schedule(k)
+            if self._chunk_rates is not None:
+                self._fused.set_lr_schedule(self._chunk_rates)
             self.profiler.start("run_training_batch")
             outs = self._fused.train_chunk(k)
             self.profiler.stop("run_training_batch")
@@ -1089,6 +1126,7 @@ class Trainer:
                 self._drain_staged_logs(wait=False)  # the previous validation's rows, if copied
             self.global_step += k
             epoch_outputs.extend(outs)
+            self._lr_log_points = None
             for cb in self.callbacks:
                 fn = getattr(cb, "on_train_chunk_end", None)
                 if fn is not None:
@@ -1097,9 +1135,11 @@ class Trainer:
                 rows = getattr(self._fused, "_last_rows", None)
                 if rows is not None and rows.size(0) == k:
                     final, current = self.global_step, dict(self.logged_metrics)
+                    lr_points = self._lr_log_points or {}
                     for st, met in self._fused.log_points(rows, final - k, every):
                         self.global_step = st  # the row is written under its own step
                         self.logged_metrics.update(met)
+                        self.logged_metrics.update(lr_points.get(st, {}))  # LearningRateMonitor("step")
                         self._flush_logger(defer=True)
                     self.global_step = final
                     self.logged_metrics.clear()
@@ -1178,6 +1218,7 @@ class Trainer:
             out = self._fused.train_batch(batch, batch_idx)
             if not getattr(self._fused, "counts_steps", False):
                 self.global_step += 1
+                self._update_lr_schedulers("step")  # (a step that counts itself steps them itself)
         else:
             out = self._autograd_step(batch, batch_idx, is_last)
         self.profiler.stop("run_training_batch")

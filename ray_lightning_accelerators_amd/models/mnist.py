@@ -238,7 +238,16 @@ ENGINE_STATS_RING = 4096
 
 
 class FusedMNISTStep:
-    """Drives the fused HIP step from the Trainer's loop (replaces autograd + optimizer)."""
+    """Drives the fused HIP step from the Trainer's loop (replaces autograd + optimizer).
+
+    A step-interval LR scheduler (``{"scheduler": OneCycleLR(...), "interval": "step"}``; not
+    ``ReduceLROnPlateau``) keeps chunked dispatch: the engine is built in ring mode
+    (``FusedMLPEngine(lr_ring=ENGINE_STATS_RING)``), ``lr_tensor`` is the ring, and the Trainer
+    hands each chunk's rates to ``set_lr_schedule`` -- the captured graph reads step ``t``'s
+    rate from entry ``(t - 1) & mask``."""
+
+    # the Trainer may chunk under a step-interval scheduler: this step takes a chunk's rates
+    schedules_lr = True
 
     def __init__(self, model: LightningMNISTClassifier, trainer):
         dev = model.device
@@ -279,7 +288,12 @@ class FusedMNISTStep:
         self.counters = torch.zeros(2, dtype=torch.int64, device=dev)
         self.counters[0] = self.gs.step
         self.lr_val = float(opt.param_groups[0]["lr"])
-        self.lr_tensor = torch.full((1,), self.lr_val, device=dev)
+        # a ring of rates indexed by the optimizer step when a step-interval scheduler drives
+        # the rate (fixed here: the engine's graphs bake the mask); else the one scalar
+        self.lr_ring = ENGINE_STATS_RING if any(
+            s.get("interval", "epoch") == "step" and not s.get("reduce_on_plateau")
+            for s in getattr(trainer, "lr_schedulers", None) or []) else 0
+        self.lr_tensor = torch.full((max(self.lr_ring, 1),), self.lr_val, device=dev)
         self.stats = torch.zeros(64, 4, device=dev)
         self._u8 = None
         self._normalize = None  # the training dataset's Normalize (mean, std), folded into the kernels
@@ -325,9 +339,13 @@ class FusedMNISTStep:
                              weight_decay=g["weight_decay"], device=self.dev, world_size=self.world,
                              rank=self.trainer.global_rank, allreduce=self._allreduce, buffers=bufs,
                              stats_ring=ENGINE_STATS_RING, dp_context=dp_ctx, dp_rearm=rearm,
-                             clip_norm=self.clip_norm, accumulate=self.accumulate, **hyper)
+                             clip_norm=self.clip_norm, accumulate=self.accumulate, lr_ring=self.lr_ring, **hyper)
         eng.set_step(self.gs.step)
-        eng.lr_tensor = self.lr_tensor  # LR schedulers update one device scalar
+        # LR schedulers update one device scalar (ring mode: this object's ring, which set_lr
+        # below fills so that the engine's host picture of it is true)
+        eng.lr_tensor = self.lr_tensor
+        if self.lr_ring:
+            eng.set_lr(self.lr_val)
         eng.attach_dataset(self._u8, self._labels, normalize=self._normalize)
         self.eng = eng
         return eng
@@ -421,10 +439,34 @@ class FusedMNISTStep:
         lr = float(self.opt.param_groups[0]["lr"])
         if lr != self.lr_val:
             self.lr_val = lr
-            self.lr_tensor.fill_(lr)
+            if self.lr_ring and self.eng is not None:
+                self.eng.set_lr(lr)  # the whole ring; any schedule is forgotten
+            else:
+                self.lr_tensor.fill_(lr)
 
     def on_lr_change(self) -> None:
         self._sync_lr()
+
+    def set_lr_schedule(self, rates) -> None:
+        """The rates of the next ``len(rates)`` optimizer steps, from the Trainer ahead of
+        ``train_chunk``: it has already stepped the schedulers past them, so the group's rate
+        is now the one of the step after the chunk -- which is what any step past the
+        schedule runs with."""
+        self.lr_val = float(self.opt.param_groups[0]["lr"])
+        self._sync_engine()
+        self.eng.set_lr_schedule(rates)
+
+    def _lr_one(self) -> torch.Tensor:
+        """The one-element rate tensor of a loader-fed batch (those kernels keep their
+        single-scalar contract): ring mode fills the ring with the current rate first."""
+        if not self.lr_ring:
+            return self.lr_tensor
+        if self.eng is None or self.eng._ring_uniform != self.lr_val:
+            if self.eng is not None:
+                self.eng.set_lr(self.lr_val)
+            else:
+                self.lr_tensor.fill_(self.lr_val)
+        return self.lr_tensor[:1]
 
     def _sync_engine(self) -> None:
         """The group's hyperparameters, refreshed per dispatch (a user or a scheduler may
@@ -452,11 +494,11 @@ class FusedMNISTStep:
             fused_sgd_(p, gr, self.gs.buf[: self.np] if mom != 0.0 else None, lr=self.lr_val, momentum=mom,
                        dampening=g.get("dampening", 0.0), weight_decay=g["weight_decay"],
                        nesterov=bool(g.get("nesterov", False)), grad_scale=scale, step=self.counters[0:1],
-                       lr_tensor=self.lr_tensor)
+                       lr_tensor=self._lr_one())
         else:
             fused_adam_(p, gr, self.gs.m[: self.np], self.gs.v[: self.np], lr=self.lr_val, betas=tuple(g["betas"]),
                         eps=g["eps"], weight_decay=g["weight_decay"], grad_scale=scale,
-                        adamw=self.opt_kind == "adamw", step=self.counters[0:1], lr_tensor=self.lr_tensor)
+                        adamw=self.opt_kind == "adamw", step=self.counters[0:1], lr_tensor=self._lr_one())
 
     def _train_micro_batch(self, batch, batch_idx: int):
         """``train_batch`` under ``accumulate_grad_batches=K``: one micro-batch.  Batch i of
@@ -488,7 +530,7 @@ class FusedMNISTStep:
             fused_mlp.mlp_train_step(p, gr, B=x.size(0), labels=y, x_f32=x, L1=self.L1, L2=self.L2,
                                      stats=stats, accumulate_grad=micro > 0, apply_adam=False,
                                      advance_step=closing, lr=self.lr_val, weight_decay=g["weight_decay"],
-                                     lr_tensor=self.lr_tensor, counters=self.counters)
+                                     lr_tensor=self._lr_one(), counters=self.counters)
             if closing:
                 scale = 1.0 / (self.world * K)
                 if self._allreduce is not None and self.acc.sync is not None:
@@ -524,7 +566,7 @@ class FusedMNISTStep:
         # the loader-fed kernel applies Adam / AdamW itself; SGD follows it as its own launch
         fused = self.world == 1 and self.clip_norm is None and not self.sgd
         kw = dict(L1=self.L1, L2=self.L2, stats=self.stats, apply_adam=fused, advance_step=True, lr=self.lr_val,
-                  weight_decay=g["weight_decay"], lr_tensor=self.lr_tensor, counters=self.counters)
+                  weight_decay=g["weight_decay"], lr_tensor=self._lr_one(), counters=self.counters)
         if not self.sgd:
             kw.update(exp_avg=self.gs.m[: self.np], exp_avg_sq=self.gs.v[: self.np], betas=tuple(g["betas"]),
                       eps=g["eps"], adamw=self.opt_kind == "adamw")

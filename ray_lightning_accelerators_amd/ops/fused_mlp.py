@@ -435,6 +435,7 @@ def mlp3_launch(
     x_scale: float = X_SCALE_DEFAULT,
     x_shift: float = 0.0,
     last_rows: Optional[int] = None,
+    lr_mask: int = 0,
 ) -> None:
     """One v3 launch (GPU only; ``repeat``: that many identical launches back to back
     from one C++ loop -- every step's state lives on the device).  ``kind``: MLP3_STEP (head + fused tail, world size 1),
@@ -494,7 +495,20 @@ def mlp3_launch(
     ``1 / last_rows`` and files the stats row ``(mean NLL, #correct, last_rows, step)``.
     ``order`` keeps the stride ``n_batches * B``; its padding slots are never read.  Outside
     ``[1, B]``, or below ``B`` on MLP3_STEP1 / MLP3_STEP1_DP / MLP3_STEP_DP (which have no short
-    batch): ValueError before any launch (launch_mlp3's code -15)."""
+    batch): ValueError before any launch (launch_mlp3's code -15).
+
+    ``lr_mask`` (0: ``lr_tensor`` is the one scalar): ``lr_tensor`` is a ring of ``lr_mask + 1``
+    rates, a power of two, and a launch that applies the optimizer for optimizer step ``t``
+    (1-based: Adam's bias-correction count, the counter behind SGD's first-step rule) reads
+    ``lr_tensor[(t - 1) & lr_mask]``.  Nothing on the device writes the ring, so a captured
+    graph follows a schedule the host keeps ahead of it.  MLP3_STEP1 runs its schedule
+    instances; MLP3_STEP1_DP has none (MLP3_STEP_DP serves a ring): ValueError before any
+    launch (code -16).  Kinds that apply no optimizer ignore it."""
+    lr_mask = int(lr_mask)
+    if lr_mask < 0 or lr_mask & (lr_mask + 1):
+        raise ValueError(f"mlp3_launch: lr_mask must be 2^k - 1, got {lr_mask}")
+    if lr_mask and (lr_tensor is None or lr_tensor.numel() < lr_mask + 1):
+        raise ValueError(f"mlp3_launch: lr_mask = {lr_mask} needs lr_tensor of {lr_mask + 1} rates")
     x_scale, x_shift = check_input_affine(x_scale, x_shift)
     last_rows = check_last_rows(last_rows, B, "mlp3_launch")
     if last_rows != int(B) and kind in (MLP3_STEP1, MLP3_STEP1_DP, MLP3_STEP_DP):
@@ -535,7 +549,7 @@ def mlp3_launch(
         clip_part, float(clip_max_norm), clip_out, -1 if clip_nblk is None else int(clip_nblk),
         bool(acc_add), bool(acc_rows), acc_head_row,
         None if sgd_momentum is None else float(sgd_momentum), float(sgd_dampening), bool(sgd_nesterov),
-        float(x_scale), float(x_shift), int(last_rows),
+        float(x_scale), float(x_shift), int(last_rows), lr_mask,
     )
 
 

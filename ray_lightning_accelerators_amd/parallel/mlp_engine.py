@@ -134,6 +134,7 @@ class FusedMLPEngine:
         momentum: float = 0.0,
         dampening: float = 0.0,
         nesterov: bool = False,
+        lr_ring: int = 0,
     ):
         """``buffers``: optional external fp32 tensors ``params`` / ``grads`` /
         ``exp_avg`` / ``exp_avg_sq`` (e.g. views of a Trainer's parameter arena,
@@ -166,7 +167,19 @@ class FusedMLPEngine:
         world size 1 without clipping or accumulation is head -> tail (two launches), every
         other combination head -> tail(grad | acc) -> [allreduce] -> [norm partials] ->
         tail(sgd).  Its velocity is ``momentum_buffer`` (``buffers["momentum_buffer"]`` when
-        external); ``exp_avg`` aliases it and ``exp_avg_sq`` is None."""
+        external); ``exp_avg`` aliases it and ``exp_avg_sq`` is None.
+        ``lr_ring``: 0 (default): the learning rate is one device scalar, rewritten by
+        ``set_lr``.  A power of two >= 2 puts the engine in ring mode for its lifetime (graphs
+        bake the mask): ``lr_tensor`` holds that many rates and the launch that applies
+        optimizer step ``t`` reads entry ``(t - 1) & (lr_ring - 1)``, so ``set_lr_schedule``
+        hands a captured graph a different rate at every step without a host write in between.
+        A step without a scheduled rate runs at ``lr``, as outside ring mode.  The one-launch
+        step runs its schedule instances; the one-launch in-kernel exchange has none, so a
+        ``dp_context`` engine then steps as two launches (one warning)."""
+        if isinstance(lr_ring, bool) or int(lr_ring) != lr_ring or int(lr_ring) < 0 or int(lr_ring) == 1 \
+                or int(lr_ring) & (int(lr_ring) - 1):
+            raise ValueError(f"lr_ring must be 0 or a power of two >= 2, got {lr_ring!r}")
+        lr_ring = int(lr_ring)
         if optimizer not in ("adam", "adamw", "sgd"):
             raise ValueError(f"optimizer must be 'adam', 'adamw' or 'sgd', got {optimizer!r}")
         momentum, dampening, nesterov = float(momentum), float(dampening), bool(nesterov)
@@ -233,7 +246,15 @@ class FusedMLPEngine:
             self.grads = self._grads_padded[:n]
             self.exp_avg = torch.zeros(n, device=self.device)  # SGD: the velocity (momentum_buffer)
             self.exp_avg_sq = None if self.sgd else torch.zeros(n, device=self.device)
-        self.lr_tensor = torch.full((1,), self.lr, device=self.device)
+        self.lr_ring, self.lr_mask = lr_ring, max(lr_ring - 1, 0)
+        self.lr_tensor = torch.full((max(lr_ring, 1),), self.lr, device=self.device)
+        # ring mode, host side: what each entry will hold once the stream reaches the next
+        # launch; the value every entry holds (None: they differ); the last optimizer step
+        # with a scheduled rate; pinned staging buffers with the event of their last copy
+        self._ring_host = [self.lr] * lr_ring
+        self._ring_uniform: Optional[float] = self.lr
+        self._sched_end = 0
+        self._lr_stage: list = []
         self.clip_norm = clip_norm
         self.accumulate = accumulate
         # the one-block head's stats row of the current micro-batch (accumulation: the tail
@@ -283,6 +304,10 @@ class FusedMLPEngine:
         self.one_launch_dp = False
         # (collective with a rearm callable: every rank builds its engine together)
         self.set_dp_proto(dp_proto or os.environ.get("RLA_DP_PROTO") or "packed", rearm=True)
+        if self.lr_mask and self.one_launch and self.dp_ctx is not None and not self.one_launch_dp:
+            log.warning("fused MLP step: a learning-rate ring (lr_ring=%d) takes the data-parallel exchange out of "
+                        "the one-launch step (its schedule instances exist at world size 1 only): every step runs "
+                        "as two launches, head + tail with the in-kernel exchange", self.lr_ring)
         self.stats = torch.zeros(stats_ring, 4, device=self.device)
         self.seed = seed
         self.epoch = 0
@@ -467,6 +492,7 @@ class FusedMLPEngine:
     def set_step(self, step: int) -> None:
         self.counters[0] = int(step)
         self.optimizer_steps = int(step)
+        self._sched_end = 0  # a schedule belongs to the count it was given under
         self._publish_counters()
 
     @property
@@ -482,7 +508,8 @@ class FusedMLPEngine:
         ctx, name = self.dp_ctx, self.dp_proto
         need = 2 * fused_mlp.mlp_param_count(self.L1, self.L2) if name == "granule" else fused_mlp.DP_AREA_FLOATS
         return (self.one_launch and ctx is not None and name in fused_mlp.DP_PROTOS and ctx[2] >= need
-                and (self.x_scale, self.x_shift) == fused_mlp.input_affine(None))
+                and (self.x_scale, self.x_shift) == fused_mlp.input_affine(None)
+                and not self.lr_mask)  # nor a schedule instance: a rate ring runs in the two-launch tail
 
     def _set_normalize(self, normalize) -> None:
         """The dataset's single-channel ``Normalize(mean, std)`` (None: ToTensor alone).  A
@@ -630,8 +657,90 @@ class FusedMLPEngine:
         self.refresh_shadow()
 
     def set_lr(self, lr: float) -> None:
+        """The rate of every step from now on (ring mode: the whole ring, and any schedule is
+        forgotten)."""
         self.lr = float(lr)
         self.lr_tensor.fill_(self.lr)
+        if self.lr_mask:
+            self._ring_host = [self.lr] * self.lr_ring
+            self._ring_uniform = self.lr
+            self._sched_end = 0
+
+    # ------------------------------------------------------------- LR ring
+    def set_lr_schedule(self, rates: Sequence[float]) -> None:
+        """Ring mode: ``rates[i]`` is the learning rate of optimizer step
+        ``optimizer_steps + 1 + i`` (at most ``lr_ring`` of them; an earlier schedule is
+        replaced).  The values travel in stream order with the launches -- steps already
+        dispatched keep their rates, no host sync -- and are rounded to fp32 as
+        ``set_lr`` rounds, so a scheduled run equals a ``set_lr``-per-step run bit for bit.
+        Steps past the schedule run at ``lr``."""
+        if not self.lr_mask:
+            raise RuntimeError("set_lr_schedule needs ring mode: build the engine with lr_ring=<power of two>")
+        rates = [float(r) for r in rates]
+        if len(rates) > self.lr_ring:
+            raise ValueError(f"set_lr_schedule: {len(rates)} rates do not fit a ring of {self.lr_ring}")
+        self._sched_end = 0
+        if rates:
+            self._ring_write(self.optimizer_steps + 1, rates)
+            self._sched_end = self.optimizer_steps + len(rates)
+
+    def _ring_write(self, first_step: int, rates: Sequence[float]) -> None:
+        """Entries of optimizer steps ``first_step ..`` := ``rates`` (<= lr_ring values), on
+        the current stream; two copies where the range wraps."""
+        n, R = len(rates), self.lr_ring
+        i0 = (first_step - 1) & self.lr_mask
+        for j, r in enumerate(rates):
+            self._ring_host[(i0 + j) & self.lr_mask] = r
+        if self._ring_uniform is None or any(r != self._ring_uniform for r in rates):
+            self._ring_uniform = None
+        src = torch.tensor(rates, dtype=torch.float64).to(torch.float32)  # fill_'s rounding
+        buf = None
+        if self.native:
+            buf = self._stage_buffer()
+            buf[:n].copy_(src)
+            src = buf
+        n1 = min(n, R - i0)
+        self.lr_tensor[i0:i0 + n1].copy_(src[:n1], non_blocking=True)
+        if n1 < n:
+            self.lr_tensor[:n - n1].copy_(src[n1:n], non_blocking=True)
+        if buf is not None:
+            ev = torch.cuda.Event()
+            ev.record()
+            self._lr_stage.append((buf, ev))
+
+    def _stage_buffer(self) -> torch.Tensor:
+        """A pinned ``[lr_ring]`` buffer no copy still reads: chunks are dispatched back to
+        back without a sync, so a buffer is taken again only once the event behind its last
+        copy has completed (else a new one joins the pool)."""
+        for k, (b, ev) in enumerate(self._lr_stage):
+            if ev.query():
+                del self._lr_stage[k]
+                return b
+        return torch.empty(self.lr_ring, dtype=torch.float32, pin_memory=True)
+
+    def _opt_steps_in(self, n: int) -> int:
+        """Optimizer steps among the next ``n`` batches (accumulation: the windows that close)."""
+        if self.accumulate == 1:
+            return n
+        return sum(self._window(self.step_in_epoch + i)[1] for i in range(n))
+
+    def _ring_prepare(self, n: int) -> None:
+        """Ring mode, before ``n`` batches are dispatched: the optimizer steps among them that
+        have no scheduled rate get ``lr`` written into their entries (stream-ordered)."""
+        if not self.lr_mask or self._ring_uniform == self.lr:
+            return
+        t0 = self.optimizer_steps + 1
+        lo, hi = max(t0, self._sched_end + 1), t0 + self._opt_steps_in(n)
+        if hi - lo > self.lr_ring:
+            raise RuntimeError(f"ring mode: one dispatch of {hi - lo} optimizer steps exceeds lr_ring={self.lr_ring}")
+        if lo < hi and any(self._ring_host[(t - 1) & self.lr_mask] != self.lr for t in range(lo, hi)):
+            i0, m = (lo - 1) & self.lr_mask, hi - lo
+            n1 = min(m, self.lr_ring - i0)
+            self.lr_tensor[i0:i0 + n1].fill_(self.lr)
+            if n1 < m:
+                self.lr_tensor[:m - n1].fill_(self.lr)
+            for t in range(lo, hi):
+                self._ring_host[(t - 1) & self.lr_mask] = self.lr
 
     # ----------------------------------------------------------------- step
     def _kw3(self) -> dict:
@@ -641,7 +750,7 @@ class FusedMLPEngine:
                     dh1t=self.dh1t, xring=self.xring, h1pre=self.h1pre, act=self.act, yring=self.yring,
                     head_part=self.head_part, hand=self.hand, lr=self.lr, betas=self.betas,
                     eps=self.eps, weight_decay=self.wd, lr_tensor=self.lr_tensor, adamw=self.adamw,
-                    x_scale=self.x_scale, x_shift=self.x_shift, last_rows=self.last_rows)
+                    x_scale=self.x_scale, x_shift=self.x_shift, last_rows=self.last_rows, lr_mask=self.lr_mask)
 
     def _short_pos(self, pos: int) -> bool:
         """Whether the step at epoch position ``pos`` touches the epoch's short last batch:
@@ -751,6 +860,10 @@ class FusedMLPEngine:
         c = self.counters
         cursor, ob = int(c[1]), int(c[4])
         acc = self.accumulate > 1
+        # the reference kernels keep their one-scalar contract: the ring entry of the optimizer
+        # step this window applies (counters[0] + 1), as a one-element view
+        i_lr = int(c[0]) & self.lr_mask
+        lr_now = self.lr_tensor[i_lr:i_lr + 1]
         # SGD: mlp_train_step leaves the gradient, fused_sgd_ follows below
         fused = self.world_size == 1 and self.clip_norm is None and not acc and not self.sgd
         fused_mlp.mlp_train_step(
@@ -758,7 +871,7 @@ class FusedMLPEngine:
             order=self.order[ob], counters=c[:2], n_batches=self.n_batches, exp_avg=self.exp_avg,
             exp_avg_sq=self.exp_avg_sq, stats=self._head_row if acc else self.stats, accumulate_grad=micro > 0,
             apply_adam=fused, advance_step=closing, lr=self.lr,
-            betas=self.betas, eps=self.eps, weight_decay=self.wd, lr_tensor=self.lr_tensor, adamw=self.adamw,
+            betas=self.betas, eps=self.eps, weight_decay=self.wd, lr_tensor=lr_now, adamw=self.adamw,
             x_scale=self.x_scale, x_shift=self.x_shift, last_rows=self.last_rows,
         )
         c[2] = cursor
@@ -781,11 +894,11 @@ class FusedMLPEngine:
                 fused_sgd_(self.params, self.grads, self.exp_avg if self.momentum != 0.0 else None, lr=self.lr,
                            momentum=self.momentum, dampening=self.dampening, weight_decay=self.wd,
                            nesterov=self.nesterov, grad_scale=self._grad_scale, step=self.counters[0:1],
-                           lr_tensor=self.lr_tensor)
+                           lr_tensor=lr_now)
                 return
             fused_adam_(self.params, self.grads, self.exp_avg, self.exp_avg_sq, lr=self.lr, betas=self.betas,
                         eps=self.eps, weight_decay=self.wd, grad_scale=self._grad_scale, adamw=self.adamw,
-                        step=self.counters[0:1], lr_tensor=self.lr_tensor)
+                        step=self.counters[0:1], lr_tensor=lr_now)
 
     def _reference_clip(self) -> None:
         """The ADAM tail's clipping in torch fp32: scales ``grads`` in place by the
@@ -806,10 +919,7 @@ class FusedMLPEngine:
         self.clip_out[0], self.clip_out[1] = norm, coef
 
     def _advance_host(self, n: int) -> None:
-        if self.accumulate == 1:
-            self.optimizer_steps += n
-        else:  # the windows that close among the n batches from step_in_epoch on
-            self.optimizer_steps += sum(self._window(self.step_in_epoch + i)[1] for i in range(n))
+        self.optimizer_steps += self._opt_steps_in(n)  # accumulation: the windows that close
         self.global_step += n
         self.step_in_epoch += n
         if self.step_in_epoch >= self.n_batches:
@@ -841,8 +951,12 @@ class FusedMLPEngine:
             # a graph holds whole windows: each captured launch has its place in the window baked in
             raise ValueError(f"capture({steps_per_graph}): with accumulate={K} a graph must hold whole windows "
                              f"(a multiple of {K} batches)")
+        if self.lr_mask and steps_per_graph // K > self.lr_ring:
+            raise ValueError(f"capture({steps_per_graph}): a graph of {steps_per_graph // K} optimizer steps does "
+                             f"not fit the learning-rate ring (lr_ring={self.lr_ring})")
         if not self.native:
             return False
+        self._ring_prepare(K)  # the warm-up batches' rates, ahead of the side stream's wait
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         # warm the allocator / RCCL outside capture (a real step; keeps counters consistent);
@@ -908,9 +1022,11 @@ class FusedMLPEngine:
         """Run one (or ``steps_per_graph`` when captured) batch(es): optimizer steps, or
         micro-batches with ``accumulate`` > 1."""
         if self._graph_ok(self._graph_steps):
+            self._ring_prepare(self._graph_steps)
             self._graph.replay()
             self._advance_host(self._graph_steps)
             return
+        self._ring_prepare(1)
         self._device_step()
         self._advance_host(1)
 
@@ -918,6 +1034,7 @@ class FusedMLPEngine:
         done = 0
         while done < n_steps:
             g, k = self._pick_graph(n_steps - done)
+            self._ring_prepare(k)
             if g is not None:
                 g.replay()
             else:
