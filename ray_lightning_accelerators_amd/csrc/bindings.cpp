@@ -5,6 +5,7 @@
 // built for (an out-of-bounds access can reset every GPU of the host).
 #include <torch/extension.h>
 #include <algorithm>
+#include <climits>
 #include <cstdlib>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
@@ -954,6 +955,34 @@ std::vector<Tensor> conv1x1_stats(Tensor x, Tensor w, optional<Tensor> pre_ss, o
   return {y, part};
 }
 
+// The same forward on the wide-tile split-K kernel (csrc/conv1x1_wide.hip, K >= 256).
+// bn / splits 0: the planner's instance; else that one, refused where the shape does not
+// admit it.  The split workspace and its ticket counters are allocated on the current stream.
+std::vector<Tensor> conv1x1_wide(Tensor x, Tensor w, int64_t bn, int64_t splits) {
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && w.size(1) == x.size(1), "conv1x1_wide: x must be [M, K] and w [N, K]");
+  const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
+  const uint16_t* xp = bf16_operand(x, "conv1x1_wide: x", M * K, x);
+  const uint16_t* wp = bf16_operand(w, "conv1x1_wide: w", N * K, x);
+  TORCH_CHECK(K <= INT_MAX && N <= INT_MAX && rla::conv1x1_wide_ok(M, (int)K, (int)N),
+              "conv1x1_wide: unsupported shape (K >= 256, K % 64, N % 128, N <= 4096)");
+  TORCH_CHECK(bn >= 0 && bn <= 256 && splits >= 0 && splits <= 4, "conv1x1_wide: bn is 0 / 128 / 256, splits 0 / 1 / 2 / 4");
+  const rla::Conv1x1WidePlan p = rla::conv1x1_wide_plan(M, (int)K, (int)N, (int)bn, (int)splits);
+  TORCH_CHECK(p.bn != 0, "conv1x1_wide: [", M, ", ", K, "] x [", N, ", ", K, "] does not admit bn = ", bn,
+              ", splits = ", splits, " (bn divides N; splits > 1 only with one tile per workgroup)");
+  const at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor y = at::empty({M, N}, x.options());
+  Tensor part = at::empty({p.gx, 2, N}, x.options().dtype(at::kFloat));
+  Tensor ws, cnt;
+  if (p.splits > 1) {
+    ws = at::empty({rla::conv1x1_wide_ws_floats(M, (int)N, p)}, x.options().dtype(at::kFloat));
+    cnt = at::zeros({rla::conv1x1_wide_tiles(M, (int)N, p)}, x.options().dtype(at::kInt));
+  }
+  rla::launch_conv1x1_wide(xp, wp, reinterpret_cast<uint16_t*>(y.data_ptr()), M, (int)K, (int)N, p,
+                           part.data_ptr<float>(), p.splits > 1 ? ws.data_ptr<float>() : nullptr,
+                           p.splits > 1 ? reinterpret_cast<unsigned*>(cnt.data_ptr()) : nullptr, cur_stream(x));
+  return {y, part};
+}
+
 void bn_bwd_apply(Tensor x, optional<Tensor> y, Tensor dy, Tensor coef, bool relu, Tensor dx,
                   optional<Tensor> dres, optional<Tensor> dy2, optional<Tensor> ss, optional<Tensor> pool_arg,
                   std::vector<int64_t> pool_geo) {
@@ -1264,6 +1293,14 @@ std::vector<int64_t> conv1x1_plan(int64_t M, int64_t K, int64_t N, bool bwd) {
   return {p.tnw, p.gy, p.gx, p.tiles_per_blk, rla::conv1x1_variant((int)K, p)};
 }
 
+// (bn, splits, gx, tiles_per_blk, rows) the planner gives conv1x1_wide for the current plan CU count
+std::vector<int64_t> conv1x1_wide_plan(int64_t M, int64_t K, int64_t N) {
+  TORCH_CHECK(K <= INT_MAX && N <= INT_MAX && rla::conv1x1_wide_ok(M, (int)K, (int)N),
+              "conv1x1_wide_plan: unsupported shape");
+  const rla::Conv1x1WidePlan p = rla::conv1x1_wide_plan(M, (int)K, (int)N);
+  return {p.bn, p.splits, p.gx, p.tiles_per_blk, p.gx};
+}
+
 Tensor dp_pack_roundtrip(Tensor x, int64_t tag) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat && x.is_contiguous(), "x: contiguous fp32 on the GPU");
   Tensor y = at::empty_like(x);
@@ -1349,6 +1386,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("shift"), py::arg("res"), py::arg("relu"), py::arg("y"), py::arg("nbt_inc") = py::none());
   m.def("conv1x1_stats", &conv1x1_stats, "1x1 conv forward on MFMA + BatchNorm partial sums of its output",
         py::arg("x"), py::arg("w"), py::arg("pre_ss") = py::none(), py::arg("nbt_inc") = py::none());
+  m.def("conv1x1_wide", &conv1x1_wide,
+        "1x1 conv forward (K >= 256) on the wide-tile split-K MFMA kernel + BatchNorm partial sums of its output; "
+        "bn / splits 0: the planner's instance",
+        py::arg("x"), py::arg("w"), py::arg("bn") = 0, py::arg("splits") = 0);
+  m.def("conv1x1_wide_ok", [](int64_t M, int64_t K, int64_t N) {
+    return K <= INT_MAX && N <= INT_MAX && rla::conv1x1_wide_ok(M, (int)K, (int)N);
+  });
+  m.def("conv1x1_wide_plan", &conv1x1_wide_plan, "the wide 1x1 kernel's (bn, splits, gx, tiles_per_blk, rows)",
+        py::arg("M"), py::arg("K"), py::arg("N"));
   m.def("conv1x1_pre_ok", [](int64_t M, int64_t K, int64_t N) { return rla::conv1x1_pre_ok(M, (int)K, (int)N); });
   m.def("conv1x1_bn_bwd", &conv1x1_bn_bwd,
         "1x1 conv input gradient fused with the previous BatchNorm's backward partial -> (d, part)");

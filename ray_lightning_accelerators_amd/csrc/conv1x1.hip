@@ -46,6 +46,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "lds_dma.h"
 
 namespace rla {
 namespace {
@@ -56,16 +57,6 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kC1Threads = 256;
 constexpr int kC1LdsBytes = 65536;  // ring (+ resident weights) per workgroup: 2 workgroups per CU
-
-// 16 bytes per lane, global -> LDS, lane-linear from the wave-uniform LDS byte
-// address `lds`; M0 saved and restored in the same statement (LDS-DMA recipe)
-__device__ __forceinline__ void c1_dma16(const void* gsrc, uint32_t lds) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(gsrc), "s"(lds)
-               : "memory");
-}
 
 // BWD: the same GEMM as an input gradient (x = the conv's output gradient dy1 [M][K],
 // w = its weight transposed [N = Cin][K = Cout]) whose epilogue is the PREVIOUS

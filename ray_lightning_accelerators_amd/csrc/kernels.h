@@ -203,6 +203,25 @@ int conv1x1_variant(int K, const Conv1x1Plan& p);
 void launch_conv1x1_stats(const uint16_t* x, const uint16_t* w, uint16_t* y, int64_t M, int K, int N,
                           const Conv1x1Plan& p, float* part, hipStream_t s, const float* pre_ss = nullptr,
                           int64_t* nbt_inc = nullptr);
+// The same contract for K >= 256 (csrc/conv1x1_wide.hip): 128 x bn tiles on one 512-thread
+// workgroup per CU, 64-channel stages, and a fixed-order split-K over `splits` slices of a
+// tile where the tiles cannot fill the machine.  part is [gx, 2, N].
+struct Conv1x1WidePlan {
+  int bn;             // workgroup channels, 256 or 128; 0: the shape does not admit the plan asked for
+  int splits;         // K-slices per tile: 1, 2 or 4 (> 1 only with tiles_per_blk == 1)
+  int gx;             // pixel ranges = partial rows (multiple of 8)
+  int tiles_per_blk;  // 128-pixel tiles per range
+};
+// K >= 256, K % 64 == 0, N % 128 == 0, N <= 4096
+bool conv1x1_wide_ok(int64_t M, int K, int N);
+// bn / splits 0: the planner's choice (plan_cus()); else that instance, or bn == 0 back
+Conv1x1WidePlan conv1x1_wide_plan(int64_t M, int K, int N, int bn = 0, int splits = 0);
+// splits > 1: the tiles (= ticket counters, zero at launch and again afterwards) and the
+// fp32 workspace [tiles][splits][128 x bn]; else 0
+int64_t conv1x1_wide_tiles(int64_t M, int N, const Conv1x1WidePlan& p);
+int64_t conv1x1_wide_ws_floats(int64_t M, int N, const Conv1x1WidePlan& p);
+void launch_conv1x1_wide(const uint16_t* x, const uint16_t* w, uint16_t* y, int64_t M, int K, int N,
+                         const Conv1x1WidePlan& p, float* part, float* ws, unsigned* counters, hipStream_t s);
 // input gradient of a 1x1 conv (dy1 [M][K] . W, wt = W^T [N][K]) fused with the previous
 // BatchNorm's backward partial: d = (da + dy2) * (yb > 0) written to d, part [rows, 2, N]
 // = sums of d and d * xb.  part == nullptr: only *rows is set (the partial row count).

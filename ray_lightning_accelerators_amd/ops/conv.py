@@ -126,14 +126,15 @@ def _run(op: str, key: Tuple[int, ...], cands: Dict[str, Callable]):
     return cands[_pick(op, key, cands)]()
 
 
-def _run_stats(op: str, key: Tuple[int, ...], cands: Dict[str, Callable], fused: str, bn_stats: "BNStats"):
-    """``_run`` for a forward whose output a training BatchNorm reads: ``cands[fused]``
-    returns (y, part) from a statistics epilogue and hands ``part`` to that BatchNorm;
-    the others return y alone and BatchNorm then runs its own partial pass, so they
-    are timed with that pass (and run without it)."""
-    timed = {name: fn if name == fused else (lambda fn=fn: _bn_partial(fn())) for name, fn in cands.items()}
+def _run_stats(op: str, key: Tuple[int, ...], cands: Dict[str, Callable], fused: Tuple[str, ...],
+               bn_stats: "BNStats"):
+    """``_run`` for a forward whose output a training BatchNorm reads: the candidates
+    named in ``fused`` return (y, part) from a statistics epilogue and hand ``part`` to
+    that BatchNorm; the others return y alone and BatchNorm then runs its own partial
+    pass, so they are timed with that pass (and run without it)."""
+    timed = {name: fn if name in fused else (lambda fn=fn: _bn_partial(fn())) for name, fn in cands.items()}
     name = _pick(op, key, timed)
-    if name != fused:
+    if name not in fused:
         return cands[name]()
     y, bn_stats.part = cands[name]()
     return y
@@ -546,6 +547,31 @@ def conv1x1_stats_hip(x: torch.Tensor, wb: torch.Tensor, pre=None):
     return _from2d(y2, n, h, w), part
 
 
+def conv1x1_wide_ok(m: int, cin: int, cout: int) -> bool:
+    """Shapes of the wide-tile, fixed-order split-K 1x1 forward with BatchNorm statistics
+    (csrc/conv1x1_wide.hip): cin >= 256, cin % 64 == 0, cout % 128 == 0.
+    ``RLA_CONV1X1_STATS=off`` turns it off together with the other statistics forward."""
+    return os.environ.get("RLA_CONV1X1_STATS", "auto") != "off" and _conv1x1_wide_shape_ok(m, cin, cout)
+
+
+@functools.lru_cache(maxsize=256)
+def _conv1x1_wide_shape_ok(m: int, k: int, n: int) -> bool:
+    from . import require
+
+    return bool(require().conv1x1_wide_ok(m, k, n))
+
+
+def conv1x1_wide_hip(x: torch.Tensor, wb: torch.Tensor):
+    """:func:`conv1x1_stats_hip` on the wide-tile kernel, the planner's instance: ``x``
+    [N, Cin, H, W] channels_last bf16, ``wb`` [Cout, Cin] bf16.  Returns (y channels_last,
+    part [rows, 2, Cout]); bitwise reproducible (its split-K adds in slice order)."""
+    from . import require
+
+    n, _, h, w = x.shape
+    y2, part = require().conv1x1_wide(_nhwc2d(x), wb)
+    return _from2d(y2, n, h, w), part
+
+
 def conv1x1_pre_ok(m: int, cin: int, cout: int) -> bool:
     """Where a 1x1 conv applies a deferred BatchNorm + ReLU in its own kernels (forward
     and weight gradient): K <= 128, the shapes whose forward runs on the in-tree kernel
@@ -595,7 +621,13 @@ class _Conv1x1Fn(torch.autograd.Function):
         elif bn_stats is not None and conv1x1_stats_ok(x2.size(0), cin, cout):
             # the next BatchNorm's statistics: in this GEMM's epilogue, or the library
             # forward + BN's own partial pass -- whichever is faster for the shape
-            y = _run_stats("fwd_st", key, {"hip": lambda: conv1x1_stats_hip(x, wb), **cands}, "hip", bn_stats)
+            fused = {"hip": lambda: conv1x1_stats_hip(x, wb)}
+            if _mode() == "hip_wide" and conv1x1_wide_ok(x2.size(0), cin, cout):
+                # cin >= 256: the wide-tile kernel, only when pinned -- it beats "hip" but no
+                # library entry at any ResNet-50 shape (docs/resnet50.md), so the timed pick
+                # is not lengthened by it
+                fused["hip_wide"] = lambda: conv1x1_wide_hip(x, wb)
+            y = _run_stats("fwd_st", key, {**fused, **cands}, tuple(fused), bn_stats)
         else:
             y = _run("fwd", key, cands)
         ctx.save_for_backward(x, wb)
@@ -749,7 +781,7 @@ class _ConvNHWCFn(torch.autograd.Function):
             if (bn_stats is not None and conv3x3_stats_enabled()
                     and not torch.are_deterministic_algorithms_enabled()):
                 cands["hip_st"] = lambda: conv3x3s2_stats_hip(x, wb)
-                y = _run_stats("fwd_kxk_st", key, cands, "hip_st", bn_stats)
+                y = _run_stats("fwd_kxk_st", key, cands, ("hip_st",), bn_stats)
             else:
                 # deterministic mode too: _pick's fixed order lands on "hip" (bitwise
                 # reproducible) and the BatchNorm makes its own pass
@@ -763,7 +795,7 @@ class _ConvNHWCFn(torch.autograd.Function):
                 # the next BatchNorm's statistics: in this kernel's epilogue, or the
                 # library forward + BN's own partial pass -- whichever is faster
                 cands["hip_st"] = lambda: conv3x3_stats_hip(x, wb)
-                y = _run_stats("fwd_kxk_st", key, cands, "hip_st", bn_stats)
+                y = _run_stats("fwd_kxk_st", key, cands, ("hip_st",), bn_stats)
             else:
                 cands["hip"] = lambda: conv3x3_hip(x, wb)
                 y = _run("fwd_kxk", key, cands)
