@@ -308,9 +308,21 @@ void mlp_train_step(optional<Tensor> x_u8, optional<Tensor> x_f32, Tensor labels
                     optional<Tensor> exp_avg_sq, optional<Tensor> stats, bool accumulate_grad,
                     bool apply_adam, bool advance_step, double lr, double beta1, double beta2,
                     double eps, double weight_decay, optional<Tensor> lr_t, bool adamw,
-                    optional<Tensor> stamps, double x_scale, double x_shift) {
+                    optional<Tensor> stamps, double x_scale, double x_shift, optional<int64_t> last_rows,
+                    int64_t lr_mask, optional<Tensor> wide_park, optional<Tensor> wide_part,
+                    optional<Tensor> wide_hdr) {
   TORCH_CHECK(rla::mlp_supported((int)L1, (int)L2), "no fused MLP kernel for layer sizes ", L1, "/", L2);
-  TORCH_CHECK(B >= 1, "batch size must be >= 1");
+  TORCH_CHECK_VALUE(B >= 1 && B <= rla::kMLPWideMaxB, "mlp_train_step: batch size must be in [1, ",
+                    rla::kMLPWideMaxB, "], got ", B, " (nothing was launched)");
+  // above 256 rows: the wide family (csrc/mlp_step_wide.hip); at or below, the one-workgroup kernel
+  const bool wide = B >= rla::kMLPWideMinB;
+  const int64_t rows_last = last_rows.has_value() ? *last_rows : B;
+  TORCH_CHECK_VALUE(rows_last >= 1 && rows_last <= B, "mlp_train_step: last_rows must be in [1, B = ", B, "], got ",
+                    rows_last, " (nothing was launched)");
+  TORCH_CHECK_VALUE(wide || (rows_last == B && lr_mask == 0),
+                    "mlp_train_step: last_rows < B and lr_mask belong to the wide step (B > 256)");
+  TORCH_CHECK_VALUE(lr_mask >= 0 && lr_mask < (1 << 20) && (lr_mask & (lr_mask + 1)) == 0,
+                    "mlp_train_step: lr_mask must be 2^k - 1, got ", lr_mask);
   const int64_t np = mlp_param_count(L1, L2);
   check_dev(params, "params", at::kFloat);
   check_dev(grads, "grads", at::kFloat);
@@ -350,10 +362,40 @@ void mlp_train_step(optional<Tensor> x_u8, optional<Tensor> x_f32, Tensor labels
   a.advance_step = advance_step;
   a.lr = (float)lr; a.beta1 = (float)beta1; a.beta2 = (float)beta2; a.eps = (float)eps;
   a.weight_decay = (float)weight_decay;
-  a.lr_ptr = ptr_or_null<const float>(lr_t, "lr", at::kFloat, 1);
+  a.lr_ptr = ptr_or_null<const float>(lr_t, "lr", at::kFloat, lr_mask + 1);
   a.adamw = adamw;
   a.stamps = ptr_or_null<int64_t>(stamps, "stamps", at::kLong, 16);
   a.x_scale = (float)x_scale; a.x_shift = (float)x_shift;
+  if (wide) {
+    // every operand is checked here, before the first of the three launches
+    TORCH_CHECK_VALUE(a.x_u8 || rows_last == B, "mlp_train_step: last_rows < B needs u8 mode");
+    TORCH_CHECK_VALUE(lr_mask == 0 || a.lr_ptr, "mlp_train_step: lr_mask = ", lr_mask, " needs lr_t of ",
+                      lr_mask + 1, " rates");
+    TORCH_CHECK(a.counters || !a.x_u8, "mlp_train_step: u8 mode needs device counters");
+    const rla::MLPWideLayout lay = rla::mlp_wide_layout((int)L1, (int)L2, (int)B);
+    rla::MLPWideArgs w{};
+    w.park = ptr_or_null<uint16_t>(wide_park, "wide_park", at::kBFloat16, lay.park_elems);
+    w.part = ptr_or_null<float>(wide_part, "wide_part", at::kFloat, lay.part_elems);
+    w.hdr = ptr_or_null<int64_t>(wide_hdr, "wide_hdr", at::kLong, 4);
+    TORCH_CHECK_VALUE(w.park && w.part && w.hdr, "mlp_train_step: B = ", B, " > 256 needs the wide workspace "
+                      "(ops.fused_mlp.mlp_wide_buffers: wide_park, wide_part, wide_hdr)");
+    for (const Tensor* t : {&params, &grads, &*wide_park, &*wide_part, &*wide_hdr, &labels})
+      TORCH_CHECK(t->device() == params.device(), "mlp_train_step: every operand must be on ", params.device());
+    check_aligned(params, "params", 16);
+    check_aligned(*wide_park, "wide_park", 16);
+    check_aligned(*wide_part, "wide_part", 16);
+    if (a.x_u8) check_aligned(*x_u8, "x_u8", 16);
+    else check_aligned(*x_f32, "x_f32", 16);
+    w.step = a;
+    w.park_elems = wide_park->numel();
+    w.part_elems = wide_part->numel();
+    w.last_rows = (int)rows_last;
+    w.lr_mask = (int)lr_mask;
+    const int rc = rla::launch_mlp_wide_step(w, cur_stream(params));
+    check_input_affine(rc, "mlp_train_step", x_scale, x_shift);
+    TORCH_CHECK(rc == 0, "wide fused MLP launch refused (code ", rc, "; nothing was launched)");
+    return;
+  }
   const int rc = rla::launch_mlp_train_step(a, cur_stream(params));
   check_input_affine(rc, "mlp_train_step", x_scale, x_shift);
   TORCH_CHECK(rc == 0, "fused MLP launch failed");
@@ -1331,7 +1373,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("accumulate_grad"), py::arg("apply_adam"), py::arg("advance_step"), py::arg("lr"),
         py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"), py::arg("lr_t"),
         py::arg("adamw"), py::arg("stamps") = py::none(), py::arg("x_scale") = (double)rla::kMLPXScale,
-        py::arg("x_shift") = 0.0);
+        py::arg("x_shift") = 0.0, py::arg("last_rows") = py::none(), py::arg("lr_mask") = 0,
+        py::arg("wide_park") = py::none(), py::arg("wide_part") = py::none(), py::arg("wide_hdr") = py::none());
+  m.def("mlp_wide_layout", [](int64_t L1, int64_t L2, int64_t B) {
+    const rla::MLPWideLayout l = rla::mlp_wide_layout((int)L1, (int)L2, (int)B);
+    py::dict d;
+    d["nslab"] = l.nslab; d["Bp"] = l.Bp; d["slices"] = l.slices; d["np_pad"] = l.np_pad;
+    d["park_elems"] = l.park_elems; d["part_elems"] = l.part_elems;
+    return d;
+  }, "workspace layout of the wide MLP step (csrc/mlp_step_wide.hip)");
   m.def("mlp_eval", &mlp_eval, "fused MNIST-MLP forward + NLL/accuracy (u8 mode: pixel = fma(u8, x_scale, x_shift))",
         py::arg("x_u8"), py::arg("x_f32"), py::arg("labels"), py::arg("index"), py::arg("B"), py::arg("L1"),
         py::arg("L2"), py::arg("params"), py::arg("logits"), py::arg("out"),

@@ -473,6 +473,41 @@ int launch_mlp_eval(const MLPEvalArgs& a, hipStream_t stream);
 bool mlp_supported(int L1, int L2);
 int launch_mlp_adam(const MLPAdamArgs& a, hipStream_t stream);
 
+// ---------------------------------------------------------------------------
+// Wide-batch step (csrc/mlp_step_wide.hip): mlp_train_step's contract for
+// kMLPWideMinB <= B <= kMLPWideMaxB, three launches (64-row slabs, gradient tiles x
+// batch slices, slice sum + epilogue), every reduction in a fixed order.
+// ---------------------------------------------------------------------------
+constexpr int kMLPWideMinB = 257, kMLPWideMaxB = 4096;
+constexpr int kMLPWideWaveSlots = 1024;  // tiles x slices aims at 256 CUs x 4 waves
+constexpr int kMLPWideMaxSlices = 16;
+
+struct MLPWideLayout {
+  int nslab;           // 64-row slabs
+  int64_t Bp;          // nslab * 64: the row stride of every parked operand
+  int slices;          // batch slices of the parameter launch
+  int64_t np_pad;      // floats per slice partial (the arena rounded up to 4)
+  int64_t park_elems;  // bf16: XT[784] H1T[L1] H2T[L2] dH2T[L2] dZT[16] dH1T[L1], each [.][Bp]
+  int64_t part_elems;  // fp32: [slices][np_pad] partials, then [nslab][4] slab stats
+};
+MLPWideLayout mlp_wide_layout(int L1, int L2, int B);
+
+struct MLPWideArgs {
+  MLPStepArgs step;     // shadow / dh1t / stamps unused
+  uint16_t* park;       // workspace (mlp_wide_layout), 16-byte aligned
+  float* part;          // 16-byte aligned
+  int64_t* hdr;         // [4]: the step's (t, cursor, rows), handed from launch 1 to launch 3
+  int64_t park_elems, part_elems;
+  int last_rows;        // rows of the batch at cursor n_batches - 1 (u8 mode); else B
+  int lr_mask;          // lr_ptr is a ring of lr_mask + 1 rates, entry (t - 1) & lr_mask
+  // filled by launch_mlp_wide_step:
+  int64_t Bp, np_pad;
+  float* slab_stats;
+};
+// 0, or before any launch: -1 widths, -2 batch outside the range, -13 pixel map, -15 last_rows,
+// -16 lr_mask, -17 workspace missing or too small
+int launch_mlp_wide_step(const MLPWideArgs& a, hipStream_t stream);
+
 }  // namespace rla
 
 namespace rla {

@@ -33,6 +33,12 @@ as well: it is the epoch's last step, over its own rows (``begin_epoch(last_rows
 loss and gradient over ``r`` rows, a stats row that counts ``r``), run as head / tail where the
 other steps are one launch; ``eval_epoch`` weighs a partial validation batch like a full one,
 as the eager loop does.  Only the in-kernel exchange still drops it (one warning).
+Batch sizes 257 .. 4096 (``ops.fused_mlp.WIDE_MAX_B``) run the wide step of
+csrc/mlp_step_wide.hip -- 64-row slabs, gradient tiles split over the batch, a fixed-order slice
+sum with Adam / AdamW -- through the same engine (``FusedMLPEngine(batch_size=512)``: graphs,
+stats ring, short last batch and LR ring as below 256).  Clipping, accumulation and SGD above
+256 rows step through the loader-fed branch of ``train_batch``: ``mlp_train_step`` on the same
+wide kernels, then the allreduce, clip and optimizer launches that branch always had.
 
 Datasets the resident path serves (``_u8_source``; ``Subset`` / ``random_split`` chains of
 them included): ``.images`` uint8 ``[N, 784]`` with tensor ``.targets`` (``SyntheticMNIST``),
@@ -328,7 +334,7 @@ class FusedMNISTStep:
         # accumulation steps once per window, the in-kernel exchange at every batch; and the
         # exchange's epilogue is Adam / AdamW, so SGD takes the allreduce route too
         if self.world > 1 and get_config().fused_dp and self.clip_norm is None and self.accumulate == 1 \
-                and not self.sgd:
+                and not self.sgd and B <= 256:  # (the in-kernel exchange stops at 256 rows)
             from ..parallel.comm import get_native_comm
 
             comm = get_native_comm()  # every rank reaches here together (first epoch)
@@ -389,6 +395,12 @@ class FusedMNISTStep:
         else:
             order = self._epoch_order(dl.sampler, idx_map)
         B = dl.batch_size
+        if B > 256 and (B > fused_mlp.WIDE_MAX_B or self.clip_norm is not None or self.accumulate > 1 or self.sgd
+                        or (self.lr_ring and self.world > 1)):
+            # above 256 rows the engine serves Adam / AdamW alone (the wide step); clipping,
+            # accumulation and SGD step through the loader-fed branch of train_batch, whose
+            # mlp_train_step takes the same wide kernels
+            return None
         full, rem = divmod(order.numel(), B)
         nb = min(n_batches, full if dl.drop_last else -(-order.numel() // B))
         # the short last batch of a drop_last=False loader is the epoch's last step: its

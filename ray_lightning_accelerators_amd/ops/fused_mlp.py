@@ -21,6 +21,7 @@ from . import require, use_native
 
 IN_FEATURES = 784
 NUM_CLASSES = 10
+WIDE_MIN_B, WIDE_MAX_B = 257, 4096  # the wide step (csrc/mlp_step_wide.hip): 256 < B <= 4096
 SUPPORTED = {(32, 32), (32, 64), (32, 128), (32, 256), (64, 64), (64, 128), (64, 256),
              (128, 64), (128, 128), (128, 256)}
 
@@ -183,6 +184,8 @@ def mlp_train_step(
     x_scale: float = X_SCALE_DEFAULT,
     x_shift: float = 0.0,
     last_rows: Optional[int] = None,
+    lr_mask: int = 0,
+    workspace: Optional[Dict[str, torch.Tensor]] = None,
 ) -> None:
     """One training micro-step of the MNIST MLP over a flat parameter arena.
 
@@ -191,23 +194,45 @@ def mlp_train_step(
     step advances (mod ``n_batches``) -- so a captured hipGraph replays
     successive batches.  ``counters[0]`` is the optimizer step t.  A pixel enters the
     network as ``fmaf(u8, x_scale, x_shift)`` (``input_affine``); ``x_f32`` mode ignores both.
-    ``last_rows`` (u8 mode, the fp32 reference only): the batch at cursor ``n_batches - 1``
-    holds that many rows, ``order[cursor*B : cursor*B + last_rows]``; loss and gradient are
-    their mean and the stats row counts them (None or ``B``: every batch is full).
+    ``last_rows`` (u8 mode; the fp32 reference and, above 256 rows, the GPU): the batch at
+    cursor ``n_batches - 1`` holds that many rows, ``order[cursor*B : cursor*B + last_rows]``;
+    loss and gradient are their mean and the stats row counts them (None or ``B``: every batch
+    is full).
+
+    ``B`` up to 256 runs one workgroup (csrc/mlp_kernels.hip).  ``256 < B <= WIDE_MAX_B`` runs
+    the wide step (csrc/mlp_step_wide.hip): one workgroup per 64 rows, then the gradient tiles
+    split over the batch, then the slice sum with the epilogue -- three launches, every sum in
+    a fixed order, so two runs (eager or graph replay) agree bitwise.  ``workspace``:
+    ``mlp_wide_buffers(L1, L2, B, device)`` (None: one is kept per shape and device; a caller
+    with several streams passes its own).  ``lr_mask`` (``2^k - 1``, above 256 rows and with
+    ``apply_adam``): ``lr_tensor`` is a ring and optimizer step ``t`` reads entry
+    ``(t - 1) & lr_mask``; the reference reads the same entry.  Anything above ``WIDE_MAX_B``
+    raises a ValueError before a launch.
     """
     if x_u8 is not None:
         x_scale, x_shift = check_input_affine(x_scale, x_shift)
+    if not 1 <= int(B) <= WIDE_MAX_B:
+        raise ValueError(f"mlp_train_step: batch size must be in [1, {WIDE_MAX_B}], got {B} (nothing was launched)")
     last_rows = check_last_rows(last_rows, B, "mlp_train_step")
-    if last_rows != int(B) and (x_u8 is None or use_native(params)):
-        raise ValueError("mlp_train_step: a short last batch (last_rows < B) exists in the u8-mode fp32 reference "
-                         "and in the mlp3 kernels (mlp3_launch) only")
+    lr_mask = int(lr_mask)
+    if lr_mask < 0 or lr_mask & (lr_mask + 1) or (lr_mask and (lr_tensor is None or lr_tensor.numel() < lr_mask + 1)):
+        raise ValueError(f"mlp_train_step: lr_mask must be 2^k - 1 with lr_tensor of lr_mask + 1 rates, got {lr_mask}")
+    wide = int(B) >= WIDE_MIN_B
+    if last_rows != int(B) and (x_u8 is None or (use_native(params) and not wide)):
+        raise ValueError("mlp_train_step: a short last batch (last_rows < B) exists in u8 mode only: in the fp32 "
+                         "reference, in the wide step (B > 256) and in the mlp3 kernels (mlp3_launch)")
     if use_native(params):
-        require().mlp_train_step(
-            x_u8, x_f32, labels, order, counters, int(n_batches), int(B), int(L1), int(L2),
-            params, grads, exp_avg, exp_avg_sq, stats, bool(accumulate_grad), bool(apply_adam),
-            bool(advance_step), float(lr), float(betas[0]), float(betas[1]), float(eps),
-            float(weight_decay), lr_tensor, bool(adamw), stamps, float(x_scale), float(x_shift),
-        )
+        args = (x_u8, x_f32, labels, order, counters, int(n_batches), int(B), int(L1), int(L2),
+                params, grads, exp_avg, exp_avg_sq, stats, bool(accumulate_grad), bool(apply_adam),
+                bool(advance_step), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                float(weight_decay), lr_tensor, bool(adamw), stamps, float(x_scale), float(x_shift))
+        if not wide:
+            if lr_mask:
+                raise ValueError("mlp_train_step: lr_mask belongs to the wide step (B > 256)")
+            require().mlp_train_step(*args)
+            return
+        ws = workspace if workspace is not None else _wide_workspace(L1, L2, B, params.device)
+        require().mlp_train_step(*args, last_rows, lr_mask, ws["park"], ws["part"], ws["hdr"])
         return
     # ---- fp32 reference ----
     cursor = int(counters[1].item()) if (counters is not None and x_u8 is not None) else 0
@@ -229,8 +254,10 @@ def mlp_train_step(
             from .optim import fused_adam_
 
             gbuf = g.clone()
+            i_lr = (t - 1) & lr_mask
             fused_adam_(params, gbuf, exp_avg, exp_avg_sq, lr=lr, betas=betas, eps=eps,
-                        weight_decay=weight_decay, adamw=adamw, step=t, lr_tensor=lr_tensor)
+                        weight_decay=weight_decay, adamw=adamw, step=t,
+                        lr_tensor=lr_tensor[i_lr:i_lr + 1] if lr_mask else lr_tensor)
         else:
             grads.copy_(g)
         if counters is not None:
@@ -244,6 +271,53 @@ def mlp_train_step(
             correct = (logp.argmax(dim=1) == y).sum().float()
             stats.view(-1, 4)[slot] = torch.stack(
                 [loss.detach(), correct, torch.tensor(float(rows)), torch.tensor(float(t))])
+
+
+WIDE_SLAB = 64            # rows per workgroup of the wide step's first launch
+WIDE_WAVE_SLOTS = 1024    # gradient tiles x batch slices aims at 256 CUs x 4 waves
+WIDE_MAX_SLICES = 16
+
+
+def mlp_wide_layout(L1: int, L2: int, B: int) -> Dict[str, int]:
+    """Workspace of the wide step as csrc/mlp_step_wide.hip lays it out (``_C.mlp_wide_layout``;
+    the binding checks the sizes against its own).  ``park`` (bf16) holds what the parameter
+    launch contracts over the batch, transposed -- ``[feature][Bp]`` each, at element offsets
+    ``xt`` (784 rows), ``h1t`` (L1), ``h2t`` (L2), ``dh2t`` (L2), ``dzt`` (16), ``dh1t`` (L1);
+    ``part`` (fp32) holds ``slices`` partial gradients of ``np_pad`` floats, then 4 floats per
+    slab (sum NLL, #correct, #rows, -)."""
+    L1, L2, B = int(L1), int(L2), int(B)
+    nslab = (B + WIDE_SLAB - 1) // WIDE_SLAB
+    Bp = nslab * WIDE_SLAB
+    t1, t2 = L1 // 16, L2 // 16
+    ntasks = W1_TILES * t1 + t2 * t1 + t2 + t1 + t2 + 1
+    slices = max(1, min((WIDE_WAVE_SLOTS + ntasks - 1) // ntasks, WIDE_MAX_SLICES, Bp // 32))
+    np_pad = (mlp_param_count(L1, L2) + 3) // 4 * 4
+    off, rows = {}, 0
+    for name, n in (("xt", IN_FEATURES), ("h1t", L1), ("h2t", L2), ("dh2t", L2), ("dzt", 16), ("dh1t", L1)):
+        off[name] = rows * Bp
+        rows += n
+    return {"nslab": nslab, "Bp": Bp, "slices": slices, "np_pad": np_pad, "park_elems": rows * Bp,
+            "part_elems": slices * np_pad + nslab * 4, **off}
+
+
+def mlp_wide_buffers(L1: int, L2: int, B: int, device) -> Dict[str, torch.Tensor]:
+    """Device workspace of the wide step (``mlp_train_step(..., workspace=...)``): the parked
+    operands, the slice partials with the slab rows, and the 4-word header that hands the
+    step's (t, cursor, rows) from the first launch to the last."""
+    lay = mlp_wide_layout(L1, L2, B)
+    return {"park": torch.zeros(lay["park_elems"], dtype=torch.bfloat16, device=device),
+            "part": torch.zeros(lay["part_elems"], dtype=torch.float32, device=device),
+            "hdr": torch.zeros(4, dtype=torch.int64, device=device)}
+
+
+_wide_cache: Dict[tuple, Dict[str, torch.Tensor]] = {}
+
+
+def _wide_workspace(L1, L2, B, device) -> Dict[str, torch.Tensor]:
+    key = (int(L1), int(L2), int(B), str(device))
+    if key not in _wide_cache:
+        _wide_cache[key] = mlp_wide_buffers(L1, L2, B, device)
+    return _wide_cache[key]
 
 
 def mlp_shadow_layout(L1: int, L2: int) -> Dict[str, int]:

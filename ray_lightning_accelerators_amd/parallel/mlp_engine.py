@@ -17,6 +17,13 @@ re-designed for MI355X instead of translating PL's DDP loop:
   every block replays the serial head chain on its own CU, then does its tail
   share), else TWO (head + 49-workgroup tail; Adam fused into both, the next
   step's layer 1 computed by the tail);
+  batch sizes 257..4096 (``ops.fused_mlp.WIDE_MAX_B``): the wide step of
+  csrc/mlp_step_wide.hip -- 64-row slabs on MFMA with fp32 layer-1 accumulation (no 12.20
+  clamp: ``health()`` reports zeros), gradient tiles split over the batch, slices summed in a
+  fixed order -- as one fused ``mlp_train_step`` per step with Adam / AdamW; world size > 1
+  adds the allreduce and the arena Adam.  ``clip_norm``, ``accumulate`` > 1, SGD and
+  ``dp_context`` stop at 256 rows (ValueError); ``capture`` / ``run``, the stats ring,
+  ``set_step``, ``begin_epoch(last_rows=...)`` and the LR ring work as below 256;
   world size > 1: with a ``dp_context`` the same launches, each block exchanging
   its gradient values with the peers over xGMI inside its Adam epilogue (kinds
   Step1DP / StepDP); otherwise head -> tail(grad) -> allreduce(SUM) ->
@@ -207,8 +214,18 @@ class FusedMLPEngine:
                              "(dp_context) cannot clip -- pass allreduce= and no dp_context")
         if not fused_mlp.mlp_supported(layer_1, layer_2):
             raise ValueError(f"no fused kernel for layer sizes {layer_1}/{layer_2}")
-        if not 1 <= batch_size <= 256:
-            raise ValueError("fused MLP engine supports batch sizes 1..256")
+        if not 1 <= batch_size <= fused_mlp.WIDE_MAX_B:
+            raise ValueError(f"fused MLP engine supports batch sizes 1..{fused_mlp.WIDE_MAX_B}")
+        # above 256 rows: the wide step (csrc/mlp_step_wide.hip), Adam / AdamW only
+        self.wide = int(batch_size) >= fused_mlp.WIDE_MIN_B
+        if self.wide:
+            for bad, what in ((dp_context is not None, "dp_context (the in-kernel exchange)"),
+                              (clip_norm is not None, "clip_norm"), (accumulate > 1, "accumulate > 1"),
+                              (optimizer == "sgd", "optimizer='sgd'"),
+                              (lr_ring and int(world_size) > 1, "lr_ring at world size > 1")):
+                if bad:
+                    raise ValueError(f"fused MLP engine: {what} is served up to batch size 256 only (got "
+                                     f"{batch_size}); above it the engine runs Adam / AdamW on the wide step")
         self.L1, self.L2, self.B = int(layer_1), int(layer_2), int(batch_size)
         self.lr, self.betas, self.eps, self.wd = float(lr), tuple(betas), float(eps), float(weight_decay)
         self.optimizer = optimizer
@@ -270,7 +287,10 @@ class FusedMLPEngine:
         self._clip_since = 0  # global_step when clip_out was last zeroed
         lay = fused_mlp.mlp_shadow_layout(self.L1, self.L2)
         self.shadow = torch.zeros(lay["total"], dtype=torch.bfloat16, device=self.device)
-        bufs = fused_mlp.mlp3_buffers(self.L1, self.L2, self.B, self.device)
+        # (the wide step keeps none of the pipelined step's rings: only counters / hand are used)
+        bufs = fused_mlp.mlp3_buffers(self.L1, self.L2, 32 if self.wide else self.B, self.device)
+        self.wide_ws = (fused_mlp.mlp_wide_buffers(self.L1, self.L2, self.B, self.device)
+                        if self.wide and self.native else None)
         # counters: [0] optimizer step, [1] next batch cursor, [2] last consumed cursor,
         # [3] H1pre/X ring slot, [4] epoch buffer of `order` that [1] indexes
         self.counters = bufs["counters"]
@@ -619,7 +639,8 @@ class FusedMLPEngine:
             raise ValueError("dataset shard smaller than one batch")
         self.order = torch.empty(2, self.n_batches * self.B, dtype=torch.int64, device=self.device)
         self._fill_order(0)
-        self._fill_order(1)
+        if not self._wide_native:
+            self._fill_order(1)
         self.counters[1:5].zero_()
         self._publish_counters()
         self.epoch = 0
@@ -628,11 +649,17 @@ class FusedMLPEngine:
         self._primed = False
 
     def _fill_order(self, epoch: int) -> None:
-        """Write ``epoch``'s shard order into buffer ``epoch % 2`` (stream-ordered)."""
+        """Write ``epoch``'s shard order into buffer ``epoch % 2`` (stream-ordered).  The wide
+        step has no device-side buffer switch: it always reads buffer 0, which the host refills
+        behind each epoch's last step."""
         idx = shard_indices(self.n_data, self.world_size, self.rank, epoch, self.seed, self.shuffle)
         idx = idx[: self.n_batches * self.B]
         assert int(idx.max()) < self.n_data and int(idx.min()) >= 0  # the kernels trust indices
-        self.order[epoch % 2].copy_(idx.to(self.device), non_blocking=True)
+        self.order[0 if self._wide_native else epoch % 2].copy_(idx.to(self.device), non_blocking=True)
+
+    @property
+    def _wide_native(self) -> bool:
+        return self.wide and self.native
 
     # ------------------------------------------------------------ broadcast
     def broadcast_from(self, src: int = 0) -> None:
@@ -768,6 +795,9 @@ class FusedMLPEngine:
 
     def prime(self) -> None:
         """Layer-1 pre-activations of the pending batch from the current weights."""
+        if self._wide_native:  # self-contained steps: no pending batch, no shadow
+            self._primed = True
+            return
         if self._shadow_stale:
             self._shadow_stale = False
             fused_mlp.mlp_refresh_shadow(self.params, self.shadow, self.L1, self.L2)
@@ -821,6 +851,8 @@ class FusedMLPEngine:
             return
         if not self.native:
             self._reference_step()
+        elif self.wide:
+            self._wide_step()
         else:
             kw = self._kw3()
             if self.clip_norm is not None:
@@ -853,6 +885,26 @@ class FusedMLPEngine:
                     self.allreduce(self.comm_buffer)
                 fused_mlp.mlp3_launch(fused_mlp.MLP3_TAIL_ADAM, grad_scale=1.0 / self.world_size,
                                       **self._sgd_kw(), **kw)
+
+    def _wide_step(self) -> None:
+        """One batch above 256 rows: world size 1 is one fused ``mlp_train_step`` (three
+        launches, Adam in the last); otherwise gradients -> allreduce -> ``mlp_adam_`` with the
+        1 / world average folded into ``grad_scale``.  u8 mode on the engine's own order /
+        counters, so a captured graph replays successive batches."""
+        fused = self.world_size == 1
+        fused_mlp.mlp_train_step(
+            self.params, self.grads, L1=self.L1, L2=self.L2, B=self.B, labels=self.labels, x_u8=self.x_u8,
+            order=self.order[0], counters=self.counters[:2], n_batches=self.n_batches, exp_avg=self.exp_avg,
+            exp_avg_sq=self.exp_avg_sq, stats=self.stats, apply_adam=fused, lr=self.lr, betas=self.betas,
+            eps=self.eps, weight_decay=self.wd, lr_tensor=self.lr_tensor, adamw=self.adamw, x_scale=self.x_scale,
+            x_shift=self.x_shift, last_rows=self.last_rows, lr_mask=self.lr_mask, workspace=self.wide_ws)
+        if not fused:
+            if self.allreduce is not None:
+                self.allreduce(self.comm_buffer)
+            fused_mlp.mlp_adam_(self.params, self.grads, self.exp_avg, self.exp_avg_sq, self.shadow, L1=self.L1,
+                                L2=self.L2, lr=self.lr, step=self.counters[0:1], betas=self.betas, eps=self.eps,
+                                weight_decay=self.wd, grad_scale=1.0 / self.world_size, adamw=self.adamw,
+                                lr_tensor=self.lr_tensor)
 
     def _reference_step(self, micro: int = 0, closing: bool = True) -> None:
         """fp32 PyTorch step with the device kernels' batch / counter semantics
@@ -928,8 +980,9 @@ class FusedMLPEngine:
             self.step_in_epoch = 0
             if self._host_epochs:
                 return  # the host calls begin_epoch()
-            # buffer (epoch + 1) % 2 was last read by the step just enqueued
-            self._fill_order(self.epoch + 1)
+            # buffer (epoch + 1) % 2 was last read by the step just enqueued (the wide step: its
+            # one buffer gets the epoch that starts now)
+            self._fill_order(self.epoch if self._wide_native else self.epoch + 1)
 
     def steps_to_epoch_end(self) -> int:
         return self.n_batches - self.step_in_epoch
