@@ -1065,7 +1065,8 @@ void bn_bwd_apply(Tensor x, optional<Tensor> y, Tensor dy, Tensor coef, bool rel
 // ---- NHWC bf16 convolutions -----------------------------------------------------------
 // Every Python-visible function of a kernel family -- launch, *_supported / *_ok and
 // *_plan -- builds its geometry with the family's one builder (rla::conv3x3_geom,
-// rla::conv3x3s2_geom, rla::conv3x3s2_dgrad_geom, rla::stem_geom, wgrad_geom below) and its operands with
+// rla::conv3x3s2_geom, rla::conv3x3s2_dgrad_geom, rla::conv1x1s2_geom, rla::stem_geom, wgrad_geom below) and
+// its operands with
 // bf16_operand / stats4 / ptr_or_null, so the three cannot disagree.
 
 // conv_wgrad's geometry from the binding's arguments, range-checked before the int casts
@@ -1249,6 +1250,54 @@ std::vector<int64_t> conv3x3s2_plan(int64_t N, int64_t H, int64_t W, int64_t Cin
   TORCH_CHECK(rla::conv3x3s2_ok(g), "conv3x3s2_plan: unsupported shape");
   return {rla::conv3x3s2_tm(), g.wpb, g.vrows, rla::conv3x3s2_pieces_per_thread(g), rla::conv3x3s2_nx(), 0,
           g.OH, g.OW};
+}
+
+// 1x1 / stride 2 / pad 0 NHWC bf16 convolution forward (csrc/conv1x1s2.hip): x [N, H, W, Cin]
+// contiguous (the NHWC view of a channels_last tensor) and w [Cout, Cin]; returns y as
+// contiguous [N, OH, OW, Cout].  stats: also the next BatchNorm's partial sums of bf16(y)
+// -> {y, part [row tiles, 2, Cout]}.  Every operand is checked before the launch.
+std::vector<Tensor> conv1x1s2_impl(Tensor x, Tensor w, bool stats) {
+  TORCH_CHECK(x.dim() == 4, "conv1x1s2: x must be [N, H, W, Cin] (NHWC), got ", x.dim(), " dimensions");
+  TORCH_CHECK(w.dim() == 2, "conv1x1s2: w must be [Cout, Cin], got ", w.dim(), " dimensions");
+  const int64_t N = x.size(0), H = x.size(1), W = x.size(2), Cin = x.size(3), Cout = w.size(0);
+  TORCH_CHECK(w.size(1) == Cin, "conv1x1s2: w has ", w.size(1), " input channels, x has ", Cin);
+  const uint16_t* xp = bf16_operand(x, "conv1x1s2: x", N * H * W * Cin, x);
+  const uint16_t* wp = bf16_operand(w, "conv1x1s2: w", Cout * Cin, x);
+  const rla::Conv1x1S2Geom g = rla::conv1x1s2_geom(N, H, W, Cin, Cout);
+  TORCH_CHECK(rla::conv1x1s2_ok(g), "conv1x1s2: unsupported shape [", N, ", ", H, ", ", W, ", ", Cin, "] -> ", Cout,
+              " (Cin % 64, Cin >= 64, Cout % 128, N H W < 2^31)");
+  const at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor y = at::empty({N, g.OH, g.OW, Cout}, x.options());
+  Tensor part;
+  if (stats) part = at::empty({g.rows, 2, Cout}, x.options().dtype(at::kFloat));
+  TORCH_CHECK(rla::launch_conv1x1s2(xp, wp, reinterpret_cast<uint16_t*>(y.data_ptr()), g, cur_stream(x),
+                                    stats ? part.data_ptr<float>() : nullptr),
+              "conv1x1s2: launch refused");
+  if (stats) return {y, part};
+  return {y};
+}
+
+Tensor conv1x1s2(Tensor x, Tensor w) { return conv1x1s2_impl(x, w, false)[0]; }
+
+std::vector<Tensor> conv1x1s2_stats(Tensor x, Tensor w) { return conv1x1s2_impl(x, w, true); }
+
+// the layer's geometry as conv2d names it; anything but 1x1 / stride (2, 2) / pad 0 is refused
+bool conv1x1s2_supported(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t kh, int64_t kw,
+                         int64_t sh, int64_t sw, int64_t ph, int64_t pw) {
+  return kh == 1 && kw == 1 && sh == 2 && sw == 2 && ph == 0 && pw == 0 &&
+         rla::conv1x1s2_ok(rla::conv1x1s2_geom(N, H, W, Cin, Cout));
+}
+
+// Read-only plan query (tests, docs): what a conv1x1s2 / conv1x1s2_stats launch runs.  Workgroup
+// (row tile i, column j) owns output pixels [128 i, 128 i + 128) x channels [128 j, 128 j + 128)
+// and, with stats, writes part[i][:][128 j .. +128].  Returns (tile_m, tile_n, rows, cols, grid,
+// stage_k, stages, OH, OW); stats changes the epilogue only
+std::vector<int64_t> conv1x1s2_plan(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout, bool stats) {
+  (void)stats;
+  const rla::Conv1x1S2Geom g = rla::conv1x1s2_geom(N, H, W, Cin, Cout);
+  TORCH_CHECK(rla::conv1x1s2_ok(g), "conv1x1s2_plan: unsupported shape");
+  return {rla::conv1x1s2_tile_m(), rla::conv1x1s2_tile_n(), g.rows, g.cols, g.grid, rla::conv1x1s2_stage_k(),
+          rla::conv1x1s2_stages(), g.OH, g.OW};
 }
 
 // Input gradient of the 3x3 / stride 2 / pad 1 convolution (csrc/conv3x3s2_dgrad.hip):
@@ -1507,6 +1556,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv3x3s2_supported", &conv3x3s2_supported, "shapes the 3x3 stride-2 MFMA convolution covers");
   m.def("conv3x3s2_plan", &conv3x3s2_plan,
         "the 3x3 stride-2 kernel's (tm, wpb, vrows, pieces_per_thread, nx, fixed, OH, OW)", py::arg("N"),
+        py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"), py::arg("stats") = false);
+  m.def("conv1x1s2", &conv1x1s2, "1x1 / stride 2 / pad 0 NHWC bf16 convolution on MFMA -> [N, OH, OW, Cout]",
+        py::arg("x"), py::arg("wb"));
+  m.def("conv1x1s2_stats", &conv1x1s2_stats,
+        "1x1 / stride 2 / pad 0 forward + BatchNorm partial sums of its bf16 output -> (y, part [rows, 2, Cout])",
+        py::arg("x"), py::arg("wb"));
+  m.def("conv1x1s2_ok", &conv1x1s2_supported, "layers the 1x1 stride-2 MFMA convolution covers", py::arg("N"),
+        py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"), py::arg("kh") = 1, py::arg("kw") = 1,
+        py::arg("sh") = 2, py::arg("sw") = 2, py::arg("ph") = 0, py::arg("pw") = 0);
+  m.def("conv1x1s2_plan", &conv1x1s2_plan,
+        "the 1x1 stride-2 kernel's (tile_m, tile_n, rows, cols, grid, stage_k, stages, OH, OW)", py::arg("N"),
         py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"), py::arg("stats") = false);
   m.def("conv3x3s2_dgrad", &conv3x3s2_dgrad,
         "3x3 / stride 2 / pad 1 input gradient on MFMA: dy [N, OH, OW, Cr], forward weight [Cr, 3, 3, Co] "

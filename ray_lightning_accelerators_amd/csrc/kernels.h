@@ -612,6 +612,29 @@ bool conv3x3s2_ok(const Conv3x3S2Geom& g);
 bool launch_conv3x3s2(const uint16_t* x, const uint16_t* w, uint16_t* y, const Conv3x3S2Geom& g,
                       hipStream_t stream, float* part = nullptr);
 
+// 1x1 / stride 2 / pad 0 NHWC bf16 convolution forward on MFMA (csrc/conv1x1s2.hip):
+// y [N, OH, OW, Cout] = x [N, 2 oh, 2 ow, :] . w^T, w [Cout][Cin], OH = (H - 1) / 2 + 1,
+// OW = (W - 1) / 2 + 1.  A workgroup owns 128 output pixels x 128 output channels.
+struct Conv1x1S2Geom {
+  int N, H, W, Cin, Cout, OH, OW;
+  int M;     // output pixels N OH OW
+  int rows;  // 128-pixel row tiles = partial rows
+  int cols;  // 128-channel column tiles
+  int grid;  // workgroups: rows padded to a multiple of 8 (XCD deal) x cols
+};
+// The geometry of every launch, predicate and plan query.  Arguments that are not positive
+// or leave 32-bit row indexing (N H W < 2^31) give the all-zero geometry, which conv1x1s2_ok
+// refuses; Cin % 64 == 0, Cin >= 64 and Cout % 128 == 0 are conv1x1s2_ok's.
+Conv1x1S2Geom conv1x1s2_geom(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout);
+bool conv1x1s2_ok(const Conv1x1S2Geom& g);
+int conv1x1s2_tile_m();   // output pixels per tile
+int conv1x1s2_tile_n();   // output channels per tile
+int conv1x1s2_stage_k();  // channels per K stage
+int conv1x1s2_stages();   // LDS ring depth
+// part (or null): BatchNorm partial sums of bf16(y), [g.rows][2][Cout] fp32
+bool launch_conv1x1s2(const uint16_t* x, const uint16_t* w, uint16_t* y, const Conv1x1S2Geom& g,
+                      hipStream_t stream, float* part = nullptr);
+
 // Input gradient of the 3x3 / stride 2 / pad 1 convolution on MFMA (csrc/conv3x3s2_dgrad.hip):
 // dx [N, H, W, Co] from dy [N, OH, OW, Cr] and the FORWARD weight w [Cr][3][3][Co] (Cr the
 // layer's output channels, Co its input channels, as conv3x3_dgrad_bn names them).  The work

@@ -21,7 +21,8 @@ So every (operation, shape) picks its backend once, timed on the device at first
 use (like cudnn.benchmark): each operation builds ONE table ``{name: callable}``,
 ``_pick`` names the winner and that table's callable runs.  ``RLA_CONV1X1`` and
 ``RLA_CONV_WGRAD`` pin a backend by its name in the table (``miopen|gemm|hip|...``),
-``RLA_CONV3X3S2_DGRAD`` that of the stride-2 3x3 input gradient (``_pick_dgrad_s2``).
+``RLA_CONV3X3S2_DGRAD`` that of the stride-2 3x3 input gradient (``_pick_dgrad_s2``),
+``RLA_CONV1X1S2`` that of the stride-2 1x1 forward (``_pick_fwd_1x1s2``).
 
 Around the convolutions themselves:
 
@@ -121,19 +122,20 @@ def choices() -> Dict[str, Dict[str, float]]:
     return {" ".join(map(str, k)): dict(_timings.get(k, {}), pick=c) for k, c in _choice.items()}
 
 
-def _run(op: str, key: Tuple[int, ...], cands: Dict[str, Callable]):
-    """The result of ``op``'s picked backend: the callable that ``_pick`` timed, run once more."""
-    return cands[_pick(op, key, cands)]()
+def _run(op: str, key: Tuple[int, ...], cands: Dict[str, Callable], pick=None):
+    """The result of ``op``'s picked backend: the callable that ``_pick`` (or the family's own
+    ``pick``) timed, run once more."""
+    return cands[(pick or _pick)(op, key, cands)]()
 
 
 def _run_stats(op: str, key: Tuple[int, ...], cands: Dict[str, Callable], fused: Tuple[str, ...],
-               bn_stats: "BNStats"):
+               bn_stats: "BNStats", pick=None):
     """``_run`` for a forward whose output a training BatchNorm reads: the candidates
     named in ``fused`` return (y, part) from a statistics epilogue and hand ``part`` to
     that BatchNorm; the others return y alone and BatchNorm then runs its own partial
     pass, so they are timed with that pass (and run without it)."""
     timed = {name: fn if name in fused else (lambda fn=fn: _bn_partial(fn())) for name, fn in cands.items()}
-    name = _pick(op, key, timed)
+    name = (pick or _pick)(op, key, timed)
     if name not in fused:
         return cands[name]()
     y, bn_stats.part = cands[name]()
@@ -397,6 +399,91 @@ def conv3x3s2_stats_hip(x: torch.Tensor, wb: torch.Tensor):
     cout = wb.size(0)
     y, part = require().conv3x3s2_stats(x.permute(0, 2, 3, 1), wb.permute(0, 2, 3, 1), n, h, w, cin, cout)
     return y.permute(0, 3, 1, 2), part
+
+
+def _s2_1x1_mode() -> str:
+    """``RLA_CONV1X1S2=auto|hip|miopen``: backend of the stride-2 1x1 forwards (ResNet's
+    downsample shortcuts).  auto: timed per shape, deterministic mode the in-tree kernel;
+    ``miopen``: the library alone, the kernel is not a candidate."""
+    m = os.environ.get("RLA_CONV1X1S2", "auto")
+    return m if m in ("hip", "miopen") else "auto"
+
+
+def conv1x1s2_ok(x: torch.Tensor, wb: torch.Tensor, stride, padding) -> bool:
+    """1x1 / stride 2 / pad 0 forwards the MFMA kernel covers (csrc/conv1x1s2.hip): bf16
+    channels_last operands on the GPU, 16-byte aligned, Cin % 64 == 0, Cout % 128 == 0.
+    ``RLA_CONV1X1S2=miopen`` turns the kernel off."""
+    if tuple(wb.shape[2:]) != (1, 1) or tuple(stride) != (2, 2) or tuple(padding) != (0, 0):
+        return False
+    if not x.is_cuda or _s2_1x1_mode() == "miopen":
+        return False
+    n, cin, h, w = x.shape
+    cout = wb.size(0)
+    return (x.dtype == torch.bfloat16 and wb.dtype == torch.bfloat16 and wb.size(1) == cin
+            and x.is_contiguous(memory_format=torch.channels_last) and wb.reshape(cout, cin).is_contiguous()
+            and x.data_ptr() % 16 == 0 and wb.data_ptr() % 16 == 0
+            and _conv1x1s2_shape_ok(n, h, w, cin, cout))
+
+
+@functools.lru_cache(maxsize=64)
+def _conv1x1s2_shape_ok(n: int, h: int, w: int, cin: int, cout: int) -> bool:
+    # cached: this family's geometry does not follow the planning CU count
+    from . import require
+
+    return bool(require().conv1x1s2_ok(n, h, w, cin, cout))
+
+
+def _conv1x1s2_ref(x: torch.Tensor, wb: torch.Tensor, stats: bool):
+    """The kernel's contract on CPU tensors: fp64 accumulation rounded once to bf16, and the
+    sums of the ROUNDED values and their squares over each 128-pixel row tile."""
+    n, cout = x.size(0), wb.size(0)
+    y = F.conv2d(x.double(), wb.reshape(cout, -1, 1, 1).double(), stride=2).to(torch.bfloat16)
+    y = y.contiguous(memory_format=torch.channels_last)
+    if not stats:
+        return y
+    rows = [t.float() for t in _nhwc2d(y).split(128)]
+    return y, torch.stack([torch.stack([t.sum(0), t.square().sum(0)]) for t in rows])
+
+
+def conv1x1s2_hip(x: torch.Tensor, wb: torch.Tensor) -> torch.Tensor:
+    """``conv2d(x, wb, stride=2)`` for a 1x1 layer on the MFMA kernel: ``x`` [N, Cin, H, W]
+    channels_last bf16, ``wb`` [Cout, Cin(, 1, 1)] bf16; returns
+    [N, Cout, (H - 1) // 2 + 1, (W - 1) // 2 + 1] channels_last.  Odd rows and columns of
+    ``x`` are not read.  CPU tensors take the reference body."""
+    if not x.is_cuda:
+        return _conv1x1s2_ref(x, wb, False)
+    from . import require
+
+    y = require().conv1x1s2(x.permute(0, 2, 3, 1), wb.reshape(wb.size(0), -1))
+    return y.permute(0, 3, 1, 2)
+
+
+def conv1x1s2_stats_hip(x: torch.Tensor, wb: torch.Tensor):
+    """:func:`conv1x1s2_hip` plus the per-channel partial sums of its bf16 output from the
+    epilogue (csrc/conv1x1s2.hip ST): returns (y channels_last, part [rows, 2, Cout])."""
+    if not x.is_cuda:
+        return _conv1x1s2_ref(x, wb, True)
+    from . import require
+
+    y, part = require().conv1x1s2_stats(x.permute(0, 2, 3, 1), wb.reshape(wb.size(0), -1))
+    return y.permute(0, 3, 1, 2), part
+
+
+def conv1x1s2_stats_enabled() -> bool:
+    """``RLA_CONV1X1S2_STATS=off`` keeps the downsample BatchNorm's statistics in BN's own pass."""
+    return os.environ.get("RLA_CONV1X1S2_STATS", "auto") != "off"
+
+
+def _pick_fwd_1x1s2(op: str, key: Tuple[int, ...], cands) -> str:
+    """The backend of a stride-2 1x1 forward (``fwd_1x1s2`` / ``fwd_1x1s2_st`` in
+    :func:`choices`): ``RLA_CONV1X1S2=hip`` pins the in-tree kernel (its statistics instance
+    where that is the candidate), deterministic mode takes ``hip`` untimed (fixed order), a
+    graph capture with no cached pick takes ``miopen``."""
+    if _s2_1x1_mode() == "hip":
+        return "hip_st" if "hip_st" in cands else "hip"
+    if torch.are_deterministic_algorithms_enabled():
+        return "hip"
+    return _timed_pick((op,) + key, cands)
 
 
 def conv3x3s2_dgrad_ok(dy: torch.Tensor, wb: torch.Tensor, h: int, w: int) -> bool:
@@ -753,7 +840,8 @@ class _ConvNHWCFn(torch.autograd.Function):
     """KxK (or strided) bf16 NHWC convolution: MIOpen or, for 3x3 / stride 1 / pad 1, the
     MFMA kernels for the forward and dgrad, for 3x3 / stride 2 / pad 1 the MFMA forward
     and the MFMA quad-tiled dgrad (``conv3x3s2_dgrad_hip``; ``dgrad_s2``, picked by
-    ``_pick_dgrad_s2``: the in-tree kernel untimed in deterministic mode); the weight
+    ``_pick_dgrad_s2``: the in-tree kernel untimed in deterministic mode), for 1x1 / stride 2
+    / pad 0 the gathered-row MFMA forward (``conv1x1s2_hip``, ``_pick_fwd_1x1s2``); the weight
     gradient from MIOpen or the MFMA kernel (``wgrad_hip``); each picked per shape on device
     time.  The weight gradient reaches the fp32 master weight in fp32."""
 
@@ -787,6 +875,20 @@ class _ConvNHWCFn(torch.autograd.Function):
                 # reproducible) and the BatchNorm makes its own pass
                 cands["hip"] = lambda: conv3x3s2_hip(x, wb)
                 y = _run("fwd_kxk", key, cands)
+        elif not ctx.c3 and conv1x1s2_ok(x, wb, stride, padding):
+            # 1x1 / stride 2 / pad 0 (ResNet's downsample shortcut): the gathered-row MFMA
+            # forward against the library (RLA_CONV1X1S2); the backward is the strided
+            # layer's as before
+            key = (x.size(0) * x.size(2) * x.size(3), x.size(1), wb.size(0), 1, 1, 2, 0)
+            if (bn_stats is not None and conv1x1s2_stats_enabled()
+                    and not torch.are_deterministic_algorithms_enabled()):
+                cands["hip_st"] = lambda: conv1x1s2_stats_hip(x, wb)
+                y = _run_stats("fwd_1x1s2_st", key, cands, ("hip_st",), bn_stats, _pick_fwd_1x1s2)
+            else:
+                # deterministic mode too: "hip" untimed (bitwise reproducible) and the
+                # BatchNorm makes its own pass
+                cands["hip"] = lambda: conv1x1s2_hip(x, wb)
+                y = _run("fwd_1x1s2", key, cands, _pick_fwd_1x1s2)
         elif not ctx.c3:
             y = cands["miopen"]()  # the only backend of any other strided or non-3x3 forward
         else:
@@ -971,7 +1073,8 @@ def conv_nhwc(x: torch.Tensor, conv: nn.Conv2d, wb: torch.Tensor, fork: Optional
               bn_stats: Optional[BNStats] = None) -> torch.Tensor:
     """``conv(x)`` with the bf16 weight ``wb`` (the arena shadow), the weight gradient
     going to ``conv.weight`` in fp32 (``fork``: see :class:`GradFork`; ``bn_stats``:
-    see :class:`BNStats`, filled only by the 3x3 MFMA forwards, stride 1 or 2)."""
+    see :class:`BNStats`, filled only by the 3x3 MFMA forwards, stride 1 or 2, and the
+    stride-2 1x1 MFMA forward)."""
     # before materialize(x), whose result no longer carries the tag
     fold = getattr(x, "_rla_fold", None) if getattr(conv, "fuse_bn_dgrad", False) else None
     pre = getattr(x, "_rla_pre", None)
