@@ -3,7 +3,10 @@ kernel ``mlp_eval`` (csrc/mlp_kernels.hip): the buffer-layout maps, the operand 
 a-priori rounding bounds and the exactness certificate that tests/test_mlp3_stages_fp64.py
 holds the kernels to, element by element and stage by stage.  tests/test_mlp_reference.py
 checks all of it on the CPU (against fp64 autograd, an fp32 / bf16 emulation of the kernels'
-arithmetic and mutants of that emulation) before anything runs on a GPU.
+arithmetic and mutants of that emulation) before anything runs on a GPU.  The last section
+holds the one-workgroup step ``mlp_train_kernel`` (csrc/mlp_kernels.hip) to the same stage
+references through a gate that silences rows (tests/test_mlp_step_1wg_fp64.py, checked on the
+CPU by tests/test_mlp_probe_reference.py).
 
 Every stage is judged ALONE: its reference is computed in float64 from the kernel's own
 output of the stage before (``xring`` -> ``h1pre`` -> H1 -> H2 -> dZ -> dH2 -> dH1 ->
@@ -525,3 +528,320 @@ def emulate_grads(obs):
     x, h1, h2, dh2, dh1 = (obs[k].to(f) for k in ("x", "h1", "h2", "dh2", "dh1"))
     g = [dh1.t() @ x, dh1.sum(0), dh2.t() @ h1, dh2.sum(0), dz.t() @ h2, dz.sum(0)]
     return torch.cat([t.reshape(-1) for t in g])
+
+
+# ------------------------------------------------------------------ the one-workgroup step (csrc/mlp_kernels.hip)
+# mlp_train_kernel exports nothing but the six gradients and a stats row, so its stages are observed
+# through a GATE: pixel 0, hidden unit 0 of each layer and one class c0 are reserved so that a row
+# with pixel 0 = 1 and label c0 is SILENT (dZ exactly zero, loss exactly 0, counted correct).  With
+# every row but one silent the gradients are that row's own rank-1 products, and exact quotients
+# give back its X, H1, H2, dZ, dH2 and dH1.  tests/test_mlp_probe_reference.py checks the method
+# on the CPU, tests/test_mlp_step_1wg_fp64.py runs it on the kernel.
+GATE, GAP_MIN = 8.0, 128.0   # fp32 expf is exactly 0 below about -104; 128 leaves the logit error room
+LDS_BYTES = 160 * 1024
+
+
+def lds_total_1wg(BC, L1, L2):
+    """A Python mirror of ``Cfg<BC, L1, L2>::total`` (bytes of LDS).  Nothing exported by the
+    kernel can confirm it: it labels cases and shows that the case lists reach both chunk sizes
+    and all three split counts, no more."""
+    TS = BC + 8
+    szR = max((L2 + L1) * TS * 2, BC * L1 * 4, BC * 16 * 4)
+    return (BC * 808 * 2 + BC * (L1 + 8) * 2 + L1 * TS * 2 + BC * (L2 + 8) * 2 + L2 * TS * 2 + (szR + 15) // 16 * 16
+            + BC * 40 * 2 + 16 * TS * 2 + BC * 4 + 64)
+
+
+def chunk_rows_1wg(L1, L2, B):
+    """Rows per chunk as ``dispatch_train`` picks them (``fits<64>()`` and B > 32); a mirror, see
+    ``lds_total_1wg``."""
+    return 64 if B > 32 and lds_total_1wg(64, L1, L2) + 256 <= LDS_BYTES else 32
+
+
+def nsplit_1wg(L1):
+    """Waves that share one layer-1 column tile (``NSPLIT``); a mirror, see ``lds_total_1wg``."""
+    return 8 // (L1 // 16)
+
+
+def gate_params(flat, L1, L2, c0):
+    """A copy of the arena with the gate planted: W1[0] = 8 e0, b1[0] = 0, W2[0] = 8 e0,
+    b2[0] = 0, W3[:, 0] = 8 at class c0 and 0 elsewhere."""
+    out = flat.clone()
+    W1, b1, W2, b2, W3, _ = fused_mlp.mlp_unpack(out, L1, L2).values()
+    W1[0], b1[0], W2[0], b2[0], W3[:, 0] = 0.0, 0.0, 0.0, 0.0, 0.0
+    W1[0, 0], W2[0, 0], W3[c0, 0] = GATE, GATE, GATE
+    return out
+
+
+def gate_rows(x, y, c0, on, off):
+    """(x2 [2 B, 784], y2 [2 B]): rows 0..B-1 are the batch with the gate off and its own labels,
+    rows B..2B-1 the same rows silenced (pixel 0 = ``on``, label c0)."""
+    x_off, x_on = x.clone(), x.clone()
+    x_off[:, 0], x_on[:, 0] = off, on
+    return torch.cat([x_off, x_on]), torch.cat([y, torch.full_like(y, c0)])
+
+
+def probe_order(B, r=None, loud=False):
+    """Rows of ``gate_rows``' pair that make the batch in which only row r speaks (None: nobody).
+    ``loud``: row r keeps the gate on and takes its own label (the caller picks one != c0)."""
+    idx = torch.arange(B, 2 * B)
+    if r is not None and not loud:
+        idx[r] = r
+    return idx
+
+
+def step_weights(params, L1, L2):
+    """What mlp_train_kernel reads: bf16(fp32 master) weights, fp32 biases, as float64."""
+    W1, b1, W2, b2, W3, b3 = fused_mlp.mlp_unpack(params.detach().cpu().float(), L1, L2).values()
+    W1, W2, W3 = _bf(W1), _bf(W2), _bf(W3)
+    w3t = torch.zeros(L2, 16, dtype=torch.float64)
+    w3t[:, :NC] = W3.t()
+    return Weights(W1, b1.double(), W2, b2.double(), W3, b3.double(), W2.t().contiguous(), w3t)
+
+
+def forward_fp64(X, wt):
+    """(H1, H2, Z) in float64 with the kernel's two bf16 roundings."""
+    H1 = _bf(torch.relu(X @ wt.W1.t() + wt.b1))
+    H2 = _bf(torch.relu(H1 @ wt.W2.t() + wt.b2))
+    return H1, H2, H2 @ wt.W3.t() + wt.b3
+
+
+def gate_gap(X_on, wt, c0):
+    """min over the gate-on rows of z[c0] - max(the other logits), float64."""
+    Z = forward_fp64(X_on, wt)[2]
+    others = Z.clone()
+    others[:, c0] = -float("inf")
+    return float((Z[:, c0] - others.max(1).values).min())
+
+
+def recover_row(grads, L1, L2):
+    """(row, [(check, Cmp)]) from the flat gradient of a step in which one row spoke.  db3 / db2 /
+    db1 are that row's dZ / dH2 / dH1 (one nonzero term plus zeros), each dW is a rank-1 product of
+    two bf16 numbers, exact in fp32, so the float64 quotient by the largest factor IS the other
+    factor: H2 = dW3[j*] / db3[j*], H1 = dW2[n*] / db2[n*], X = dW1[m*] / db1[m*].  ``rank1_*``: the
+    whole dW equals the outer product (tile placement; rows without a factor exactly zero).  A
+    factor that is all zero (or not finite) is a refusal, a failed ``speaks``, never a skip."""
+    g = fused_mlp.mlp_unpack(grads.detach().cpu().double(), L1, L2)
+    dW1, db1, dW2, db2, dW3, db3 = g.values()
+    row, out = {}, []
+    for name, dW, db, fac in (("W3", dW3, db3, "h2"), ("W2", dW2, db2, "h1"), ("W1", dW1, db1, "x")):
+        if not bool(torch.isfinite(dW).all() and torch.isfinite(db).all() and (db != 0).any()):
+            return None, [("speaks", Cmp(False, float("inf"), f"db{name[1]} is all zero or not finite: no factor"))]
+        i = int(db.abs().argmax())
+        row[fac] = dW[i] / db[i]
+        out.append(("rank1_" + name, cmp_equal(dW, torch.outer(db, row[fac]))))
+    dz = torch.zeros(16, dtype=torch.float64)
+    dz[:NC] = db3
+    row.update(dz=dz, dh2=db2.clone(), dh1=db1.clone())
+    allv = torch.cat([v for v in row.values()])
+    return row, [("speaks", Cmp(True, 0.0, "equal")), ("bf16", cmp_equal(allv, _bf(allv)))] + out
+
+
+def stack_rows(rows):
+    return {k: torch.stack([r[k] for r in rows]) for k in rows[0]}
+
+
+def row_nll(Z, ez, y):
+    """``ref_stats`` row by row: (nll, bound, certainly right, ambiguous), each [n]."""
+    m = Z.max(1).values
+    lse = m + torch.log(torch.exp(Z - m.view(-1, 1)).sum(1))
+    zy = Z.gather(1, y.view(-1, 1)).squeeze(1)
+    emax = ez.max(1).values
+    top = Z.topk(2, dim=1).values
+    amb = (top[:, 0] - top[:, 1]) < 2.0 * emax
+    pred = torch.where(Z == m.view(-1, 1), torch.arange(NC).expand_as(Z), torch.full_like(Z, NC, dtype=torch.long)
+                       ).min(1).values
+    return lse - zy, 2.0 * emax + SOFT * (m.abs() + lse.abs() + zy.abs()), (pred == y) & ~amb, amb
+
+
+def _certified(a, w, b, got, ref):
+    c = exact_certificate(a, w, b)
+    return cmp_equal(got, _bf(ref)) if c.ok else Cmp(False, float("inf"), f"not certified: {c}")
+
+
+def probe_checks(obs, wt, x_want, y, B, exact=False, stats=None, steps=None):
+    """[(stage, Cmp)] of the recovered rows ``obs`` (``stack_rows``: x, h1, h2, dz, dh2, dh1, one
+    row per probe run), each stage from the kernel's own stage before.  ``x_want``: bf16 of what
+    was fed; ``y``: the rows' labels; ``B``: the batch (dZ carries 1 / B).  Layer 1 is a plain fp32
+    sum here (K = 784, in any split), so H1 takes ``ref_h2``'s form; ``exact``: H1 / H2 equal under
+    the certificate.  ``stats`` [n, 4], ``steps`` [n]: each run's stats row -- the speaking row's
+    NLL / B (the B - 1 silent rows add exactly 0; then the rounding of 1 / B and one product,
+    2 U24), B - 1 silent rows counted correct, B rows, the step."""
+    out = [("X", cmp_equal(obs["x"], x_want))]
+    for name, a, w, b, got in (("H1", obs["x"], wt.W1, wt.b1, obs["h1"]), ("H2", obs["h1"], wt.W2, wt.b2, obs["h2"])):
+        ref, bound = ref_h2(a, w, b)
+        out.append((name, _certified(a, w, b, got, ref) if exact else cmp_bound(got, ref, bound)))
+    Z, ez = ref_logits(obs["h2"], wt.W3, wt.b3)
+    if exact and exact_certificate(obs["h2"], wt.W3, wt.b3).ok:
+        ez = torch.zeros_like(ez)
+    out.append(("dZ", cmp_bound(obs["dz"], *ref_dz(Z, ez, y, B))))
+    out.append(("dH2", cmp_bound(obs["dh2"], *ref_dh2(obs["dz"], wt.W3T, obs["h2"]))))
+    out.append(("dH1", cmp_bound(obs["dh1"], *ref_dh1(obs["dh2"], wt.W2T, obs["h1"]))))
+    if stats is not None:
+        nll, nb, sure, amb = row_nll(Z, ez, y)
+        got = stats.double()
+        out.append(("loss", cmp_bound(got[:, 0], nll / B, (nb + 2.0 * U24 * nll) / B)))
+        lo = B - 1 + sure.double()
+        ok = bool(((got[:, 1] >= lo) & (got[:, 1] <= lo + amb.double()) & (got[:, 2] == B)
+                   & (got[:, 3] == steps.double())).all())
+        out.append(("count", Cmp(ok, 0.0 if ok else float("inf"), "equal" if ok else "a stats row's (correct, rows, "
+                                                                                      "step) is off")))
+    return out
+
+
+def superposition_checks(g, gsum, gabs, Bp, L1, L2):
+    """[(name, Cmp)]: the full batch's flat gradient within 2 Bp U24 sum_r |G_r| of the float64
+    sum of the probe runs' per-row gradients (``grad_checks``' form, the terms the kernel's own)."""
+    got, ref, amp = (fused_mlp.mlp_unpack(t.detach().cpu().double(), L1, L2) for t in (g, gsum, gabs))
+    return [("d" + k, cmp_bound(got[n], ref[n], 2.0 * Bp * U24 * amp[n])) for k, n in zip(NAMES, got)]
+
+
+def exact_batch(X_on, y, wt, B, c0):
+    """The all-gate-on batch predicted in float64 with bf16 roundings at the kernel's rounding
+    points: ``obs`` (x, h1, h2, dz, dh2, dh1 over the B rows), and which stages the certificate
+    proves exact.  dZ needs no softmax: prob[c0] is exactly 1.0f (``gate_gap`` >= GAP_MIN, asserted
+    by the caller), so a row with label c0 is zero and any other holds bf16(+-float32(1 / B))."""
+    H1, H2, _ = forward_fp64(X_on, wt)
+    invB = float(_bf(torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(B), dtype=torch.float32)))
+    dz = torch.zeros(B, 16, dtype=torch.float64)
+    loud = y != c0
+    dz[loud, c0] = invB
+    dz[loud, y[loud]] = -invB
+    dh2 = _bf(dz @ wt.W3T.t()) * (H2 > 0)
+    dh1 = _bf(dh2 @ wt.W2T.t()) * (H1 > 0)
+    obs = {"x": X_on, "h1": H1, "h2": H2, "dz": dz, "dh2": dh2, "dh1": dh1}
+    cert = {"H1": exact_certificate(X_on, wt.W1, wt.b1).ok, "H2": exact_certificate(H1, wt.W2, wt.b2).ok,
+            "dH2": exact_certificate(dz, wt.W3T).ok, "dH1": exact_certificate(dh2, wt.W2T).ok}
+    ones = torch.ones(1, B, dtype=torch.float64)
+    for k, d, a in (("W1", dh1, X_on), ("W2", dh2, H1), ("W3", dz[:, :NC], H2)):
+        cert["d" + k] = exact_certificate(d.t(), a.t()).ok
+        cert["db" + k[1]] = exact_certificate(d.t(), ones).ok
+    return obs, cert
+
+
+def exact_batch_checks(g, obs, cert, L1, L2, Bp):
+    """[(name, Cmp)] of the flat gradient against ``exact_batch``: equal where the certificate
+    covers the batch sum (any order, the chunk adds included), ``grad_checks``' bound otherwise.
+    Sound only with every activation stage certified: the caller asserts that."""
+    refs = ref_grads(obs)
+    got = fused_mlp.mlp_unpack(g.detach().cpu().double(), L1, L2)
+    return [("d" + k, cmp_equal(t, refs[k][0]) if cert["d" + k]
+             else cmp_bound(t, refs[k][0], 2.0 * Bp * U24 * refs[k][1])) for k, t in zip(NAMES, got.values())]
+
+
+def adam_checks(before, after, g_applied, cfg, t, lr=None):
+    """[("adam_m", ..), ("adam", ..)]: with beta1 = 0 and a zeroed exp_avg, m' must BE the gradient
+    the step applied (``g_applied``: the same step without Adam; None: not compared), and p, v
+    follow tests/optim_reference.py's ``ref_adam`` from the state before and that m'."""
+    import optim_reference as OR
+
+    out = []
+    if g_applied is not None:
+        out.append(("adam_m", cmp_equal(after["m"].cpu(), g_applied.cpu())))
+    ref = OR.ref_adam({"p": before["p"].cpu(), "g": after["m"].cpu(), "m": torch.zeros_like(before["p"]).cpu(),
+                       "v": before["v"].cpu()}, cfg, t=t, lr=lr)
+    c = OR.check_adam({k: after[k].cpu() for k in ("p", "m", "v")}, ref)
+    return out + [("adam", Cmp(c.ok, c.ratio, c.detail))]
+
+
+WRONG_1WG = {"a": "the second chunk overwrites the gradient", "b": "invB = 1 / rows of the chunk",
+             "c": "dH1 masked by H2's mask shifted one unit", "d": "dZ not zeroed for padded rows",
+             "e": "two 4-pixel groups of one dW1 tile swapped", "f": "Adam on every chunk",
+             "g": "db summed over the first chunk only"}
+
+
+def emulate_step_1wg(params, X, y, B, BC, L1, L2, grads=None, accumulate_grad=False, adam=None, step=1, wrong=None):
+    """mlp_train_kernel's arithmetic in torch fp32 / bf16: chunks of ``BC`` rows (the last one
+    padded with zero rows of label -1), invB = 1 / B, fp32 accumulation through ``grads`` from the
+    second chunk on, bias sums over the chunk, Adam on the last chunk only.  ``X`` [B, 784]: the
+    staged bf16 pixels; ``adam``: None or dict(m, v, lr, betas, eps, wd, adamw) -- ``step`` is t
+    after the update.  -> dict grads, p, m, v, stats [4], rows (every stage over the padded rows).
+    ``wrong``: a key of WRONG_1WG."""
+    f = torch.float32
+    P = params.detach().cpu().to(f).clone()
+    G = torch.zeros_like(P) if grads is None else grads.detach().cpu().to(f).clone()
+    M = V = None
+    if adam is not None:
+        M, V = adam["m"].cpu().to(f).clone(), adam["v"].cpu().to(f).clone()
+    nch = (B + BC - 1) // BC
+    Xp = torch.zeros(nch * BC, 784, dtype=f)
+    Xp[:B] = X.to(f)
+    yp = torch.full((nch * BC,), -1, dtype=torch.long)
+    yp[:B] = y
+    one = torch.tensor(1.0, dtype=f)
+    loss_sum, hits, count, rows = torch.tensor(0.0, dtype=f), 0, 0, []
+
+    def bf(t):
+        return t.to(torch.bfloat16).to(f)
+
+    for c in range(nch):
+        W1, b1, W2, b2, W3, b3 = fused_mlp.mlp_unpack(P, L1, L2).values()
+        x, yc = Xp[c * BC:(c + 1) * BC], yp[c * BC:(c + 1) * BC]
+        ok = (yc >= 0).view(-1, 1)
+        invB = one / torch.tensor(float(int(ok.sum()) if wrong == "b" else B), dtype=f)
+        h1 = bf(torch.relu(x @ bf(W1).t() + b1))
+        h2 = bf(torch.relu(h1 @ bf(W2).t() + b2))
+        z = h2 @ bf(W3).t() + b3
+        m = z.max(1, keepdim=True).values
+        p = torch.exp(z - m)
+        s = p.sum(1, keepdim=True)
+        hot = F.one_hot(yc.clamp_min(0), NC).to(f) * ok
+        d = bf((p * (one / s) - hot) * invB)
+        dz = d if wrong == "d" else torch.where(ok, d, torch.zeros_like(d))
+        zy = z.gather(1, yc.clamp_min(0).view(-1, 1)).squeeze(1)
+        nll = torch.where(ok.squeeze(1), (m + torch.log(s)).squeeze(1) - zy, torch.zeros(BC, dtype=f))
+        loss_sum = loss_sum + nll.sum()
+        hits += int(((z.argmax(1) == yc) & ok.squeeze(1)).sum())
+        count += int(ok.sum())
+        dh2 = torch.where(h2 > 0, bf(dz @ bf(W3)), torch.zeros_like(h2))
+        mask1 = (h2 > 0)[:, (torch.arange(L1) + 1) % L2] if wrong == "c" else h1 > 0
+        dh1 = torch.where(mask1, bf(dh2 @ bf(W2)), torch.zeros_like(h1))
+        dW1 = dh1.t() @ x
+        if wrong == "e":
+            dW1[16:32, 160:168] = torch.cat([dW1[16:32, 164:168], dW1[16:32, 160:164]], 1)
+        db = [dh1.sum(0), dh2.sum(0), dz.sum(0)]
+        if wrong == "g" and c > 0:
+            db = [torch.zeros_like(t) for t in db]
+        gc = torch.cat([t.reshape(-1) for t in (dW1, db[0], dh2.t() @ h1, db[1], dz.t() @ h2, db[2])])
+        if accumulate_grad or (c > 0 and not (wrong == "a" and c == 1)):
+            gc = gc + G
+        if adam is not None and (c == nch - 1 or wrong == "f"):
+            lr, b1_, b2_, eps, wd = (torch.tensor(float(v), dtype=f)
+                                     for v in (adam["lr"], *adam["betas"], adam["eps"], adam["wd"]))
+            ss = torch.tensor(float(lr) / (1.0 - float(b1_) ** step), dtype=f)
+            bs = torch.tensor((1.0 - float(b2_) ** step) ** 0.5, dtype=f)
+            g2 = gc
+            if float(wd) != 0.0:
+                if adam.get("adamw"):
+                    P = P * (one - lr * wd)
+                else:
+                    g2 = gc + wd * P
+            M = M + (one - b1_) * (g2 - M)
+            V = V * b2_ + (one - b2_) * (g2 * g2)
+            P = P + (-ss) * (M / (torch.sqrt(V) / bs + eps))
+        else:
+            G = gc
+        rows.append({"x": x, "h1": h1, "h2": h2, "dz": F.pad(dz, (0, 6)), "dh2": dh2, "dh1": dh1})
+    invB = one / torch.tensor(float(B), dtype=f)
+    stats = torch.tensor([float(loss_sum * invB), float(hits), float(count), float(step)], dtype=f)
+    return {"grads": G, "p": P, "m": M, "v": V, "stats": stats,
+            "rows": {k: torch.cat([r[k] for r in rows]).double() for k in rows[0]}}
+
+
+def probe_sweep(step, B, L1, L2):
+    """Every row of the batch speaks in turn.  ``step(order, t)`` runs one step over the rows
+    ``order`` of ``gate_rows``' pair (t = 1..B) and returns (flat gradient, stats row).  ->
+    (rows or None, stats [B, 4], gsum, gabs, failures): the recovered rows stacked, each run's stats
+    row, the running float64 sum of the per-row gradients and of their absolute values (kept where
+    the gradient lives), and the failed ``recover_row`` checks as (row, check, detail)."""
+    rows, stats, bad, gsum, gabs = [], [], [], None, None
+    for r in range(B):
+        g, st = step(probe_order(B, r), r + 1)
+        g64 = g.detach().double()
+        gsum = g64.clone() if gsum is None else gsum + g64
+        gabs = g64.abs() if gabs is None else gabs + g64.abs()
+        row, res = recover_row(g, L1, L2)
+        bad += [(r, s, c.detail) for s, c in res if not c.ok]
+        if row is not None:
+            rows.append(row)
+        stats.append(st.detach().cpu().clone())
+    return (stack_rows(rows) if len(rows) == B else None), torch.stack(stats), gsum.cpu(), gabs.cpu(), bad
