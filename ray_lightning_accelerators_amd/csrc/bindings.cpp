@@ -310,17 +310,21 @@ void mlp_train_step(optional<Tensor> x_u8, optional<Tensor> x_f32, Tensor labels
                     double eps, double weight_decay, optional<Tensor> lr_t, bool adamw,
                     optional<Tensor> stamps, double x_scale, double x_shift, optional<int64_t> last_rows,
                     int64_t lr_mask, optional<Tensor> wide_park, optional<Tensor> wide_part,
-                    optional<Tensor> wide_hdr) {
-  TORCH_CHECK(rla::mlp_supported((int)L1, (int)L2), "no fused MLP kernel for layer sizes ", L1, "/", L2);
+                    optional<Tensor> wide_hdr, bool general) {
+  // widths outside the table, or `general` on a table pair: the general-width kernels
+  // (csrc/mlp_step_general.hip) at every batch size, on the workspace of mlp_general_layout
+  const bool gen = general || rla::mlp_general_supported((int)L1, (int)L2);
+  TORCH_CHECK(gen ? rla::mlp_general_widths_ok((int)L1, (int)L2) : rla::mlp_supported((int)L1, (int)L2),
+              "no fused MLP kernel for layer sizes ", L1, "/", L2);
   TORCH_CHECK_VALUE(B >= 1 && B <= rla::kMLPWideMaxB, "mlp_train_step: batch size must be in [1, ",
                     rla::kMLPWideMaxB, "], got ", B, " (nothing was launched)");
   // above 256 rows: the wide family (csrc/mlp_step_wide.hip); at or below, the one-workgroup kernel
-  const bool wide = B >= rla::kMLPWideMinB;
+  const bool wide = gen || B >= rla::kMLPWideMinB;
   const int64_t rows_last = last_rows.has_value() ? *last_rows : B;
   TORCH_CHECK_VALUE(rows_last >= 1 && rows_last <= B, "mlp_train_step: last_rows must be in [1, B = ", B, "], got ",
                     rows_last, " (nothing was launched)");
   TORCH_CHECK_VALUE(wide || (rows_last == B && lr_mask == 0),
-                    "mlp_train_step: last_rows < B and lr_mask belong to the wide step (B > 256)");
+                    "mlp_train_step: last_rows < B and lr_mask belong to the wide step (B > 256) and the general widths");
   TORCH_CHECK_VALUE(lr_mask >= 0 && lr_mask < (1 << 20) && (lr_mask & (lr_mask + 1)) == 0,
                     "mlp_train_step: lr_mask must be 2^k - 1, got ", lr_mask);
   const int64_t np = mlp_param_count(L1, L2);
@@ -372,13 +376,25 @@ void mlp_train_step(optional<Tensor> x_u8, optional<Tensor> x_f32, Tensor labels
     TORCH_CHECK_VALUE(lr_mask == 0 || a.lr_ptr, "mlp_train_step: lr_mask = ", lr_mask, " needs lr_t of ",
                       lr_mask + 1, " rates");
     TORCH_CHECK(a.counters || !a.x_u8, "mlp_train_step: u8 mode needs device counters");
-    const rla::MLPWideLayout lay = rla::mlp_wide_layout((int)L1, (int)L2, (int)B);
+    int64_t park_elems, part_elems;
+    if (gen) {
+      const rla::MLPGeneralLayout lay = rla::mlp_general_layout((int)L1, (int)L2, (int)B);
+      park_elems = lay.park_elems; part_elems = lay.part_elems;
+    } else {
+      const rla::MLPWideLayout lay = rla::mlp_wide_layout((int)L1, (int)L2, (int)B);
+      park_elems = lay.park_elems; part_elems = lay.part_elems;
+    }
     rla::MLPWideArgs w{};
-    w.park = ptr_or_null<uint16_t>(wide_park, "wide_park", at::kBFloat16, lay.park_elems);
-    w.part = ptr_or_null<float>(wide_part, "wide_part", at::kFloat, lay.part_elems);
+    TORCH_CHECK_VALUE(wide_park.has_value() && wide_part.has_value() && wide_hdr.has_value() &&
+                      wide_park->defined() && wide_part->defined() && wide_hdr->defined(),
+                      "mlp_train_step: ", gen ? "general widths need" : "B > 256 needs", " the workspace (ops.fused_mlp.",
+                      gen ? "mlp_general_buffers" : "mlp_wide_buffers", ": wide_park, wide_part, wide_hdr)");
+    TORCH_CHECK_VALUE(wide_park->numel() >= park_elems && wide_part->numel() >= part_elems && wide_hdr->numel() >= 4,
+                      "mlp_train_step: workspace too small: park ", wide_park->numel(), " / ", park_elems, ", part ",
+                      wide_part->numel(), " / ", part_elems, " (nothing was launched)");
+    w.park = ptr_or_null<uint16_t>(wide_park, "wide_park", at::kBFloat16, park_elems);
+    w.part = ptr_or_null<float>(wide_part, "wide_part", at::kFloat, part_elems);
     w.hdr = ptr_or_null<int64_t>(wide_hdr, "wide_hdr", at::kLong, 4);
-    TORCH_CHECK_VALUE(w.park && w.part && w.hdr, "mlp_train_step: B = ", B, " > 256 needs the wide workspace "
-                      "(ops.fused_mlp.mlp_wide_buffers: wide_park, wide_part, wide_hdr)");
     for (const Tensor* t : {&params, &grads, &*wide_park, &*wide_part, &*wide_hdr, &labels})
       TORCH_CHECK(t->device() == params.device(), "mlp_train_step: every operand must be on ", params.device());
     check_aligned(params, "params", 16);
@@ -391,9 +407,10 @@ void mlp_train_step(optional<Tensor> x_u8, optional<Tensor> x_f32, Tensor labels
     w.part_elems = wide_part->numel();
     w.last_rows = (int)rows_last;
     w.lr_mask = (int)lr_mask;
-    const int rc = rla::launch_mlp_wide_step(w, cur_stream(params));
+    const int rc = gen ? rla::launch_mlp_general_step(w, cur_stream(params))
+                       : rla::launch_mlp_wide_step(w, cur_stream(params));
     check_input_affine(rc, "mlp_train_step", x_scale, x_shift);
-    TORCH_CHECK(rc == 0, "wide fused MLP launch refused (code ", rc, "; nothing was launched)");
+    TORCH_CHECK(rc == 0, gen ? "general" : "wide", " fused MLP launch refused (code ", rc, "; nothing was launched)");
     return;
   }
   const int rc = rla::launch_mlp_train_step(a, cur_stream(params));
@@ -654,8 +671,9 @@ void mlp_adam(Tensor params, Tensor grads, Tensor exp_avg, Tensor exp_avg_sq, Te
 
 void mlp_eval(optional<Tensor> x_u8, optional<Tensor> x_f32, Tensor labels, optional<Tensor> index,
               int64_t B, int64_t L1, int64_t L2, Tensor params, optional<Tensor> logits, Tensor out,
-              double x_scale, double x_shift) {
-  TORCH_CHECK(rla::mlp_supported((int)L1, (int)L2), "no fused MLP kernel for layer sizes ", L1, "/", L2);
+              double x_scale, double x_shift, optional<Tensor> h1) {
+  const bool gen = rla::mlp_general_supported((int)L1, (int)L2);
+  TORCH_CHECK(gen || rla::mlp_supported((int)L1, (int)L2), "no fused MLP kernel for layer sizes ", L1, "/", L2);
   check_dev(params, "params", at::kFloat);
   TORCH_CHECK(params.numel() == mlp_param_count(L1, L2), "param arena size mismatch");
   check_dev(labels, "labels", at::kLong);
@@ -685,7 +703,23 @@ void mlp_eval(optional<Tensor> x_u8, optional<Tensor> x_f32, Tensor labels, opti
   a.out = out.data_ptr<float>();
   a.partials = partials ? 1 : 0;
   a.x_scale = (float)x_scale; a.x_shift = (float)x_shift;
-  const int rc = rla::launch_mlp_eval(a, cur_stream(params));
+  int rc;
+  if (gen) {
+    // layer 1 hands H1 [Bp][L1] to the head through this workspace (mlp_general_layout h1_elems)
+    const int64_t need = rla::mlp_general_layout((int)L1, (int)L2, (int)B).h1_elems;
+    uint16_t* hp = ptr_or_null<uint16_t>(h1, "h1", at::kBFloat16);
+    TORCH_CHECK_VALUE(B <= 0 || (hp && h1->numel() >= need), "mlp_eval: layer sizes ", L1, "/", L2, " need the h1 workspace of ",
+                      need, " bf16 (nothing was launched)");
+    TORCH_CHECK((!hp || h1->device() == params.device()) && labels.device() == params.device() &&
+                out.device() == params.device(), "mlp_eval: every operand must be on ", params.device());
+    check_aligned(params, "params", 16);
+    if (hp) check_aligned(*h1, "h1", 16);
+    if (a.x_u8) check_aligned(*x_u8, "x_u8", 16);
+    else check_aligned(*x_f32, "x_f32", 16);
+    rc = rla::launch_mlp_general_eval(a, hp, hp ? h1->numel() : 0, cur_stream(params));
+  } else {
+    rc = rla::launch_mlp_eval(a, cur_stream(params));
+  }
   check_input_affine(rc, "mlp_eval", x_scale, x_shift);
   TORCH_CHECK(rc == 0, "fused MLP eval launch failed");
 }
@@ -1423,7 +1457,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"), py::arg("lr_t"),
         py::arg("adamw"), py::arg("stamps") = py::none(), py::arg("x_scale") = (double)rla::kMLPXScale,
         py::arg("x_shift") = 0.0, py::arg("last_rows") = py::none(), py::arg("lr_mask") = 0,
-        py::arg("wide_park") = py::none(), py::arg("wide_part") = py::none(), py::arg("wide_hdr") = py::none());
+        py::arg("wide_park") = py::none(), py::arg("wide_part") = py::none(), py::arg("wide_hdr") = py::none(),
+        py::arg("general") = false);
+  m.def("mlp_general_layout", [](int64_t L1, int64_t L2, int64_t B) {
+    const rla::MLPGeneralLayout l = rla::mlp_general_layout((int)L1, (int)L2, (int)B);
+    py::dict d;
+    d["nslab"] = l.nslab; d["ncb"] = l.ncb; d["Bp"] = l.Bp; d["slices"] = l.slices; d["np_pad"] = l.np_pad;
+    d["h1"] = l.h1; d["park_elems"] = l.park_elems; d["part_elems"] = l.part_elems; d["h1_elems"] = l.h1_elems;
+    return d;
+  }, "workspace layout of the general-width MLP step (csrc/mlp_step_general.hip)");
+  m.def("mlp_general_supported", [](int64_t a, int64_t b) { return rla::mlp_general_supported((int)a, (int)b); });
   m.def("mlp_wide_layout", [](int64_t L1, int64_t L2, int64_t B) {
     const rla::MLPWideLayout l = rla::mlp_wide_layout((int)L1, (int)L2, (int)B);
     py::dict d;
@@ -1434,7 +1477,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mlp_eval", &mlp_eval, "fused MNIST-MLP forward + NLL/accuracy (u8 mode: pixel = fma(u8, x_scale, x_shift))",
         py::arg("x_u8"), py::arg("x_f32"), py::arg("labels"), py::arg("index"), py::arg("B"), py::arg("L1"),
         py::arg("L2"), py::arg("params"), py::arg("logits"), py::arg("out"),
-        py::arg("x_scale") = (double)rla::kMLPXScale, py::arg("x_shift") = 0.0);
+        py::arg("x_scale") = (double)rla::kMLPXScale, py::arg("x_shift") = 0.0, py::arg("h1") = py::none());
   m.def("mlp3", &mlp3, "fused MNIST-MLP step v3 (pipelined layer 1): kind 0 step, 1 head, 2 tail-grad, "
         "3 tail-adam, 4 prime, 5 step with the in-kernel xGMI exchange, 6 one-launch step (B <= 32), "
         "8 tail-acc (gradient accumulation: a micro-batch inside its window); sgd_momentum: SGD in the tail of 0 / 3",

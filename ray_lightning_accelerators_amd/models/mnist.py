@@ -39,6 +39,11 @@ sum with Adam / AdamW -- through the same engine (``FusedMLPEngine(batch_size=51
 stats ring, short last batch and LR ring as below 256).  Clipping, accumulation and SGD above
 256 rows step through the loader-fed branch of ``train_batch``: ``mlp_train_step`` on the same
 wide kernels, then the allreduce, clip and optimizer launches that branch always had.
+Layer widths outside the ten table pairs -- any multiples of 32 up to 512, e.g. 256/256 or
+96/160 (``ops.fused_mlp.mlp_general``) -- run the general-width kernels of
+csrc/mlp_step_general.hip through the same engine route at EVERY batch size; clipping,
+accumulation, SGD and a scheduled rate at world size > 1 then take the loader-fed branch at
+every batch size, and ``eval_epoch`` reaches the general forward through ``mlp_eval``.
 
 Datasets the resident path serves (``_u8_source``; ``Subset`` / ``random_split`` chains of
 them included): ``.images`` uint8 ``[N, 784]`` with tensor ``.targets`` (``SyntheticMNIST``),
@@ -334,7 +339,8 @@ class FusedMNISTStep:
         # accumulation steps once per window, the in-kernel exchange at every batch; and the
         # exchange's epilogue is Adam / AdamW, so SGD takes the allreduce route too
         if self.world > 1 and get_config().fused_dp and self.clip_norm is None and self.accumulate == 1 \
-                and not self.sgd and B <= 256:  # (the in-kernel exchange stops at 256 rows)
+                and not self.sgd and B <= 256 and not fused_mlp.mlp_general(self.L1, self.L2):
+            # (the in-kernel exchange stops at 256 rows and serves the table widths)
             from ..parallel.comm import get_native_comm
 
             comm = get_native_comm()  # every rank reaches here together (first epoch)
@@ -395,9 +401,9 @@ class FusedMNISTStep:
         else:
             order = self._epoch_order(dl.sampler, idx_map)
         B = dl.batch_size
-        if B > 256 and (B > fused_mlp.WIDE_MAX_B or self.clip_norm is not None or self.accumulate > 1 or self.sgd
+        if (B > 256 or fused_mlp.mlp_general(self.L1, self.L2)) and (B > fused_mlp.WIDE_MAX_B or self.clip_norm is not None or self.accumulate > 1 or self.sgd
                         or (self.lr_ring and self.world > 1)):
-            # above 256 rows the engine serves Adam / AdamW alone (the wide step); clipping,
+            # above 256 rows, and at a general width, the engine serves Adam / AdamW alone; clipping,
             # accumulation and SGD step through the loader-fed branch of train_batch, whose
             # mlp_train_step takes the same wide kernels
             return None

@@ -5,6 +5,13 @@ log_softmax + NLL + accuracy, backward and -- at world size 1 -- the Adam
 update fused into the weight-gradient epilogues.  CPU: an fp32 PyTorch
 reference with identical semantics (also the oracle for the GPU tests).
 
+Layer widths: the ten ``SUPPORTED`` pairs run the table kernels (``csrc/mlp_kernels.hip``,
+``csrc/mlp_step3.hip``, above 256 rows ``csrc/mlp_step_wide.hip``).  Every other pair of
+multiples of 32 in 32 .. 512 (``mlp_general``) runs the general-width kernels of
+``csrc/mlp_step_general.hip`` at every batch size 1 .. 4096 -- layer 1 split over 64-row slabs
+and 64-column blocks, a head per slab, gradient tiles split over the batch, a fixed-order slice
+sum -- and its forward-only instance in ``mlp_eval``.  Anything else has no fused kernel.
+
 Parameter arena layout (== ``nn.Linear`` state_dict order of
 ``layer_1``/``layer_2``/``layer_3``):  W1[L1,784] b1[L1] W2[L2,L1] b2[L2] W3[10,L2] b3[10].
 """
@@ -30,8 +37,23 @@ def mlp_param_count(L1: int, L2: int) -> int:
     return L1 * IN_FEATURES + L1 + L2 * L1 + L2 + NUM_CLASSES * L2 + NUM_CLASSES
 
 
+GENERAL_MAX_WIDTH = 512   # the general head's LDS plan (csrc/mlp_step_general.hip)
+GENERAL_COL_BLOCK = 64    # layer-1 columns per workgroup
+
+
+def _general_widths_ok(L1: int, L2: int) -> bool:
+    return all(32 <= int(w) <= GENERAL_MAX_WIDTH and int(w) % 32 == 0 for w in (L1, L2))
+
+
+def mlp_general(L1: int, L2: int) -> bool:
+    """Whether ``(L1, L2)`` is served by the general-width kernels alone: multiples of 32 in
+    32 .. 512 outside the ``SUPPORTED`` table."""
+    return _general_widths_ok(L1, L2) and (int(L1), int(L2)) not in SUPPORTED
+
+
 def mlp_supported(L1: int, L2: int) -> bool:
-    return (int(L1), int(L2)) in SUPPORTED
+    """A fused kernel exists: a table pair or a general one."""
+    return (int(L1), int(L2)) in SUPPORTED or mlp_general(L1, L2)
 
 
 def mlp_unpack(flat: torch.Tensor, L1: int, L2: int) -> Dict[str, torch.Tensor]:
@@ -186,6 +208,7 @@ def mlp_train_step(
     last_rows: Optional[int] = None,
     lr_mask: int = 0,
     workspace: Optional[Dict[str, torch.Tensor]] = None,
+    route: str = "auto",
 ) -> None:
     """One training micro-step of the MNIST MLP over a flat parameter arena.
 
@@ -208,7 +231,18 @@ def mlp_train_step(
     ``apply_adam``): ``lr_tensor`` is a ring and optimizer step ``t`` reads entry
     ``(t - 1) & lr_mask``; the reference reads the same entry.  Anything above ``WIDE_MAX_B``
     raises a ValueError before a launch.
+
+    A general pair (``mlp_general``) runs csrc/mlp_step_general.hip at every ``B``: four launches
+    with the wide step's contract (``last_rows``, ``lr_mask``, bitwise repeatable), on the
+    workspace of ``mlp_general_buffers``.  ``route="general"`` forces those kernels on a table
+    pair (tests and measurements); ``"auto"`` never does.  Widths with no kernel raise a
+    ValueError before a launch.
     """
+    if route not in ("auto", "general"):
+        raise ValueError(f"mlp_train_step: route must be 'auto' or 'general', got {route!r}")
+    general = use_native(params) and (route == "general" or mlp_general(L1, L2))
+    if use_native(params) and not (_general_widths_ok(L1, L2) if general else mlp_supported(L1, L2)):
+        raise ValueError(f"mlp_train_step: no fused MLP kernel for layer sizes {L1}/{L2} (nothing was launched)")
     if x_u8 is not None:
         x_scale, x_shift = check_input_affine(x_scale, x_shift)
     if not 1 <= int(B) <= WIDE_MAX_B:
@@ -217,10 +251,11 @@ def mlp_train_step(
     lr_mask = int(lr_mask)
     if lr_mask < 0 or lr_mask & (lr_mask + 1) or (lr_mask and (lr_tensor is None or lr_tensor.numel() < lr_mask + 1)):
         raise ValueError(f"mlp_train_step: lr_mask must be 2^k - 1 with lr_tensor of lr_mask + 1 rates, got {lr_mask}")
-    wide = int(B) >= WIDE_MIN_B
+    wide = general or int(B) >= WIDE_MIN_B
     if last_rows != int(B) and (x_u8 is None or (use_native(params) and not wide)):
         raise ValueError("mlp_train_step: a short last batch (last_rows < B) exists in u8 mode only: in the fp32 "
-                         "reference, in the wide step (B > 256) and in the mlp3 kernels (mlp3_launch)")
+                         "reference, in the wide step (B > 256), at the general widths and in the mlp3 "
+                         "kernels (mlp3_launch)")
     if use_native(params):
         args = (x_u8, x_f32, labels, order, counters, int(n_batches), int(B), int(L1), int(L2),
                 params, grads, exp_avg, exp_avg_sq, stats, bool(accumulate_grad), bool(apply_adam),
@@ -231,8 +266,8 @@ def mlp_train_step(
                 raise ValueError("mlp_train_step: lr_mask belongs to the wide step (B > 256)")
             require().mlp_train_step(*args)
             return
-        ws = workspace if workspace is not None else _wide_workspace(L1, L2, B, params.device)
-        require().mlp_train_step(*args, last_rows, lr_mask, ws["park"], ws["part"], ws["hdr"])
+        ws = workspace if workspace is not None else _wide_workspace(L1, L2, B, params.device, general)
+        require().mlp_train_step(*args, last_rows, lr_mask, ws["park"], ws["part"], ws["hdr"], general)
         return
     # ---- fp32 reference ----
     cursor = int(counters[1].item()) if (counters is not None and x_u8 is not None) else 0
@@ -310,13 +345,37 @@ def mlp_wide_buffers(L1: int, L2: int, B: int, device) -> Dict[str, torch.Tensor
             "hdr": torch.zeros(4, dtype=torch.int64, device=device)}
 
 
+def mlp_general_layout(L1: int, L2: int, B: int) -> Dict[str, int]:
+    """Workspace of the general-width step as csrc/mlp_step_general.hip lays it out
+    (``_C.mlp_general_layout``; the binding checks the sizes against its own): the wide step's
+    six parked operands at the same offsets, then ``h1`` -- H1 ``[Bp][L1]`` row-major, which
+    layer 1 hands to the head.  ``ncb``: 64-column blocks of layer 1.  ``h1_elems``: all the
+    forward (``mlp_eval``) needs."""
+    L1, L2, B = int(L1), int(L2), int(B)
+    lay = mlp_wide_layout(L1, L2, B)  # slabs, slices and the six offsets: the same rules
+    lay["ncb"] = (L1 + GENERAL_COL_BLOCK - 1) // GENERAL_COL_BLOCK
+    lay["h1"] = lay["park_elems"]
+    lay["h1_elems"] = lay["Bp"] * L1
+    lay["park_elems"] += lay["h1_elems"]
+    return lay
+
+
+def mlp_general_buffers(L1: int, L2: int, B: int, device) -> Dict[str, torch.Tensor]:
+    """Device workspace of the general-width step (``mlp_train_step(..., workspace=...)``), as
+    ``mlp_wide_buffers``."""
+    lay = mlp_general_layout(L1, L2, B)
+    return {"park": torch.zeros(lay["park_elems"], dtype=torch.bfloat16, device=device),
+            "part": torch.zeros(lay["part_elems"], dtype=torch.float32, device=device),
+            "hdr": torch.zeros(4, dtype=torch.int64, device=device)}
+
+
 _wide_cache: Dict[tuple, Dict[str, torch.Tensor]] = {}
 
 
-def _wide_workspace(L1, L2, B, device) -> Dict[str, torch.Tensor]:
-    key = (int(L1), int(L2), int(B), str(device))
+def _wide_workspace(L1, L2, B, device, general=False) -> Dict[str, torch.Tensor]:
+    key = (int(L1), int(L2), int(B), str(device), bool(general))
     if key not in _wide_cache:
-        _wide_cache[key] = mlp_wide_buffers(L1, L2, B, device)
+        _wide_cache[key] = (mlp_general_buffers if general else mlp_wide_buffers)(L1, L2, B, device)
     return _wide_cache[key]
 
 
@@ -662,12 +721,17 @@ def mlp_eval(
     [ceil(B/32), 2]: per-32-row-chunk (sum NLL, #correct), overwritten -- the GPU
     kernel then runs one workgroup per chunk and the caller's ``out.sum(0)`` is
     deterministic.  Optional log-probs into ``logits``.  u8 mode reads a pixel as
-    ``fmaf(u8, x_scale, x_shift)`` (``input_affine``)."""
+    ``fmaf(u8, x_scale, x_shift)`` (``input_affine``).  A general pair (``mlp_general``) runs the
+    forward-only instance of csrc/mlp_step_general.hip: one workgroup per 64 rows (two chunks),
+    H1 handed from its first launch to its second through a workspace allocated here."""
     if x_u8 is not None:
         x_scale, x_shift = check_input_affine(x_scale, x_shift)
     if use_native(params):
+        h1 = None
+        if mlp_general(L1, L2) and int(B) > 0:
+            h1 = torch.empty(mlp_general_layout(L1, L2, B)["h1_elems"], dtype=torch.bfloat16, device=params.device)
         require().mlp_eval(x_u8, x_f32, labels, index, int(B), int(L1), int(L2), params, logits, out,
-                           float(x_scale), float(x_shift))
+                           float(x_scale), float(x_shift), h1)
         return
     x, y = _gather_batch(x_u8, x_f32, labels, None, 0, B, index=index, x_scale=x_scale, x_shift=x_shift)
     with torch.no_grad():

@@ -24,6 +24,10 @@ re-designed for MI355X instead of translating PL's DDP loop:
   adds the allreduce and the arena Adam.  ``clip_norm``, ``accumulate`` > 1, SGD and
   ``dp_context`` stop at 256 rows (ValueError); ``capture`` / ``run``, the stats ring,
   ``set_step``, ``begin_epoch(last_rows=...)`` and the LR ring work as below 256;
+  layer widths outside the table (``ops.fused_mlp.mlp_general``: multiples of 32 up to 512):
+  the same self-contained route at EVERY batch size, on the general-width kernels of
+  csrc/mlp_step_general.hip (four launches per step) -- with the same refusals, and none of
+  the table kernels' shadow or rings;
   world size > 1: with a ``dp_context`` the same launches, each block exchanging
   its gradient values with the peers over xGMI inside its Adam epilogue (kinds
   Step1DP / StepDP); otherwise head -> tail(grad) -> allreduce(SUM) ->
@@ -142,6 +146,7 @@ class FusedMLPEngine:
         dampening: float = 0.0,
         nesterov: bool = False,
         lr_ring: int = 0,
+        route: str = "auto",
     ):
         """``buffers``: optional external fp32 tensors ``params`` / ``grads`` /
         ``exp_avg`` / ``exp_avg_sq`` (e.g. views of a Trainer's parameter arena,
@@ -182,7 +187,11 @@ class FusedMLPEngine:
         hands a captured graph a different rate at every step without a host write in between.
         A step without a scheduled rate runs at ``lr``, as outside ring mode.  The one-launch
         step runs its schedule instances; the one-launch in-kernel exchange has none, so a
-        ``dp_context`` engine then steps as two launches (one warning)."""
+        ``dp_context`` engine then steps as two launches (one warning).
+        ``route``: ``mlp_train_step``'s -- "general" runs the general-width kernels on a table
+        pair too (tests and measurements); "auto" never does."""
+        if route not in ("auto", "general"):
+            raise ValueError(f"route must be 'auto' or 'general', got {route!r}")
         if isinstance(lr_ring, bool) or int(lr_ring) != lr_ring or int(lr_ring) < 0 or int(lr_ring) == 1 \
                 or int(lr_ring) & (int(lr_ring) - 1):
             raise ValueError(f"lr_ring must be 0 or a power of two >= 2, got {lr_ring!r}")
@@ -216,13 +225,19 @@ class FusedMLPEngine:
             raise ValueError(f"no fused kernel for layer sizes {layer_1}/{layer_2}")
         if not 1 <= batch_size <= fused_mlp.WIDE_MAX_B:
             raise ValueError(f"fused MLP engine supports batch sizes 1..{fused_mlp.WIDE_MAX_B}")
-        # above 256 rows: the wide step (csrc/mlp_step_wide.hip), Adam / AdamW only
-        self.wide = int(batch_size) >= fused_mlp.WIDE_MIN_B
+        # above 256 rows: the wide step (csrc/mlp_step_wide.hip), Adam / AdamW only; widths outside
+        # the table: the general-width step (csrc/mlp_step_general.hip), the same route at every B
+        self.general = fused_mlp.mlp_general(layer_1, layer_2) or route == "general"
+        self.wide = int(batch_size) >= fused_mlp.WIDE_MIN_B or self.general
         if self.wide:
             for bad, what in ((dp_context is not None, "dp_context (the in-kernel exchange)"),
                               (clip_norm is not None, "clip_norm"), (accumulate > 1, "accumulate > 1"),
                               (optimizer == "sgd", "optimizer='sgd'"),
                               (lr_ring and int(world_size) > 1, "lr_ring at world size > 1")):
+                if bad and self.general:
+                    raise ValueError(f"fused MLP engine: {what} is served at the table widths only "
+                                     f"(ops.fused_mlp.SUPPORTED, up to batch size 256); at {layer_1}/{layer_2} the "
+                                     "engine runs Adam / AdamW on the general-width step")
                 if bad:
                     raise ValueError(f"fused MLP engine: {what} is served up to batch size 256 only (got "
                                      f"{batch_size}); above it the engine runs Adam / AdamW on the wide step")
@@ -285,12 +300,20 @@ class FusedMLPEngine:
             self.clip_out = torch.zeros(4, device=self.device)
         self._clip_last = dict(_CLIP_HEALTH0)
         self._clip_since = 0  # global_step when clip_out was last zeroed
-        lay = fused_mlp.mlp_shadow_layout(self.L1, self.L2)
-        self.shadow = torch.zeros(lay["total"], dtype=torch.bfloat16, device=self.device)
-        # (the wide step keeps none of the pipelined step's rings: only counters / hand are used)
-        bufs = fused_mlp.mlp3_buffers(self.L1, self.L2, 32 if self.wide else self.B, self.device)
-        self.wide_ws = (fused_mlp.mlp_wide_buffers(self.L1, self.L2, self.B, self.device)
-                        if self.wide and self.native else None)
+        if self.general:
+            # no shadow and no pipelined-step rings: the state words alone
+            self.shadow = None
+            bufs = dict.fromkeys(("dh1t", "xring", "h1pre", "act", "yring", "head_part"))
+            bufs["counters"] = torch.zeros(16, dtype=torch.int64, device=self.device)
+            bufs["hand"] = torch.zeros(fused_mlp.mlp3_hand_words(self.L1, self.L2), dtype=torch.int64,
+                                       device=self.device)
+        else:
+            lay = fused_mlp.mlp_shadow_layout(self.L1, self.L2)
+            self.shadow = torch.zeros(lay["total"], dtype=torch.bfloat16, device=self.device)
+            # (the wide step keeps none of the pipelined step's rings: only counters / hand are used)
+            bufs = fused_mlp.mlp3_buffers(self.L1, self.L2, 32 if self.wide else self.B, self.device)
+        make_ws = fused_mlp.mlp_general_buffers if self.general else fused_mlp.mlp_wide_buffers
+        self.wide_ws = make_ws(self.L1, self.L2, self.B, self.device) if self.wide and self.native else None
         # counters: [0] optimizer step, [1] next batch cursor, [2] last consumed cursor,
         # [3] H1pre/X ring slot, [4] epoch buffer of `order` that [1] indexes
         self.counters = bufs["counters"]
@@ -314,7 +337,7 @@ class FusedMLPEngine:
         # nor does accumulation (Adam only at a window's close), nor SGD (the one-launch
         # kernel applies Adam)
         self.one_launch = (self.B <= fused_mlp.ONE_LAUNCH_MAX_B and os.environ.get("RLA_MLP_ONE_LAUNCH") != "0"
-                           and clip_norm is None and accumulate == 1 and not self.sgd)
+                           and clip_norm is None and accumulate == 1 and not self.sgd and not self.general)
         # the dataset's Normalize(mean, std) or None, and the kernels' pixel map derived from it
         self.normalize = None
         self.x_scale, self.x_shift = fused_mlp.input_affine(None)
@@ -673,8 +696,10 @@ class FusedMLPEngine:
         self.refresh_shadow()
 
     def refresh_shadow(self) -> None:
-        """Rebuild the bf16 weight shadows after the fp32 params changed outside a step."""
-        fused_mlp.mlp_refresh_shadow(self.params, self.shadow, self.L1, self.L2)
+        """Rebuild the bf16 weight shadows after the fp32 params changed outside a step (the
+        general-width step reads the fp32 master alone: nothing to rebuild)."""
+        if not self.general:
+            fused_mlp.mlp_refresh_shadow(self.params, self.shadow, self.L1, self.L2)
         self._shadow_stale = False
         self._primed = False
 
@@ -798,7 +823,7 @@ class FusedMLPEngine:
         if self._wide_native:  # self-contained steps: no pending batch, no shadow
             self._primed = True
             return
-        if self._shadow_stale:
+        if self._shadow_stale and not self.general:
             self._shadow_stale = False
             fused_mlp.mlp_refresh_shadow(self.params, self.shadow, self.L1, self.L2)
         if self.native:
@@ -887,8 +912,9 @@ class FusedMLPEngine:
                                       **self._sgd_kw(), **kw)
 
     def _wide_step(self) -> None:
-        """One batch above 256 rows: world size 1 is one fused ``mlp_train_step`` (three
-        launches, Adam in the last); otherwise gradients -> allreduce -> ``mlp_adam_`` with the
+        """One batch above 256 rows, or at a general width: world size 1 is one fused
+        ``mlp_train_step`` (three or four launches, Adam in the last); otherwise gradients ->
+        allreduce -> ``mlp_adam_`` (general widths, which keep no shadow: ``fused_adam_``) with the
         1 / world average folded into ``grad_scale``.  u8 mode on the engine's own order /
         counters, so a captured graph replays successive batches."""
         fused = self.world_size == 1
@@ -897,10 +923,16 @@ class FusedMLPEngine:
             order=self.order[0], counters=self.counters[:2], n_batches=self.n_batches, exp_avg=self.exp_avg,
             exp_avg_sq=self.exp_avg_sq, stats=self.stats, apply_adam=fused, lr=self.lr, betas=self.betas,
             eps=self.eps, weight_decay=self.wd, lr_tensor=self.lr_tensor, adamw=self.adamw, x_scale=self.x_scale,
-            x_shift=self.x_shift, last_rows=self.last_rows, lr_mask=self.lr_mask, workspace=self.wide_ws)
+            x_shift=self.x_shift, last_rows=self.last_rows, lr_mask=self.lr_mask, workspace=self.wide_ws,
+            route="general" if self.general else "auto")
         if not fused:
             if self.allreduce is not None:
                 self.allreduce(self.comm_buffer)
+            if self.general:
+                fused_adam_(self.params, self.grads, self.exp_avg, self.exp_avg_sq, lr=self.lr, betas=self.betas,
+                            eps=self.eps, weight_decay=self.wd, grad_scale=1.0 / self.world_size, adamw=self.adamw,
+                            step=self.counters[0:1], lr_tensor=self.lr_tensor)
+                return
             fused_mlp.mlp_adam_(self.params, self.grads, self.exp_avg, self.exp_avg_sq, self.shadow, L1=self.L1,
                                 L2=self.L2, lr=self.lr, step=self.counters[0:1], betas=self.betas, eps=self.eps,
                                 weight_decay=self.wd, grad_scale=1.0 / self.world_size, adamw=self.adamw,
