@@ -310,7 +310,7 @@ void mlp_train_step(optional<Tensor> x_u8, optional<Tensor> x_f32, Tensor labels
                     double eps, double weight_decay, optional<Tensor> lr_t, bool adamw,
                     optional<Tensor> stamps, double x_scale, double x_shift, optional<int64_t> last_rows,
                     int64_t lr_mask, optional<Tensor> wide_park, optional<Tensor> wide_part,
-                    optional<Tensor> wide_hdr, bool general) {
+                    optional<Tensor> wide_hdr, bool general, int64_t arena_align) {
   // widths outside the table, or `general` on a table pair: the general-width kernels
   // (csrc/mlp_step_general.hip) at every batch size, on the workspace of mlp_general_layout
   const bool gen = general || rla::mlp_general_supported((int)L1, (int)L2);
@@ -327,7 +327,9 @@ void mlp_train_step(optional<Tensor> x_u8, optional<Tensor> x_f32, Tensor labels
                     "mlp_train_step: last_rows < B and lr_mask belong to the wide step (B > 256) and the general widths");
   TORCH_CHECK_VALUE(lr_mask >= 0 && lr_mask < (1 << 20) && (lr_mask & (lr_mask + 1)) == 0,
                     "mlp_train_step: lr_mask must be 2^k - 1, got ", lr_mask);
-  const int64_t np = mlp_param_count(L1, L2);
+  TORCH_CHECK_VALUE(arena_align == 1 || (gen && arena_align == 4),
+                    "mlp_train_step: arena_align must be 1, or 4 on the general-width kernels, got ", arena_align);
+  const int64_t np = gen ? rla::mlp_general_param_count((int)L1, (int)L2, (int)arena_align) : mlp_param_count(L1, L2);
   check_dev(params, "params", at::kFloat);
   check_dev(grads, "grads", at::kFloat);
   TORCH_CHECK(params.numel() == np && grads.numel() == np, "param arena must hold ", np, " floats");
@@ -407,7 +409,7 @@ void mlp_train_step(optional<Tensor> x_u8, optional<Tensor> x_f32, Tensor labels
     w.part_elems = wide_part->numel();
     w.last_rows = (int)rows_last;
     w.lr_mask = (int)lr_mask;
-    const int rc = gen ? rla::launch_mlp_general_step(w, cur_stream(params))
+    const int rc = gen ? rla::launch_mlp_general_step(w, cur_stream(params), (int)arena_align)
                        : rla::launch_mlp_wide_step(w, cur_stream(params));
     check_input_affine(rc, "mlp_train_step", x_scale, x_shift);
     TORCH_CHECK(rc == 0, gen ? "general" : "wide", " fused MLP launch refused (code ", rc, "; nothing was launched)");
@@ -671,11 +673,14 @@ void mlp_adam(Tensor params, Tensor grads, Tensor exp_avg, Tensor exp_avg_sq, Te
 
 void mlp_eval(optional<Tensor> x_u8, optional<Tensor> x_f32, Tensor labels, optional<Tensor> index,
               int64_t B, int64_t L1, int64_t L2, Tensor params, optional<Tensor> logits, Tensor out,
-              double x_scale, double x_shift, optional<Tensor> h1) {
+              double x_scale, double x_shift, optional<Tensor> h1, int64_t arena_align) {
   const bool gen = rla::mlp_general_supported((int)L1, (int)L2);
   TORCH_CHECK(gen || rla::mlp_supported((int)L1, (int)L2), "no fused MLP kernel for layer sizes ", L1, "/", L2);
+  TORCH_CHECK_VALUE(arena_align == 1 || (gen && arena_align == 4),
+                    "mlp_eval: arena_align must be 1, or 4 on the general-width kernels, got ", arena_align);
   check_dev(params, "params", at::kFloat);
-  TORCH_CHECK(params.numel() == mlp_param_count(L1, L2), "param arena size mismatch");
+  TORCH_CHECK(params.numel() == (gen ? rla::mlp_general_param_count((int)L1, (int)L2, (int)arena_align)
+                                     : mlp_param_count(L1, L2)), "param arena size mismatch");
   check_dev(labels, "labels", at::kLong);
   check_dev(out, "out", at::kFloat);
   TORCH_CHECK(out.is_contiguous(), "out must be contiguous");
@@ -716,7 +721,7 @@ void mlp_eval(optional<Tensor> x_u8, optional<Tensor> x_f32, Tensor labels, opti
     if (hp) check_aligned(*h1, "h1", 16);
     if (a.x_u8) check_aligned(*x_u8, "x_u8", 16);
     else check_aligned(*x_f32, "x_f32", 16);
-    rc = rla::launch_mlp_general_eval(a, hp, hp ? h1->numel() : 0, cur_stream(params));
+    rc = rla::launch_mlp_general_eval(a, hp, hp ? h1->numel() : 0, cur_stream(params), (int)arena_align);
   } else {
     rc = rla::launch_mlp_eval(a, cur_stream(params));
   }
@@ -1458,7 +1463,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("adamw"), py::arg("stamps") = py::none(), py::arg("x_scale") = (double)rla::kMLPXScale,
         py::arg("x_shift") = 0.0, py::arg("last_rows") = py::none(), py::arg("lr_mask") = 0,
         py::arg("wide_park") = py::none(), py::arg("wide_part") = py::none(), py::arg("wide_hdr") = py::none(),
-        py::arg("general") = false);
+        py::arg("general") = false, py::arg("arena_align") = 1);
+  m.def("mlp_general_param_count", [](int64_t L1, int64_t L2, int64_t al) {
+    TORCH_CHECK_VALUE(al == 1 || al == 4, "arena_align must be 1 or 4, got ", al);
+    return rla::mlp_general_param_count((int)L1, (int)L2, (int)al);
+  }, py::arg("L1"), py::arg("L2"), py::arg("arena_align") = 1);
   m.def("mlp_general_layout", [](int64_t L1, int64_t L2, int64_t B) {
     const rla::MLPGeneralLayout l = rla::mlp_general_layout((int)L1, (int)L2, (int)B);
     py::dict d;
@@ -1477,7 +1486,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mlp_eval", &mlp_eval, "fused MNIST-MLP forward + NLL/accuracy (u8 mode: pixel = fma(u8, x_scale, x_shift))",
         py::arg("x_u8"), py::arg("x_f32"), py::arg("labels"), py::arg("index"), py::arg("B"), py::arg("L1"),
         py::arg("L2"), py::arg("params"), py::arg("logits"), py::arg("out"),
-        py::arg("x_scale") = (double)rla::kMLPXScale, py::arg("x_shift") = 0.0, py::arg("h1") = py::none());
+        py::arg("x_scale") = (double)rla::kMLPXScale, py::arg("x_shift") = 0.0, py::arg("h1") = py::none(),
+        py::arg("arena_align") = 1);
   m.def("mlp3", &mlp3, "fused MNIST-MLP step v3 (pipelined layer 1): kind 0 step, 1 head, 2 tail-grad, "
         "3 tail-adam, 4 prime, 5 step with the in-kernel xGMI exchange, 6 one-launch step (B <= 32), "
         "8 tail-acc (gradient accumulation: a micro-batch inside its window); sgd_momentum: SGD in the tail of 0 / 3",

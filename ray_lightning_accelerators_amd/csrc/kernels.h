@@ -510,18 +510,23 @@ int launch_mlp_wide_step(const MLPWideArgs& a, hipStream_t stream);
 
 // ---------------------------------------------------------------------------
 // General-width step and forward (csrc/mlp_step_general.hip): mlp_train_step's contract for
-// every L1, L2 in {32, 64, ..., 512} at every 1 <= B <= kMLPWideMaxB, four launches (layer 1
-// over 64-row slabs x 64-column blocks, the head per slab, gradient tiles x batch slices,
-// slice sum + epilogue), every reduction in a fixed order.  Run-time widths: one instance.
+// every 1 <= L1, L2 <= 512 (but the odd multiples of 16, which stay refused) at every
+// 1 <= B <= kMLPWideMaxB, four launches (layer 1 over 64-row slabs x 64-column blocks, the head
+// per slab, gradient tiles x batch slices, slice sum + epilogue), every reduction in a fixed order.  Run-time widths: one instance for the multiples
+// of 32 and one ragged instance for the rest (padded compute, true storage: the workspace keeps
+// the widths rounded up to 32, the parameter and gradient arenas the true ones).
 // ---------------------------------------------------------------------------
 constexpr int kMLPGeneralMaxWidth = 512;  // the head's LDS plan: H1 and H2 of a slab, 2 x 66,560 B
 constexpr int kMLPGeneralColBlock = 64;   // layer-1 columns per workgroup
 
 // whether launch_mlp_general_* accept the widths (table pairs included)
 inline bool mlp_general_widths_ok(int L1, int L2) {
-  return L1 >= 32 && L2 >= 32 && L1 <= kMLPGeneralMaxWidth && L2 <= kMLPGeneralMaxWidth && L1 % 32 == 0 &&
-         L2 % 32 == 0;
+  return L1 >= 1 && L2 >= 1 && L1 <= kMLPGeneralMaxWidth && L2 <= kMLPGeneralMaxWidth && L1 % 32 != 16 &&
+         L2 % 32 != 16;  // 16, 48, 80, ...: no kernel (16/64, 48/64 and 64/48 are refused by contract)
 }
+// floats of the arena W1 b1 W2 b2 W3 b3: arena_align 1 packs them back to back, 4 starts each on
+// a multiple of 4 floats (16-byte aligned views); b3 ends it either way
+int64_t mlp_general_param_count(int L1, int L2, int arena_align);
 // the pairs only the general kernels serve: valid widths outside the table (mlp_supported)
 bool mlp_general_supported(int L1, int L2);
 
@@ -530,20 +535,22 @@ struct MLPGeneralLayout {
   int64_t Bp;          // nslab * 64
   int slices;          // batch slices of the parameter launch (the wide step's rule)
   int64_t np_pad;
-  int64_t h1;          // element offset in park of H1 [Bp][L1] row-major, after the wide step's six
-  int64_t park_elems;  // bf16: XT H1T H2T dH2T dZT dH1T ([feature][Bp] each), then H1
+  int64_t h1;          // element offset in park of H1 [Bp][L1p] row-major, after the wide step's six
+  int64_t park_elems;  // bf16: XT H1T H2T dH2T dZT dH1T ([feature][Bp] each), then H1; widths rounded up to 32
   int64_t part_elems;  // fp32: [slices][np_pad] partials, then [nslab][4] slab stats
-  int64_t h1_elems;    // Bp * L1: all the forward (launch_mlp_general_eval) needs
+  int64_t h1_elems;    // Bp * L1p: all the forward (launch_mlp_general_eval) needs
 };
 MLPGeneralLayout mlp_general_layout(int L1, int L2, int B);
 
 // MLPWideArgs with the workspace of mlp_general_layout.  0, or before any launch: -1 widths,
-// -2 batch outside [1, kMLPWideMaxB], -13 pixel map, -15 last_rows, -16 lr_mask, -17 workspace
-// missing or too small
-int launch_mlp_general_step(const MLPWideArgs& a, hipStream_t stream);
+// or arena_align, -2 batch outside [1, kMLPWideMaxB], -13 pixel map, -15 last_rows, -16 lr_mask,
+// -17 workspace missing or too small.  arena_align: how params / grads / the Adam state pack the
+// six tensors (mlp_general_param_count); the arenas' base stays 16-byte aligned.
+int launch_mlp_general_step(const MLPWideArgs& a, hipStream_t stream, int arena_align = 1);
 // mlp_eval's outputs for any B >= 0; h1: workspace of h1_elems bf16, 16-byte aligned.
-// 0, or before any launch: -1 widths, -13 pixel map, -17 workspace
-int launch_mlp_general_eval(const MLPEvalArgs& a, uint16_t* h1, int64_t h1_elems, hipStream_t stream);
+// 0, or before any launch: -1 widths or arena_align, -13 pixel map, -17 workspace
+int launch_mlp_general_eval(const MLPEvalArgs& a, uint16_t* h1, int64_t h1_elems, hipStream_t stream,
+                            int arena_align = 1);
 
 }  // namespace rla
 

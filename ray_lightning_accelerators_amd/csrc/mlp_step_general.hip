@@ -1,5 +1,6 @@
 // General-width training step and forward of the MNIST classifier MLP (784 -> L1 -> L2 -> 10)
-// for gfx950: every L1, L2 in {32, 64, ..., 512}, 1 <= B <= 4096 (the forward: any B).  The
+// for gfx950: every 1 <= L1, L2 <= 512 but the odd multiples of 16 (kernels.h), 1 <= B <= 4096
+// (the forward: any B).  The
 // table kernels hold whole layers per CU (mlp_step3.hip) or alias H1 / H2 / Z / dZ into the dead
 // X image of a slab with whole-K accumulators for every column tile of layer 1
 // (mlp_step_wide.hip, L1 <= 128, L2 <= 256); neither plan reaches 512.  Here the work is split
@@ -40,6 +41,27 @@
 // (row, column) tile as the wide slab does): the W2 / W3 fragment, which dH1 gathers with a
 // stride of L1 floats, is fetched once for four MFMAs.
 //
+// Ragged widths (L1 or L2 no multiple of 32) run instances of their own (RAGGED = true); the
+// multiples of 32 keep the instances they had.  Padded compute, true storage: with L1p, L2p the
+// widths rounded up to 32, everything the MFMA core touches -- the LDS images of H1 / H2, the
+// parked [feature][Bp] operands, the h1 hand-off, the tile lists -- keeps the padded extents,
+// so no tile loop, LDS stride or workspace offset changes shape; the parameter, gradient and
+// Adam arenas keep the true widths (goff), and nothing keeps a padded copy of the weights.
+//   * zero-fill, never over-read: a weight fragment's elements at or past the row's end (K pad)
+//     and whole rows at or past the width (column pad) are exact zeros in the registers (ldw8),
+//     padded bias lanes read 0, so the padded columns of H1 / H2 are relu(0 + 0) = 0 and stay 0
+//     through dH2 / dH1 (their ReLU mask).  What lies behind a row in the arena -- the next
+//     row's first weight, b2 behind W2 -- is never loaded, so an Inf there cannot meet a 0.
+//   * alignment: with L1 % 4 != 0 the tensors' offsets and the W2 / W3 row starts are only
+//     4-byte aligned.  ldw8 loads dwords there and float4s where a lane's eight floats exist
+//     and start a 16-byte line.  W1's rows are 784 floats: its stream stays float4, only the
+//     row count is masked.
+//   * masked stores: launch 3 computes whole 16x16 tiles over the padded extents and stores the
+//     elements inside the true tensors only.
+//   * the sums: a ragged step adds the same numbers in the same order as the aligned step at
+//     (L1p, L2p) on zero-padded parameters, plus exact zeros -- the two agree bit for bit.
+// The arena may pack the six tensors back to back or each on a multiple of 4 floats (goff's al).
+//
 // Launches 1 and 2 only READ counters and launch 4 is the only writer; block (0, 0) of launch 1
 // leaves (t, cursor, rows) in the workspace header for launch 4.
 #include "common.h"
@@ -70,12 +92,29 @@ static_assert(kCB == 64 && kWaves == 8, "a wave owns one row tile and two of the
 struct GOff {
   int64_t W1, B1, W2, B2, W3, B3, NP;
 };
+// al = 1: the six tensors back to back; al = 4: each starts on a multiple of 4 floats, as a
+// parameter arena with 16-byte aligned views packs them (the two agree where L1 and L2 are
+// multiples of 4).  NP ends with b3: no pad behind the last tensor.
 inline __host__ __device__ GOff goff(int L1, int L2) {
   GOff o;
   o.W1 = 0; o.B1 = (int64_t)L1 * kD; o.W2 = o.B1 + L1; o.B2 = o.W2 + (int64_t)L2 * L1;
   o.W3 = o.B2 + L2; o.B3 = o.W3 + kNC * L2; o.NP = o.B3 + kNC;
   return o;
 }
+inline __host__ __device__ GOff goff(int L1, int L2, int al) {
+  GOff o;
+  o.W1 = 0; o.B1 = (int64_t)L1 * kD;
+  o.W2 = (o.B1 + L1 + al - 1) / al * al;
+  o.B2 = (o.W2 + (int64_t)L2 * L1 + al - 1) / al * al;
+  o.W3 = (o.B2 + L2 + al - 1) / al * al;
+  o.B3 = (o.W3 + kNC * L2 + al - 1) / al * al;
+  o.NP = o.B3 + kNC;
+  return o;
+}
+
+// Ragged widths: what the MFMA core touches (LDS images, parked operands, the h1 hand-off, the
+// tile lists) keeps the extent rounded up to 32; the arenas keep the true one.
+inline __host__ __device__ int pad32(int w) { return (w + 31) & ~31; }
 
 // Parked operands (element offsets): the wide step's six, [feature][Bp] each, then H1 [Bp][L1].
 struct GPark {
@@ -117,9 +156,23 @@ struct GenArgs {
   float* logits;            // forward only, optional
   float* out;               // forward only
   int partials;
+  int align;                // ragged instances only: goff's al (the others never read it)
 };
 
 __device__ __forceinline__ void st4(__bf16* p, bf16x4 v) { *reinterpret_cast<bf16x4*>(p) = v; }
+
+// Ragged rows: p[0 .. 8) as bf16 with every element at or past nv an exact zero -- never what
+// lies behind the row in the arena (the next row's first weight, or the next tensor).  p needs
+// 4-byte alignment only; a lane whose eight floats exist and start a 16-byte line takes two
+// float4 loads (every lane of an interior K step when L1 is a multiple of 4).
+__device__ __forceinline__ bf16x8 ldw8(const float* p, int nv) {
+  if (nv >= 8 && (reinterpret_cast<uintptr_t>(p) & 15) == 0) return cvt8(ld4(p), ld4(p + 4));
+  bf16x8 v = zero8();
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    if (j < nv) v[j] = (__bf16)p[j];
+  return v;
+}
 
 // batch position and size from the device state (a captured graph replays at any cursor)
 __device__ __forceinline__ void batch_of(const GenArgs& a, bool u8, int64_t& cursor, int& rows) {
@@ -130,12 +183,13 @@ __device__ __forceinline__ void batch_of(const GenArgs& a, bool u8, int64_t& cur
 // ---------------------------------------------------------------------------------------
 // Launch 1: layer 1 of one (slab, column block).
 // ---------------------------------------------------------------------------------------
-template <bool U8>
+template <bool U8, bool RAGGED>
 __global__ __launch_bounds__(kThreads) void mlp_general_l1_kernel(GenArgs a) {
   __shared__ __attribute__((aligned(16))) __bf16 sX[kBC * kXS];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r16 = lane & 15, g = lane >> 4;
   const int slab = blockIdx.x, cb = blockIdx.y, row0 = slab * kBC;
   const int L1 = a.L1;
+  const int L1p = RAGGED ? pad32(L1) : L1;  // columns of H1 / H1T: those in [L1, L1p) are stored as zeros
   const int64_t Bp = a.Bp;
   int64_t cursor;
   int rows;
@@ -197,34 +251,37 @@ __global__ __launch_bounds__(kThreads) void mlp_general_l1_kernel(GenArgs a) {
   const float* b1 = a.params + (int64_t)L1 * kD;
   const int mt1 = wv & 3, ct0 = wv >> 2;
   const int nc0 = cb * kCB + ct0 * 16, nc1 = nc0 + 32;  // first column of each tile
-  const bool live0 = nc0 < L1, live1 = nc1 < L1;        // wave-uniform: L1 is a multiple of 16
+  const bool live0 = nc0 < L1p, live1 = nc1 < L1p;      // wave-uniform: L1p is a multiple of 16
+  // ragged: whether this lane's W1 row exists (a row at or past L1 is a fragment of zeros: the
+  // row count is ragged, the 784-float rows themselves stay 16-byte aligned float4 streams)
+  const bool ok0 = !RAGGED || nc0 + r16 < L1, ok1 = !RAGGED || nc1 + r16 < L1;
   f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-  const float* w0 = W1 + (int64_t)((live0 ? nc0 : 0) + r16) * kD;
-  const float* w1 = W1 + (int64_t)((live1 ? nc1 : 0) + r16) * kD;
+  const float* w0 = W1 + (int64_t)(RAGGED ? (ok0 ? nc0 + r16 : 0) : (live0 ? nc0 : 0) + r16) * kD;
+  const float* w1 = W1 + (int64_t)(RAGGED ? (ok1 ? nc1 + r16 : 0) : (live1 ? nc1 : 0) + r16) * kD;
 #pragma unroll 5
   for (int ks = 0; ks < kKS1; ++ks) {
     const int k = ks * 32 + 8 * g;
     const bf16x8 afrag = ld8(sX + (mt1 * 16 + r16) * kXS + k);
     bf16x8 f0 = zero8(), f1 = zero8();
     if (k < kD) {
-      if (live0) f0 = cvt8(ld4(w0 + k), ld4(w0 + k + 4));
-      if (live1) f1 = cvt8(ld4(w1 + k), ld4(w1 + k + 4));
+      if (live0 && ok0) f0 = cvt8(ld4(w0 + k), ld4(w0 + k + 4));
+      if (live1 && ok1) f1 = cvt8(ld4(w1 + k), ld4(w1 + k + 4));
     }
     acc0 = mfma16(afrag, f0, acc0);
     acc1 = mfma16(afrag, f1, acc1);
   }
-  __bf16* h1t = a.park ? a.park + gpark(L1, a.L2, Bp).h1t : nullptr;
+  __bf16* h1t = a.park ? a.park + gpark(L1p, a.L2, Bp).h1t : nullptr;
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     if (!(j ? live1 : live0)) continue;
     const f32x4 acc = j ? acc1 : acc0;
     const int n = (j ? nc1 : nc0) + r16;
-    const float bias = b1[n];
+    const float bias = (j ? ok1 : ok0) ? b1[n] : 0.f;  // a padded column: relu(0 + 0)
     bf16x4 t4;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const __bf16 h = (__bf16)fmaxf(acc[i] + bias, 0.f);
-      a.h1[(int64_t)(row0 + mt1 * 16 + 4 * g + i) * L1 + n] = h;
+      a.h1[(int64_t)(row0 + mt1 * 16 + 4 * g + i) * L1p + n] = h;
       t4[i] = h;
     }
     if (h1t) st4(h1t + (int64_t)n * Bp + row0 + mt1 * 16 + 4 * g, t4);
@@ -234,10 +291,12 @@ __global__ __launch_bounds__(kThreads) void mlp_general_l1_kernel(GenArgs a) {
 // ---------------------------------------------------------------------------------------
 // Launch 2: the head of one slab.
 // ---------------------------------------------------------------------------------------
-template <bool TRAIN, bool U8>
+template <bool TRAIN, bool U8, bool RAGGED>
 __global__ __launch_bounds__(kThreads) void mlp_general_head_kernel(GenArgs a) {
   __shared__ __attribute__((aligned(16))) char smem[kHeadLds];
-  const int L1 = a.L1, L2 = a.L2, H1S = L1 + 8, H2S = L2 + 8, TN1 = L1 / 16, TN2 = L2 / 16;
+  const int L1 = a.L1, L2 = a.L2;
+  const int L1p = RAGGED ? pad32(L1) : L1, L2p = RAGGED ? pad32(L2) : L2;
+  const int H1S = L1p + 8, H2S = L2p + 8, TN1 = L1p / 16, TN2 = L2p / 16;
   __bf16* sH1 = (__bf16*)smem;
   __bf16* sH2 = sH1 + kBC * H1S;
   float* sZ = (float*)(sH2 + kBC * H2S);
@@ -247,8 +306,8 @@ __global__ __launch_bounds__(kThreads) void mlp_general_head_kernel(GenArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r16 = lane & 15, g = lane >> 4;
   const int slab = blockIdx.x, row0 = slab * kBC;
   const int64_t Bp = a.Bp;
-  const GPark pk = gpark(L1, L2, Bp);
-  const GOff o = goff(L1, L2);
+  const GPark pk = gpark(L1p, L2p, Bp);
+  const GOff o = RAGGED ? goff(L1, L2, a.align) : goff(L1, L2);
   int64_t cursor;
   int rows;
   batch_of(a, U8, cursor, rows);
@@ -260,10 +319,10 @@ __global__ __launch_bounds__(kThreads) void mlp_general_head_kernel(GenArgs a) {
   const float* b3 = a.params + o.B3;
 
   // ---- the slab's H1 rows into LDS, its labels (rows past the batch: -1) ----
-  const int cpr = L1 / 8;
+  const int cpr = L1p / 8;
   for (int t = tid; t < kBC * cpr; t += kThreads) {
     const int r = t / cpr, c = t - r * cpr;
-    *reinterpret_cast<bf16x8*>(sH1 + r * H1S + c * 8) = ld8(a.h1 + (int64_t)(row0 + r) * L1 + c * 8);
+    *reinterpret_cast<bf16x8*>(sH1 + r * H1S + c * 8) = ld8(a.h1 + (int64_t)(row0 + r) * L1p + c * 8);
   }
   if (tid < kBC) {
     int y = -1;
@@ -277,15 +336,18 @@ __global__ __launch_bounds__(kThreads) void mlp_general_head_kernel(GenArgs a) {
     f32x4 acc[kMT];
 #pragma unroll
     for (int mt = 0; mt < kMT; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const float* wrow = W2 + (int64_t)(nt * 16 + r16) * L1;
-    for (int ks = 0; ks < L1 / 32; ++ks) {
+    const int n = nt * 16 + r16;
+    const bool nok = !RAGGED || n < L2;  // ragged: a column at or past L2 has zero weights and a zero bias
+    const float* wrow = W2 + (int64_t)(nok ? n : 0) * L1;
+    for (int ks = 0; ks < L1p / 32; ++ks) {
       const int k = ks * 32 + 8 * g;
-      const bf16x8 bfrag = cvt8(ld4(wrow + k), ld4(wrow + k + 4));
+      bf16x8 bfrag;
+      if constexpr (RAGGED) bfrag = ldw8(wrow + k, nok ? L1 - k : 0);
+      else bfrag = cvt8(ld4(wrow + k), ld4(wrow + k + 4));
 #pragma unroll
       for (int mt = 0; mt < kMT; ++mt) acc[mt] = mfma16(ld8(sH1 + (mt * 16 + r16) * H1S + k), bfrag, acc[mt]);
     }
-    const int n = nt * 16 + r16;
-    const float bias = b2[n];
+    const float bias = nok ? b2[n] : 0.f;
 #pragma unroll
     for (int mt = 0; mt < kMT; ++mt) {
       bf16x4 t4;
@@ -304,10 +366,14 @@ __global__ __launch_bounds__(kThreads) void mlp_general_head_kernel(GenArgs a) {
   if (wv < kMT) {
     const int mt = wv;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int ks = 0; ks < L2 / 32; ++ks) {
+    for (int ks = 0; ks < L2p / 32; ++ks) {
       const int k = ks * 32 + 8 * g;
       bf16x8 bfrag = zero8();
-      if (r16 < kNC) bfrag = cvt8(ld4(W3 + r16 * L2 + k), ld4(W3 + r16 * L2 + k + 4));
+      if constexpr (RAGGED) {
+        if (r16 < kNC) bfrag = ldw8(W3 + r16 * L2 + k, L2 - k);
+      } else {
+        if (r16 < kNC) bfrag = cvt8(ld4(W3 + r16 * L2 + k), ld4(W3 + r16 * L2 + k + 4));
+      }
       acc = mfma16(ld8(sH2 + (mt * 16 + r16) * H2S + k), bfrag, acc);
     }
     if (r16 < kNC) {
@@ -399,7 +465,7 @@ __global__ __launch_bounds__(kThreads) void mlp_general_head_kernel(GenArgs a) {
 #pragma unroll
       for (int jj = 0; jj < 8; ++jj) {
         const int j = 8 * g + jj;
-        if (j < kNC) bfrag[jj] = (__bf16)W3[j * L2 + n];
+        if (j < kNC && (!RAGGED || n < L2)) bfrag[jj] = (__bf16)W3[j * L2 + n];
       }
 #pragma unroll
       for (int mt = 0; mt < kMT; ++mt) {
@@ -424,11 +490,18 @@ __global__ __launch_bounds__(kThreads) void mlp_general_head_kernel(GenArgs a) {
       f32x4 acc[kMT];
 #pragma unroll
       for (int mt = 0; mt < kMT; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-      for (int ks = 0; ks < L2 / 32; ++ks) {
+      for (int ks = 0; ks < L2p / 32; ++ks) {
         const int k = ks * 32 + 8 * g;
         bf16x8 bfrag;
+        if constexpr (RAGGED) {
+          bfrag = zero8();
 #pragma unroll
-        for (int jj = 0; jj < 8; ++jj) bfrag[jj] = (__bf16)W2[(int64_t)(k + jj) * L1 + m];
+          for (int jj = 0; jj < 8; ++jj)
+            if (m < L1 && k + jj < L2) bfrag[jj] = (__bf16)W2[(int64_t)(k + jj) * L1 + m];
+        } else {
+#pragma unroll
+          for (int jj = 0; jj < 8; ++jj) bfrag[jj] = (__bf16)W2[(int64_t)(k + jj) * L1 + m];
+        }
 #pragma unroll
         for (int mt = 0; mt < kMT; ++mt) acc[mt] = mfma16(ld8(sH2 + (mt * 16 + r16) * H2S + k), bfrag, acc[mt]);
       }
@@ -450,8 +523,10 @@ __global__ __launch_bounds__(kThreads) void mlp_general_head_kernel(GenArgs a) {
 // Launch 3: one wave per (gradient tile, batch slice).  D[i][j] = sum_b A^T[i][b] B^T[j][b]
 // over the slice's K steps; lane (r16, g) holds D[4 g + i][r16].
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kPThreads) void mlp_general_param_kernel(MLPWideArgs w) {
-  const int L1 = w.step.L1, L2 = w.step.L2, TN1 = L1 / 16, TN2 = L2 / 16;
+template <bool RAGGED>
+__device__ __forceinline__ void param_tile(const MLPWideArgs w, int align) {
+  const int L1 = w.step.L1, L2 = w.step.L2;
+  const int L1p = RAGGED ? pad32(L1) : L1, L2p = RAGGED ? pad32(L2) : L2, TN1 = L1p / 16, TN2 = L2p / 16;
   const int NT_W1 = kTiles * TN1, NT_W2 = TN2 * TN1, NT_W3 = TN2, NT_B = TN1 + TN2 + 1;
   const int lane = threadIdx.x & 63, r16 = lane & 15, g = lane >> 4;
   const int task = blockIdx.x * (kPThreads / 64) + (threadIdx.x >> 6);
@@ -460,8 +535,8 @@ __global__ __launch_bounds__(kPThreads) void mlp_general_param_kernel(MLPWideArg
   const int64_t Bp = w.Bp;
   const int nk = (int)(Bp / 32);
   const int ks0 = (int)((int64_t)s * nk / S), ks1 = (int)((int64_t)(s + 1) * nk / S);
-  const GPark pk = gpark(L1, L2, Bp);
-  const GOff o = goff(L1, L2);
+  const GPark pk = gpark(L1p, L2p, Bp);
+  const GOff o = RAGGED ? goff(L1, L2, align) : goff(L1, L2);
   const __bf16* park = reinterpret_cast<const __bf16*>(w.park);
   float* out = w.part + (int64_t)s * w.np_pad;
 
@@ -500,66 +575,100 @@ __global__ __launch_bounds__(kPThreads) void mlp_general_param_kernel(MLPWideArg
     const bf16x8 bfrag = brow ? ld8(brow + k) : ones;
     acc = mfma16(afrag, bfrag, acc);
   }
+  // ragged: whole tiles were computed over the padded extents; only what lies inside the true
+  // [L1][784], [L2][L1], [10][L2], [L1], [L2] is stored -- an edge tile's other elements would
+  // land in the next row or the next tensor's gradient
   if (kind == 0) {
-    *reinterpret_cast<F4*>(out + o.W1 + (int64_t)(t1 * 16 + r16) * kD + t0 * 16 + 4 * g) =
-        F4{{acc[0], acc[1], acc[2], acc[3]}};
+    if (!RAGGED || t1 * 16 + r16 < L1)
+      *reinterpret_cast<F4*>(out + o.W1 + (int64_t)(t1 * 16 + r16) * kD + t0 * 16 + 4 * g) =
+          F4{{acc[0], acc[1], acc[2], acc[3]}};
   } else if (kind == 1) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) out[o.W2 + (int64_t)(t0 * 16 + 4 * g + i) * L1 + t1 * 16 + r16] = acc[i];
+    for (int i = 0; i < 4; ++i)
+      if (!RAGGED || (t0 * 16 + 4 * g + i < L2 && t1 * 16 + r16 < L1))
+        out[o.W2 + (int64_t)(t0 * 16 + 4 * g + i) * L1 + t1 * 16 + r16] = acc[i];
   } else if (kind == 2) {
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      if (4 * g + i < kNC) out[o.W3 + (int64_t)(4 * g + i) * L2 + t0 * 16 + r16] = acc[i];
+      if (4 * g + i < kNC && (!RAGGED || t0 * 16 + r16 < L2)) out[o.W3 + (int64_t)(4 * g + i) * L2 + t0 * 16 + r16] = acc[i];
   } else if (r16 == 0) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int e = 4 * g + i;
-      if (t0 < TN1) out[o.B1 + t0 * 16 + e] = acc[i];
-      else if (t0 < TN1 + TN2) out[o.B2 + (t0 - TN1) * 16 + e] = acc[i];
-      else if (e < kNC) out[o.B3 + e] = acc[i];
+      if (t0 < TN1) {
+        if (!RAGGED || t0 * 16 + e < L1) out[o.B1 + t0 * 16 + e] = acc[i];
+      } else if (t0 < TN1 + TN2) {
+        if (!RAGGED || (t0 - TN1) * 16 + e < L2) out[o.B2 + (t0 - TN1) * 16 + e] = acc[i];
+      } else if (e < kNC) {
+        out[o.B3 + e] = acc[i];
+      }
+    }
+    if (RAGGED && g == 0 && t0 == TN1 + TN2) {
+      // the words between the tensors of an aligned arena (up to 3 behind b1, W2, b2, W3; none
+      // where align is 1): a zero gradient in every slice, whatever the workspace held before
+      auto zero = [out](int64_t b, int64_t e) { for (; b < e; ++b) out[b] = 0.f; };
+      zero(o.B1 + L1, o.W2);
+      zero(o.W2 + (int64_t)L2 * L1, o.B2);
+      zero(o.B2 + L2, o.W3);
+      zero(o.W3 + (int64_t)kNC * L2, o.B3);
     }
   }
 }
 
+// The ragged instances where a width is no multiple of 32; the others run the instruction
+// streams they always ran.  Layer 1 looks at L1 alone (96/40: its aligned instance, a ragged head).
+// the aligned instance keeps its one argument (and with it its instruction stream)
+__global__ __launch_bounds__(kPThreads) void mlp_general_param_kernel(MLPWideArgs w) { param_tile<false>(w, 1); }
+__global__ __launch_bounds__(kPThreads) void mlp_general_param_ragged_kernel(MLPWideArgs w, int align) {
+  param_tile<true>(w, align);
+}
+
+template <bool TRAIN, bool U8>
+void launch_forward_u8(const GenArgs& g, int nslab, int ncb, hipStream_t stream) {
+  if (g.L1 % 32) hipLaunchKernelGGL((mlp_general_l1_kernel<U8, true>), dim3(nslab, ncb), dim3(kThreads), 0, stream, g);
+  else hipLaunchKernelGGL((mlp_general_l1_kernel<U8, false>), dim3(nslab, ncb), dim3(kThreads), 0, stream, g);
+  if (g.L1 % 32 || g.L2 % 32)
+    hipLaunchKernelGGL((mlp_general_head_kernel<TRAIN, U8, true>), dim3(nslab), dim3(kThreads), 0, stream, g);
+  else hipLaunchKernelGGL((mlp_general_head_kernel<TRAIN, U8, false>), dim3(nslab), dim3(kThreads), 0, stream, g);
+}
+
 template <bool TRAIN>
 void launch_forward(const GenArgs& g, int nslab, int ncb, hipStream_t stream) {
-  if (g.x_u8) {
-    hipLaunchKernelGGL((mlp_general_l1_kernel<true>), dim3(nslab, ncb), dim3(kThreads), 0, stream, g);
-    hipLaunchKernelGGL((mlp_general_head_kernel<TRAIN, true>), dim3(nslab), dim3(kThreads), 0, stream, g);
-  } else {
-    hipLaunchKernelGGL((mlp_general_l1_kernel<false>), dim3(nslab, ncb), dim3(kThreads), 0, stream, g);
-    hipLaunchKernelGGL((mlp_general_head_kernel<TRAIN, false>), dim3(nslab), dim3(kThreads), 0, stream, g);
-  }
+  if (g.x_u8) launch_forward_u8<TRAIN, true>(g, nslab, ncb, stream);
+  else launch_forward_u8<TRAIN, false>(g, nslab, ncb, stream);
 }
 
 }  // namespace
 
 bool mlp_general_supported(int L1, int L2) { return mlp_general_widths_ok(L1, L2) && !mlp_supported(L1, L2); }
 
+int64_t mlp_general_param_count(int L1, int L2, int arena_align) { return goff(L1, L2, arena_align).NP; }
+
 MLPGeneralLayout mlp_general_layout(int L1, int L2, int B) {
   MLPGeneralLayout lay{};
+  const int L1p = pad32(L1), L2p = pad32(L2);  // the workspace keeps the padded extents
   lay.nslab = (B + kBC - 1) / kBC;
   lay.ncb = (L1 + kCB - 1) / kCB;
   lay.Bp = (int64_t)lay.nslab * kBC;
-  lay.np_pad = (goff(L1, L2).NP + 3) / 4 * 4;
+  lay.np_pad = (goff(L1, L2, 4).NP + 3) / 4 * 4;  // room for either arena packing
   // slices: tiles x slices about the chip's wave slots, whole 32-row K steps each (the wide rule)
-  const int ntasks = gtasks(L1, L2), nk = (int)(lay.Bp / 32);
+  const int ntasks = gtasks(L1p, L2p), nk = (int)(lay.Bp / 32);
   int S = (kMLPWideWaveSlots + ntasks - 1) / ntasks;
   if (S > kMLPWideMaxSlices) S = kMLPWideMaxSlices;
   if (S > nk) S = nk;
   lay.slices = S < 1 ? 1 : S;
-  const GPark pk = gpark(L1, L2, lay.Bp);
+  const GPark pk = gpark(L1p, L2p, lay.Bp);
   lay.h1 = pk.h1;
   lay.park_elems = pk.total;
   lay.part_elems = (int64_t)lay.slices * lay.np_pad + (int64_t)lay.nslab * 4;
-  lay.h1_elems = lay.Bp * L1;
+  lay.h1_elems = lay.Bp * L1p;
   return lay;
 }
 
-int launch_mlp_general_step(const MLPWideArgs& w_in, hipStream_t stream) {
+int launch_mlp_general_step(const MLPWideArgs& w_in, hipStream_t stream, int arena_align) {
   MLPWideArgs w = w_in;
   const MLPStepArgs& a = w.step;
-  if (!mlp_general_widths_ok(a.L1, a.L2)) return -1;
+  if (!mlp_general_widths_ok(a.L1, a.L2) || (arena_align != 1 && arena_align != 4)) return -1;
   if (a.B < 1 || a.B > kMLPWideMaxB) return -2;
   if (a.x_u8 && !mlp_input_affine_ok(a.x_scale, a.x_shift)) return -13;
   if (w.last_rows < 1 || w.last_rows > a.B || (!a.x_u8 && w.last_rows != a.B)) return -15;
@@ -580,18 +689,25 @@ int launch_mlp_general_step(const MLPWideArgs& w_in, hipStream_t stream) {
   g.Bp = lay.Bp;
   g.hdr = w.hdr;
   g.slab_stats = w.slab_stats;
+  g.align = arena_align;
   launch_forward<true>(g, lay.nslab, lay.ncb, stream);
-  const int per = kPThreads / 64, ntasks = gtasks(a.L1, a.L2);
-  hipLaunchKernelGGL(mlp_general_param_kernel, dim3((ntasks + per - 1) / per, lay.slices), dim3(kPThreads), 0, stream,
-                     w);
-  const int64_t np = goff(a.L1, a.L2).NP;
+  const int per = kPThreads / 64, ntasks = gtasks(pad32(a.L1), pad32(a.L2));
+  const dim3 pgrid((ntasks + per - 1) / per, lay.slices);
+  if (a.L1 % 32 || a.L2 % 32)
+    hipLaunchKernelGGL(mlp_general_param_ragged_kernel, pgrid, dim3(kPThreads), 0, stream, w, arena_align);
+  else hipLaunchKernelGGL(mlp_general_param_kernel, pgrid, dim3(kPThreads), 0, stream, w);
+  // the apply is one thread per float of the arena: no alignment of a segment or of the total
+  // enters it (the ragged parameter launch wrote zeros to the pads of an aligned arena in every
+  // slice, so they see a zero gradient and stay zero)
+  const int64_t np = goff(a.L1, a.L2, arena_align).NP;
   hipLaunchKernelGGL(mlp_wide_apply_kernel, dim3((unsigned)((np + kApplyThreads - 1) / kApplyThreads)),
                      dim3(kApplyThreads), 0, stream, w, np, lay.slices, lay.nslab);
   return 0;
 }
 
-int launch_mlp_general_eval(const MLPEvalArgs& a, uint16_t* h1, int64_t h1_elems, hipStream_t stream) {
-  if (!mlp_general_widths_ok(a.L1, a.L2)) return -1;
+int launch_mlp_general_eval(const MLPEvalArgs& a, uint16_t* h1, int64_t h1_elems, hipStream_t stream,
+                            int arena_align) {
+  if (!mlp_general_widths_ok(a.L1, a.L2) || (arena_align != 1 && arena_align != 4)) return -1;
   if (a.x_u8 && !mlp_input_affine_ok(a.x_scale, a.x_shift)) return -13;
   if (a.B <= 0) return 0;
   const MLPGeneralLayout lay = mlp_general_layout(a.L1, a.L2, a.B);
@@ -604,6 +720,7 @@ int launch_mlp_general_eval(const MLPEvalArgs& a, uint16_t* h1, int64_t h1_elems
   g.h1 = reinterpret_cast<__bf16*>(h1);
   g.Bp = lay.Bp;
   g.logits = a.logits; g.out = a.out; g.partials = a.partials;
+  g.align = arena_align;
   launch_forward<false>(g, lay.nslab, lay.ncb, stream);
   return 0;
 }

@@ -39,8 +39,8 @@ sum with Adam / AdamW -- through the same engine (``FusedMLPEngine(batch_size=51
 stats ring, short last batch and LR ring as below 256).  Clipping, accumulation and SGD above
 256 rows step through the loader-fed branch of ``train_batch``: ``mlp_train_step`` on the same
 wide kernels, then the allreduce, clip and optimizer launches that branch always had.
-Layer widths outside the ten table pairs -- any multiples of 32 up to 512, e.g. 256/256 or
-96/160 (``ops.fused_mlp.mlp_general``) -- run the general-width kernels of
+Layer widths outside the ten table pairs -- every width from 1 to 512 but the odd multiples of 16, e.g. 256/256, 96/160 or
+the classic 300/100 (``ops.fused_mlp.mlp_general``) -- run the general-width kernels of
 csrc/mlp_step_general.hip through the same engine route at EVERY batch size; clipping,
 accumulation, SGD and a scheduled rate at world size > 1 then take the loader-fed branch at
 every batch size, and ``eval_epoch`` reaches the general forward through ``mlp_eval``.
@@ -280,9 +280,15 @@ class FusedMNISTStep:
         self.sgd = self.opt_kind == "sgd"
         acc = trainer.accelerator_backend
         arena = acc.arena
-        self.np = fused_mlp.mlp_param_count(L1, L2)
-        if arena is None or arena.numel < self.np or arena.params[0] is not model.layer_1.weight:
+        # the kernels' arena is W1 b1 W2 b2 W3 b3 back to back; the Trainer's arena starts every
+        # tensor on a multiple of 4 floats, which is the same thing unless a width is no multiple
+        # of 4 -- the general-width kernels then read that packing as it is (arena_align 4)
+        starts = [o for o, _ in arena.offsets[:6]] if arena is not None else []
+        self.arena_align = next((al for al in (1, 4) if (al == 1 or fused_mlp.mlp_general(L1, L2))
+                                 and starts == list(fused_mlp.mlp_arena_offsets(L1, L2, al)[:6])), None)
+        if self.arena_align is None or arena.params[0] is not model.layer_1.weight:
             raise RuntimeError("parameters are not in the expected arena layout")
+        self.np = fused_mlp.mlp_param_count(L1, L2, self.arena_align)
         self.model, self.trainer, self.opt, self.acc, self.arena = model, trainer, opt, acc, arena
         self.L1, self.L2 = L1, L2
         self.gs = opt._rla_groups[0]
@@ -351,7 +357,8 @@ class FusedMNISTStep:
                              weight_decay=g["weight_decay"], device=self.dev, world_size=self.world,
                              rank=self.trainer.global_rank, allreduce=self._allreduce, buffers=bufs,
                              stats_ring=ENGINE_STATS_RING, dp_context=dp_ctx, dp_rearm=rearm,
-                             clip_norm=self.clip_norm, accumulate=self.accumulate, lr_ring=self.lr_ring, **hyper)
+                             clip_norm=self.clip_norm, accumulate=self.accumulate, lr_ring=self.lr_ring,
+                             arena_align=self.arena_align, **hyper)
         eng.set_step(self.gs.step)
         # LR schedulers update one device scalar (ring mode: this object's ring, which set_lr
         # below fills so that the engine's host picture of it is true)
@@ -546,7 +553,7 @@ class FusedMNISTStep:
             y = y.to(self.dev, non_blocking=True).long().contiguous()
             stats = torch.zeros(1, 4, device=self.dev)  # this batch's own row
             fused_mlp.mlp_train_step(p, gr, B=x.size(0), labels=y, x_f32=x, L1=self.L1, L2=self.L2,
-                                     stats=stats, accumulate_grad=micro > 0, apply_adam=False,
+                                     arena_align=self.arena_align, stats=stats, accumulate_grad=micro > 0, apply_adam=False,
                                      advance_step=closing, lr=self.lr_val, weight_decay=g["weight_decay"],
                                      lr_tensor=self._lr_one(), counters=self.counters)
             if closing:
@@ -583,7 +590,7 @@ class FusedMNISTStep:
         gr = self.arena.grad[: self.np]
         # the loader-fed kernel applies Adam / AdamW itself; SGD follows it as its own launch
         fused = self.world == 1 and self.clip_norm is None and not self.sgd
-        kw = dict(L1=self.L1, L2=self.L2, stats=self.stats, apply_adam=fused, advance_step=True, lr=self.lr_val,
+        kw = dict(L1=self.L1, L2=self.L2, arena_align=self.arena_align, stats=self.stats, apply_adam=fused, advance_step=True, lr=self.lr_val,
                   weight_decay=g["weight_decay"], lr_tensor=self._lr_one(), counters=self.counters)
         if not self.sgd:
             kw.update(exp_avg=self.gs.m[: self.np], exp_avg_sq=self.gs.v[: self.np], betas=tuple(g["betas"]),
@@ -800,7 +807,8 @@ class FusedMNISTStep:
         order_dev, nb, last = cached[0], cached[1], cached[4]
         u8, labels = self._resident(images, targets)
         n = nb * B
-        kw = dict(L1=self.L1, L2=self.L2, labels=labels, x_u8=u8, x_scale=x_scale, x_shift=x_shift)
+        kw = dict(L1=self.L1, L2=self.L2, labels=labels, x_u8=u8, x_scale=x_scale, x_shift=x_shift,
+                  arena_align=self.arena_align)
         tot = None
         if n:
             part = torch.empty((n + 31) // 32, 2, device=self.dev)

@@ -7,10 +7,12 @@ reference with identical semantics (also the oracle for the GPU tests).
 
 Layer widths: the ten ``SUPPORTED`` pairs run the table kernels (``csrc/mlp_kernels.hip``,
 ``csrc/mlp_step3.hip``, above 256 rows ``csrc/mlp_step_wide.hip``).  Every other pair of
-multiples of 32 in 32 .. 512 (``mlp_general``) runs the general-width kernels of
+widths in 1 .. 512 but the odd multiples of 16 (``mlp_general``) runs the general-width kernels of
 ``csrc/mlp_step_general.hip`` at every batch size 1 .. 4096 -- layer 1 split over 64-row slabs
 and 64-column blocks, a head per slab, gradient tiles split over the batch, a fixed-order slice
-sum -- and its forward-only instance in ``mlp_eval``.  Anything else has no fused kernel.
+sum -- and its forward-only instance in ``mlp_eval``; widths that are no multiples of 32 run
+ragged instances of the same kernels (compute over the widths rounded up to 32 with exact zeros
+in the pad, the arenas at the true widths).  Anything else has no fused kernel.
 
 Parameter arena layout (== ``nn.Linear`` state_dict order of
 ``layer_1``/``layer_2``/``layer_3``):  W1[L1,784] b1[L1] W2[L2,L1] b2[L2] W3[10,L2] b3[10].
@@ -33,8 +35,23 @@ SUPPORTED = {(32, 32), (32, 64), (32, 128), (32, 256), (64, 64), (64, 128), (64,
              (128, 64), (128, 128), (128, 256)}
 
 
-def mlp_param_count(L1: int, L2: int) -> int:
-    return L1 * IN_FEATURES + L1 + L2 * L1 + L2 + NUM_CLASSES * L2 + NUM_CLASSES
+def mlp_arena_offsets(L1: int, L2: int, arena_align: int = 1) -> Tuple[int, ...]:
+    """Element offsets of W1 b1 W2 b2 W3 b3 in the flat arena, then its length.  ``arena_align``
+    1: back to back; 4: every tensor starts on a multiple of 4 floats, as ``ParamArena`` packs a
+    module (the general-width kernels read both; the two agree where L1 and L2 are multiples of
+    4).  The arena ends with b3 either way."""
+    if arena_align not in (1, 4):
+        raise ValueError(f"arena_align must be 1 or 4, got {arena_align!r}")
+    offs, off = [], 0
+    for n in (L1 * IN_FEATURES, L1, L2 * L1, L2, NUM_CLASSES * L2, NUM_CLASSES):
+        off = -(-off // arena_align) * arena_align
+        offs.append(off)
+        off += n
+    return (*offs, off)
+
+
+def mlp_param_count(L1: int, L2: int, arena_align: int = 1) -> int:
+    return mlp_arena_offsets(L1, L2, arena_align)[-1]
 
 
 GENERAL_MAX_WIDTH = 512   # the general head's LDS plan (csrc/mlp_step_general.hip)
@@ -42,12 +59,14 @@ GENERAL_COL_BLOCK = 64    # layer-1 columns per workgroup
 
 
 def _general_widths_ok(L1: int, L2: int) -> bool:
-    return all(32 <= int(w) <= GENERAL_MAX_WIDTH and int(w) % 32 == 0 for w in (L1, L2))
+    # odd multiples of 16 (16, 48, 80, ...) have no kernel: 16/64, 48/64 and 64/48 are refused by
+    # contract (tests/test_mlp_general_cpu.py), and the refusal holds for their whole residue class
+    return all(1 <= int(w) <= GENERAL_MAX_WIDTH and int(w) % 32 != 16 for w in (L1, L2))
 
 
 def mlp_general(L1: int, L2: int) -> bool:
-    """Whether ``(L1, L2)`` is served by the general-width kernels alone: multiples of 32 in
-    32 .. 512 outside the ``SUPPORTED`` table."""
+    """Whether ``(L1, L2)`` is served by the general-width kernels alone: every width in
+    1 .. 512 outside the ``SUPPORTED`` table, except the odd multiples of 16."""
     return _general_widths_ok(L1, L2) and (int(L1), int(L2)) not in SUPPORTED
 
 
@@ -56,19 +75,16 @@ def mlp_supported(L1: int, L2: int) -> bool:
     return (int(L1), int(L2)) in SUPPORTED or mlp_general(L1, L2)
 
 
-def mlp_unpack(flat: torch.Tensor, L1: int, L2: int) -> Dict[str, torch.Tensor]:
+def mlp_unpack(flat: torch.Tensor, L1: int, L2: int, arena_align: int = 1) -> Dict[str, torch.Tensor]:
     """Views of the arena as nn.Linear tensors (state_dict key order)."""
     shapes = [
         ("layer_1.weight", (L1, IN_FEATURES)), ("layer_1.bias", (L1,)),
         ("layer_2.weight", (L2, L1)), ("layer_2.bias", (L2,)),
         ("layer_3.weight", (NUM_CLASSES, L2)), ("layer_3.bias", (NUM_CLASSES,)),
     ]
-    out, off = {}, 0
-    for name, shp in shapes:
-        n = math.prod(shp)
-        out[name] = flat[off:off + n].view(shp)
-        off += n
-    assert off == flat.numel(), "arena size mismatch"
+    offs = mlp_arena_offsets(L1, L2, arena_align)
+    out = {name: flat[off:off + math.prod(shp)].view(shp) for (name, shp), off in zip(shapes, offs)}
+    assert offs[-1] == flat.numel(), "arena size mismatch"
     return out
 
 
@@ -209,6 +225,7 @@ def mlp_train_step(
     lr_mask: int = 0,
     workspace: Optional[Dict[str, torch.Tensor]] = None,
     route: str = "auto",
+    arena_align: int = 1,
 ) -> None:
     """One training micro-step of the MNIST MLP over a flat parameter arena.
 
@@ -236,7 +253,8 @@ def mlp_train_step(
     with the wide step's contract (``last_rows``, ``lr_mask``, bitwise repeatable), on the
     workspace of ``mlp_general_buffers``.  ``route="general"`` forces those kernels on a table
     pair (tests and measurements); ``"auto"`` never does.  Widths with no kernel raise a
-    ValueError before a launch.
+    ValueError before a launch.  ``arena_align`` (general pairs and the fp32 reference): how
+    ``params`` / ``grads`` / the Adam state pack the six tensors (``mlp_arena_offsets``).
     """
     if route not in ("auto", "general"):
         raise ValueError(f"mlp_train_step: route must be 'auto' or 'general', got {route!r}")
@@ -267,7 +285,8 @@ def mlp_train_step(
             require().mlp_train_step(*args)
             return
         ws = workspace if workspace is not None else _wide_workspace(L1, L2, B, params.device, general)
-        require().mlp_train_step(*args, last_rows, lr_mask, ws["park"], ws["part"], ws["hdr"], general)
+        require().mlp_train_step(*args, last_rows, lr_mask, ws["park"], ws["part"], ws["hdr"], general,
+                                 int(arena_align))
         return
     # ---- fp32 reference ----
     cursor = int(counters[1].item()) if (counters is not None and x_u8 is not None) else 0
@@ -276,7 +295,7 @@ def mlp_train_step(
     x, y = _gather_batch(x_u8, x_f32, labels, order, cursor, B, index=index, x_scale=x_scale, x_shift=x_shift)
     with torch.enable_grad():
         leaf = params.detach().clone().requires_grad_(True)
-        p = mlp_unpack(leaf, L1, L2)
+        p = mlp_unpack(leaf, L1, L2, arena_align)
         logits = _reference_forward(p, x)
         logp = F.log_softmax(logits, dim=1)
         loss = F.nll_loss(logp, y)
@@ -350,12 +369,18 @@ def mlp_general_layout(L1: int, L2: int, B: int) -> Dict[str, int]:
     (``_C.mlp_general_layout``; the binding checks the sizes against its own): the wide step's
     six parked operands at the same offsets, then ``h1`` -- H1 ``[Bp][L1]`` row-major, which
     layer 1 hands to the head.  ``ncb``: 64-column blocks of layer 1.  ``h1_elems``: all the
-    forward (``mlp_eval``) needs."""
+    forward (``mlp_eval``) needs.  Widths that are no multiples of 32 park ``[feature][Bp]`` with
+    the feature counts rounded up to 32 (the pad rows hold zeros)."""
     L1, L2, B = int(L1), int(L2), int(B)
-    lay = mlp_wide_layout(L1, L2, B)  # slabs, slices and the six offsets: the same rules
+    # the workspace keeps the widths rounded up to 32 (what the MFMA core touches); the slice
+    # partials hold the arena at its true widths, with room for either packing
+    L1p, L2p = -(-L1 // 32) * 32, -(-L2 // 32) * 32
+    lay = mlp_wide_layout(L1p, L2p, B)  # slabs, slices and the six offsets: the same rules
+    lay["np_pad"] = (mlp_param_count(L1, L2, 4) + 3) // 4 * 4
+    lay["part_elems"] = lay["slices"] * lay["np_pad"] + lay["nslab"] * 4
     lay["ncb"] = (L1 + GENERAL_COL_BLOCK - 1) // GENERAL_COL_BLOCK
     lay["h1"] = lay["park_elems"]
-    lay["h1_elems"] = lay["Bp"] * L1
+    lay["h1_elems"] = lay["Bp"] * L1p
     lay["park_elems"] += lay["h1_elems"]
     return lay
 
@@ -716,6 +741,7 @@ def mlp_eval(
     logits: Optional[torch.Tensor] = None,
     x_scale: float = X_SCALE_DEFAULT,
     x_shift: float = 0.0,
+    arena_align: int = 1,
 ) -> None:
     """Forward only.  ``out`` [2]: out[0] += sum NLL, out[1] += #correct.  ``out``
     [ceil(B/32), 2]: per-32-row-chunk (sum NLL, #correct), overwritten -- the GPU
@@ -723,7 +749,8 @@ def mlp_eval(
     deterministic.  Optional log-probs into ``logits``.  u8 mode reads a pixel as
     ``fmaf(u8, x_scale, x_shift)`` (``input_affine``).  A general pair (``mlp_general``) runs the
     forward-only instance of csrc/mlp_step_general.hip: one workgroup per 64 rows (two chunks),
-    H1 handed from its first launch to its second through a workspace allocated here."""
+    H1 handed from its first launch to its second through a workspace allocated here;
+    ``arena_align`` as in ``mlp_train_step``."""
     if x_u8 is not None:
         x_scale, x_shift = check_input_affine(x_scale, x_shift)
     if use_native(params):
@@ -731,11 +758,11 @@ def mlp_eval(
         if mlp_general(L1, L2) and int(B) > 0:
             h1 = torch.empty(mlp_general_layout(L1, L2, B)["h1_elems"], dtype=torch.bfloat16, device=params.device)
         require().mlp_eval(x_u8, x_f32, labels, index, int(B), int(L1), int(L2), params, logits, out,
-                           float(x_scale), float(x_shift), h1)
+                           float(x_scale), float(x_shift), h1, int(arena_align))
         return
     x, y = _gather_batch(x_u8, x_f32, labels, None, 0, B, index=index, x_scale=x_scale, x_shift=x_shift)
     with torch.no_grad():
-        logp = F.log_softmax(_reference_forward(mlp_unpack(params, L1, L2), x), dim=1)
+        logp = F.log_softmax(_reference_forward(mlp_unpack(params, L1, L2, arena_align), x), dim=1)
         nll = F.nll_loss(logp, y, reduction="none")
         hit = (logp.argmax(dim=1) == y).float()
         if out.dim() == 2:

@@ -24,7 +24,7 @@ re-designed for MI355X instead of translating PL's DDP loop:
   adds the allreduce and the arena Adam.  ``clip_norm``, ``accumulate`` > 1, SGD and
   ``dp_context`` stop at 256 rows (ValueError); ``capture`` / ``run``, the stats ring,
   ``set_step``, ``begin_epoch(last_rows=...)`` and the LR ring work as below 256;
-  layer widths outside the table (``ops.fused_mlp.mlp_general``: multiples of 32 up to 512):
+  layer widths outside the table (``ops.fused_mlp.mlp_general``: every width from 1 to 512 but the odd multiples of 16):
   the same self-contained route at EVERY batch size, on the general-width kernels of
   csrc/mlp_step_general.hip (four launches per step) -- with the same refusals, and none of
   the table kernels' shadow or rings;
@@ -147,6 +147,7 @@ class FusedMLPEngine:
         nesterov: bool = False,
         lr_ring: int = 0,
         route: str = "auto",
+        arena_align: int = 1,
     ):
         """``buffers``: optional external fp32 tensors ``params`` / ``grads`` /
         ``exp_avg`` / ``exp_avg_sq`` (e.g. views of a Trainer's parameter arena,
@@ -189,7 +190,10 @@ class FusedMLPEngine:
         step runs its schedule instances; the one-launch in-kernel exchange has none, so a
         ``dp_context`` engine then steps as two launches (one warning).
         ``route``: ``mlp_train_step``'s -- "general" runs the general-width kernels on a table
-        pair too (tests and measurements); "auto" never does."""
+        pair too (tests and measurements); "auto" never does.
+        ``arena_align``: how the four arenas pack the six tensors (``ops.fused_mlp.mlp_arena_offsets``):
+        1 back to back, 4 (general widths only) each on a multiple of 4 floats, as a Trainer's
+        ``ParamArena`` packs the module when a width is no multiple of 4."""
         if route not in ("auto", "general"):
             raise ValueError(f"route must be 'auto' or 'general', got {route!r}")
         if isinstance(lr_ring, bool) or int(lr_ring) != lr_ring or int(lr_ring) < 0 or int(lr_ring) == 1 \
@@ -242,6 +246,9 @@ class FusedMLPEngine:
                     raise ValueError(f"fused MLP engine: {what} is served up to batch size 256 only (got "
                                      f"{batch_size}); above it the engine runs Adam / AdamW on the wide step")
         self.L1, self.L2, self.B = int(layer_1), int(layer_2), int(batch_size)
+        self.arena_align = int(arena_align)
+        if self.arena_align != 1 and not self.general:
+            raise ValueError("arena_align != 1 belongs to the general-width step")
         self.lr, self.betas, self.eps, self.wd = float(lr), tuple(betas), float(eps), float(weight_decay)
         self.optimizer = optimizer
         self.sgd = optimizer == "sgd"
@@ -260,7 +267,7 @@ class FusedMLPEngine:
             self.dp_ctx = ctx
         self._dp_rearm = dp_rearm
         self._owner_masks = None
-        n = fused_mlp.mlp_param_count(self.L1, self.L2)
+        n = fused_mlp.mlp_param_count(self.L1, self.L2, self.arena_align)
         if buffers is not None:
             names = ("params", "grads", "momentum_buffer") if self.sgd else ("params", "grads", "exp_avg", "exp_avg_sq")
             for k in names:
@@ -272,6 +279,10 @@ class FusedMLPEngine:
         else:
             if init_params is None:
                 init_params = fused_mlp.init_mlp_params(self.L1, self.L2, torch.Generator().manual_seed(seed))
+                if self.arena_align != 1:  # the same draws, spread over the aligned arena
+                    dense, init_params = init_params, torch.zeros(n)
+                    for k, t in self._unpack(init_params).items():
+                        t.copy_(fused_mlp.mlp_unpack(dense, self.L1, self.L2)[k])
             self.params = init_params.detach().to(self.device, torch.float32).contiguous().clone()
             # padded to 4 floats: the xGMI one-shot allreduce moves 16-byte vectors
             self._grads_padded = torch.zeros((n + 3) // 4 * 4, device=self.device)
@@ -924,7 +935,7 @@ class FusedMLPEngine:
             exp_avg_sq=self.exp_avg_sq, stats=self.stats, apply_adam=fused, lr=self.lr, betas=self.betas,
             eps=self.eps, weight_decay=self.wd, lr_tensor=self.lr_tensor, adamw=self.adamw, x_scale=self.x_scale,
             x_shift=self.x_shift, last_rows=self.last_rows, lr_mask=self.lr_mask, workspace=self.wide_ws,
-            route="general" if self.general else "auto")
+            route="general" if self.general else "auto", arena_align=self.arena_align)
         if not fused:
             if self.allreduce is not None:
                 self.allreduce(self.comm_buffer)
@@ -956,7 +967,7 @@ class FusedMLPEngine:
             exp_avg_sq=self.exp_avg_sq, stats=self._head_row if acc else self.stats, accumulate_grad=micro > 0,
             apply_adam=fused, advance_step=closing, lr=self.lr,
             betas=self.betas, eps=self.eps, weight_decay=self.wd, lr_tensor=lr_now, adamw=self.adamw,
-            x_scale=self.x_scale, x_shift=self.x_shift, last_rows=self.last_rows,
+            x_scale=self.x_scale, x_shift=self.x_shift, last_rows=self.last_rows, arena_align=self.arena_align,
         )
         c[2] = cursor
         c[3] = int(c[3]) ^ 1
@@ -1137,8 +1148,11 @@ class FusedMLPEngine:
         rows = [(t - 1 - i) % ring for i in range(min(n, t, ring))][::-1]
         return self.stats[rows].cpu() if rows else torch.zeros(0, 4)
 
+    def _unpack(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
+        return fused_mlp.mlp_unpack(flat, self.L1, self.L2, self.arena_align)
+
     def state_dict(self) -> Dict[str, torch.Tensor]:
-        return {k: v.detach().cpu().clone() for k, v in fused_mlp.mlp_unpack(self.params, self.L1, self.L2).items()}
+        return {k: v.detach().cpu().clone() for k, v in self._unpack(self.params).items()}
 
     def optimizer_state_dict(self) -> Dict:
         """torch.optim.Adam / AdamW / SGD .state_dict() layout (Lightning checkpoint
@@ -1146,10 +1160,10 @@ class FusedMLPEngine:
         if self.sgd:
             # torch's SGD state: a momentum_buffer per parameter once a step has run (none
             # without momentum), and no step count
-            names = list(fused_mlp.mlp_unpack(self.params, self.L1, self.L2))
+            names = list(self._unpack(self.params))
             state = {}
             if self.momentum != 0.0 and self.optimizer_steps > 0:
-                buf = fused_mlp.mlp_unpack(self.exp_avg, self.L1, self.L2)
+                buf = self._unpack(self.exp_avg)
                 state = {i: {"momentum_buffer": buf[k].detach().cpu().clone()} for i, k in enumerate(names)}
             group = {"lr": self.lr, "momentum": self.momentum, "dampening": self.dampening,
                      "weight_decay": self.wd, "nesterov": self.nesterov, "maximize": False, "foreach": None,
@@ -1157,8 +1171,8 @@ class FusedMLPEngine:
             return {"state": state, "param_groups": [group]}
         self.sync_optimizer_state()
         step = float(self.counters[0].item())
-        m = fused_mlp.mlp_unpack(self.exp_avg, self.L1, self.L2)
-        v = fused_mlp.mlp_unpack(self.exp_avg_sq, self.L1, self.L2)
+        m = self._unpack(self.exp_avg)
+        v = self._unpack(self.exp_avg_sq)
         state = {}
         for i, k in enumerate(m):
             state[i] = {"step": torch.tensor(step), "exp_avg": m[k].detach().cpu().clone(),

@@ -9,6 +9,8 @@ Two arms, one JSON line per configuration and round:
                   (``FusedMNISTStep`` with an engine) or "autograd" (the fallback, which is what
                   a tree without the general kernels runs at these widths).  Uses the public
                   Trainer interface only, so the same file times any tree given on PYTHONPATH.
+                  ``--fused-step off`` passes ``Trainer(fused_step=False)``: the autograd path of
+                  this tree, which is the fallback itself wherever a tree has no kernel.
   --arm routes    ``FusedMLPEngine(128, 256, B, route=...)`` in captured graphs of
                   ``--graph-steps`` steps: "general" (the general-width kernels forced on a table
                   pair) against "auto" (B = 32 the one-launch step, 256 the two-launch step, 512
@@ -31,7 +33,7 @@ except ImportError:
 import torch  # noqa: E402
 
 
-def fit_seconds(l1: int, l2: int, B: int, n: int, root: str):
+def fit_seconds(l1: int, l2: int, B: int, n: int, root: str, fused_step=None):
     import ray_lightning_accelerators_amd.lightning as pl
     from ray_lightning_accelerators_amd.models.mnist import MNISTClassifier
 
@@ -39,7 +41,8 @@ def fit_seconds(l1: int, l2: int, B: int, n: int, root: str):
     model = MNISTClassifier({"layer_1": l1, "layer_2": l2, "lr": 1e-3, "batch_size": B})
     model.prepare_data()  # the synthetic dataset is built outside the timed window
     tr = pl.Trainer(default_root_dir=root, gpus=1, max_epochs=1, limit_train_batches=n, limit_val_batches=0,
-                    checkpoint_callback=False, progress_bar_refresh_rate=0, num_sanity_val_steps=0, logger=False)
+                    checkpoint_callback=False, progress_bar_refresh_rate=0, num_sanity_val_steps=0, logger=False,
+                    fused_step=fused_step)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     tr.fit(model)
@@ -52,15 +55,16 @@ def fit_seconds(l1: int, l2: int, B: int, n: int, root: str):
 
 def arm_trainer(args) -> None:
     cfgs = [(w, B) for w in args.widths.split(",") for B in (int(b) for b in args.batches.split(","))]
+    fs = False if args.fused_step == "off" else None
     with tempfile.TemporaryDirectory() as root:
         for w, B in cfgs:  # warm every shape: code objects, allocator
             l1, l2 = (int(v) for v in w.split("-"))
-            fit_seconds(l1, l2, B, args.lo, root)
+            fit_seconds(l1, l2, B, args.lo, root, fs)
         for rnd in range(args.rounds):
             for w, B in cfgs:
                 l1, l2 = (int(v) for v in w.split("-"))
-                lo, route = fit_seconds(l1, l2, B, args.lo, root)
-                hi, route2 = fit_seconds(l1, l2, B, args.hi, root)
+                lo, route = fit_seconds(l1, l2, B, args.lo, root, fs)
+                hi, route2 = fit_seconds(l1, l2, B, args.hi, root, fs)
                 assert route == route2
                 print(json.dumps({"arm": "trainer", "tag": args.tag, "round": rnd, "widths": w, "batch": B,
                                   "route": route, "us_per_step": round((hi - lo) / (args.hi - args.lo) * 1e6, 2),
@@ -110,6 +114,7 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=64)
     ap.add_argument("--graph-steps", type=int, default=8)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--fused-step", choices=["auto", "off"], default="auto")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_general_widths needs a GPU")
