@@ -1015,6 +1015,53 @@ std::vector<Tensor> conv1x1_bn_bwd(Tensor dy1, Tensor wt, Tensor dy2, Tensor yb,
   return {d, part};
 }
 
+// The same for 128 < K <= 512 (csrc/conv1x1_bn_bwd_wide.hip): dy1 [M, K], w [K, N] -- the FORWARD
+// weight as stored, no transposed copy -- dy2 / yb / xb [M, N]; returns (d [M, N] bf16,
+// part [rows, 2, N] fp32 for bn_bwd_finalize, one row per 128-pixel tile)
+std::vector<Tensor> conv1x1_bn_bwd_wide(Tensor dy1, Tensor w, Tensor dy2, Tensor yb, Tensor xb) {
+  TORCH_CHECK(dy1.dim() == 2 && w.dim() == 2 && w.size(0) == dy1.size(1),
+              "conv1x1_bn_bwd_wide: dy1 must be [M, K] and w [K, N]");
+  const int64_t M = dy1.size(0), K = dy1.size(1), N = w.size(1);
+  for (const Tensor* t : {&dy2, &yb, &xb})
+    TORCH_CHECK(t->dim() == 2 && t->size(0) == M && t->size(1) == N,
+                "conv1x1_bn_bwd_wide: dy2 / yb / xb must be [M, N]");
+  const uint16_t* dy1p = bf16_operand(dy1, "conv1x1_bn_bwd_wide: dy1", M * K, dy1);
+  const uint16_t* wp = bf16_operand(w, "conv1x1_bn_bwd_wide: w", K * N, dy1);
+  const uint16_t* dy2p = bf16_operand(dy2, "conv1x1_bn_bwd_wide: dy2", M * N, dy1);
+  const uint16_t* ybp = bf16_operand(yb, "conv1x1_bn_bwd_wide: yb", M * N, dy1);
+  const uint16_t* xbp = bf16_operand(xb, "conv1x1_bn_bwd_wide: xb", M * N, dy1);
+  const rla::Conv1x1BnBwdWideGeom g = rla::conv1x1_bn_bwd_wide_geom(M, K, N);
+  TORCH_CHECK(rla::conv1x1_bn_bwd_wide_ok(g), "conv1x1_bn_bwd_wide: unsupported shape M = ", M, ", K = ", K, ", N = ", N,
+              " (128 < K <= 512, K % 32 == 0, 64 <= N <= 4096, N % 64 == 0)");
+  const at::hip::HIPGuardMasqueradingAsCUDA guard(dy1.device());
+  Tensor d = at::empty({M, N}, dy1.options());
+  Tensor part = at::empty({g.rows, 2, N}, dy1.options().dtype(at::kFloat));
+  TORCH_CHECK(rla::launch_conv1x1_bn_bwd_wide(dy1p, wp, reinterpret_cast<uint16_t*>(d.data_ptr()), g, dy2p, ybp, xbp,
+                                              part.data_ptr<float>(), cur_stream(dy1)),
+              "conv1x1_bn_bwd_wide: launch refused");
+  return {d, part};
+}
+
+// Read-only plan query (tests, docs): what a conv1x1_bn_bwd_wide launch takes under the current
+// plan CU count, and the pixel range [lo, hi) every partial row sums.
+py::dict conv1x1_bn_bwd_wide_plan(int64_t M, int64_t K, int64_t N) {
+  const rla::Conv1x1BnBwdWideGeom g = rla::conv1x1_bn_bwd_wide_geom(M, K, N);
+  TORCH_CHECK(rla::conv1x1_bn_bwd_wide_ok(g), "conv1x1_bn_bwd_wide_plan: unsupported shape");
+  const int64_t tm = rla::conv1x1_bn_bwd_wide_tile_m();
+  std::vector<std::pair<int64_t, int64_t>> ranges;
+  for (int64_t t = 0; t < g.rows; ++t) ranges.emplace_back(t * tm, std::min<int64_t>(M, (t + 1) * tm));
+  py::dict p;
+  p["rows"] = g.rows;
+  p["row_ranges"] = ranges;
+  p["tile_m"] = tm;
+  p["groups"] = g.groups;
+  p["units"] = g.units;
+  p["grid"] = g.grid;
+  p["stages"] = g.stages;
+  p["lds_bytes"] = g.lds_bytes;
+  return p;
+}
+
 // 1x1 conv forward with BatchNorm partial sums: x [M, K] (NHWC rows), w [N, K], both
 // bf16 contiguous; returns (y [M, N] bf16, part [gx, 2, N] fp32 for bn_finalize)
 std::vector<Tensor> conv1x1_stats(Tensor x, Tensor w, optional<Tensor> pre_ss, optional<Tensor> nbt_inc) {
@@ -1551,6 +1598,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv1x1_bn_bwd", &conv1x1_bn_bwd,
         "1x1 conv input gradient fused with the previous BatchNorm's backward partial -> (d, part)");
   m.def("conv1x1_bn_bwd_ok", [](int64_t M, int64_t K, int64_t N) { return rla::conv1x1_bn_bwd_ok(M, (int)K, (int)N); });
+  m.def("conv1x1_bn_bwd_wide", &conv1x1_bn_bwd_wide,
+        "1x1 conv input gradient (128 < K <= 512, forward weight [K, N]) fused with the previous BatchNorm's "
+        "backward partial -> (d, part)");
+  m.def("conv1x1_bn_bwd_wide_ok", [](int64_t M, int64_t K, int64_t N) {
+    return rla::conv1x1_bn_bwd_wide_ok(rla::conv1x1_bn_bwd_wide_geom(M, K, N));
+  });
+  m.def("conv1x1_bn_bwd_wide_plan", &conv1x1_bn_bwd_wide_plan,
+        "rows, row_ranges, tile_m, groups, units, grid, stages, lds_bytes of a conv1x1_bn_bwd_wide launch",
+        py::arg("M"), py::arg("K"), py::arg("N"));
   m.def("conv1x1_stats_ok", [](int64_t M, int64_t K, int64_t N) { return rla::conv1x1_stats_ok(M, (int)K, (int)N); });
   m.def("maxpool_fwd", &maxpool_fwd,
         "NHWC bf16 max pool -> (y, one-byte window argmax); bn_ss: pool bf16(relu(x * scale + shift)) instead",

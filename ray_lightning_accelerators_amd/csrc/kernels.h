@@ -229,6 +229,29 @@ bool conv1x1_bn_bwd_ok(int64_t M, int K, int N);
 void launch_conv1x1_bn_bwd(const uint16_t* dy1, const uint16_t* wt, uint16_t* d, int64_t M, int K, int N,
                            const uint16_t* dy2, const uint16_t* yb, const uint16_t* xb, float* part, int* rows,
                            hipStream_t s);
+// The same contract for 128 < K <= 512 (csrc/conv1x1_bn_bwd_wide.hip): w is the FORWARD weight
+// [K][N] as stored (no transposed copy), the dy1 tile stays in LDS and only the weights stream.
+// part is [rows, 2, N], row t the sums over pixels [128 t, min(M, 128 (t + 1))).
+struct Conv1x1BnBwdWideGeom {
+  int64_t M;
+  int K, N;
+  int rows;       // 128-pixel tiles = partial rows
+  int groups;     // column groups of up to four 64-channel blocks
+  int64_t units;  // rows x groups: the work a workgroup walks a contiguous range of
+  int grid;       // workgroups (a multiple of 8: XCD deal), from plan_cus()
+  int stages;     // weight ring depth of the instance
+  int lds_bytes;  // of the instance
+};
+// The geometry of every launch, predicate and plan query, under the current plan_cus().
+// Arguments that are not positive or leave the index range give the all-zero geometry, which
+// conv1x1_bn_bwd_wide_ok refuses; K % 32 == 0, 128 < K <= 512, N % 64 == 0, 64 <= N <= 4096 are
+// conv1x1_bn_bwd_wide_ok's.
+Conv1x1BnBwdWideGeom conv1x1_bn_bwd_wide_geom(int64_t M, int64_t K, int64_t N);
+bool conv1x1_bn_bwd_wide_ok(const Conv1x1BnBwdWideGeom& g);
+int conv1x1_bn_bwd_wide_tile_m();  // pixels per partial row
+bool launch_conv1x1_bn_bwd_wide(const uint16_t* dy1, const uint16_t* w, uint16_t* d, const Conv1x1BnBwdWideGeom& g,
+                                const uint16_t* dy2, const uint16_t* yb, const uint16_t* xb, float* part,
+                                hipStream_t s);
 
 // ---------------------------------------------------------------------------
 // Fused MNIST-MLP training step (784 -> L1 -> L2 -> 10, ReLU, log_softmax+NLL).

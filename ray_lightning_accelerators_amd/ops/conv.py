@@ -50,7 +50,8 @@ from torch import nn
 # keyed by (op, M, Cin, Cout) for the 1x1 layers, (op, M, Cin, Cout, KH, KW, stride, pad) for KxK
 _choice: Dict[Tuple, str] = {}
 _timings: Dict[Tuple, Dict[str, float]] = {}
-stats = {"fast": 0, "fallback": 0, "bn_dgrad_fused": 0, "bn_dgrad_fused_3x3": 0, "stem": 0, "pre_applied": 0}
+stats = {"fast": 0, "fallback": 0, "bn_dgrad_fused": 0, "bn_dgrad_fused_3x3": 0, "stem": 0, "pre_applied": 0,
+         "bn_dgrad_fused_wide": 0}
 
 
 def _mode() -> str:
@@ -677,6 +678,66 @@ def fuse_bn_dgrad_enabled() -> bool:
     return os.environ.get("RLA_FUSE_BN_DGRAD", "1") == "1"
 
 
+def fuse_bn_dgrad_wide_mode() -> str:
+    """``RLA_FUSE_BN_DGRAD_WIDE``: the same fold for 128 < Cout <= 512 (ResNet-50's layer3 /
+    layer4 identity blocks) on the pixel-stationary kernel (csrc/conv1x1_bn_bwd_wide.hip).
+    ``0``: never; ``1``: wherever the kernel covers the shape; ``auto`` (default): per shape,
+    whichever of the fused kernel and the plain input gradient + BatchNorm's own partial
+    pass is faster (``dgrad_1x1_bn`` in :func:`choices`).  ``RLA_FUSE_BN_DGRAD=0`` turns
+    this route off too."""
+    if not fuse_bn_dgrad_enabled():
+        return "0"
+    m = os.environ.get("RLA_FUSE_BN_DGRAD_WIDE", "auto")
+    return m if m in ("0", "1") else "auto"
+
+
+def _bn_bwd_wide_shape_ok(m: int, k: int, n: int) -> bool:
+    # not cached: the answer follows the planning CU count (see _conv3x3s2_shape_ok)
+    from . import require
+
+    return bool(require().conv1x1_bn_bwd_wide_ok(m, k, n))
+
+
+def conv1x1_bn_bwd_wide_hip(dy: torch.Tensor, wb: torch.Tensor, dres: torch.Tensor, y: torch.Tensor,
+                            x3: torch.Tensor):
+    """Input gradient of a 1x1 / stride-1 conv with 128 < Cout <= 512 fused with the
+    producer BatchNorm's backward partial: ``dy`` [N, Cout, H, W], ``dres`` / ``y`` / ``x3``
+    [N, Cin, H, W], all channels_last bf16; ``wb`` [Cout, Cin] bf16, the forward weight as
+    stored.  Returns (d channels_last = (dy . W + dres) * (y > 0), part [rows, 2, Cin])."""
+    from . import require
+
+    n, _, h, w = dy.shape
+    d2, part = require().conv1x1_bn_bwd_wide(_nhwc2d(dy), wb, _nhwc2d(dres), _nhwc2d(y), _nhwc2d(x3))
+    return _from2d(d2, n, h, w), part
+
+
+def _pick_dgrad_bn_wide(key: Tuple[int, ...], dy: torch.Tensor, x: torch.Tensor, wb: torch.Tensor, fold,
+                        dgrad: Dict[str, Callable]) -> str:
+    """``fused`` or ``split`` for a wide 1x1 input gradient whose input carries a fold (both
+    fixed-order: deterministic mode takes ``fused`` untimed; a graph capture with no cached
+    pick takes ``split``).  ``split`` is timed as what runs without the fusion: the plain
+    ``dgrad`` table's pick, then BatchNorm's partial pass with the residual write.  Timing
+    reads the fold slot and never changes it."""
+    if fuse_bn_dgrad_wide_mode() == "1" or torch.are_deterministic_algorithms_enabled():
+        return "fused"
+    if ("dgrad_1x1_bn",) + key not in _choice and torch.cuda.is_current_stream_capturing():
+        return "split"
+    from . import require
+
+    dres, x3 = fold.dres, fold.x3
+    be = _pick("dgrad", key, dgrad)
+
+    def split():
+        da = dgrad[be]()
+        dout = torch.empty_like(x3, memory_format=torch.channels_last)
+        return dout, require().bn_partial(x3.permute(0, 2, 3, 1), x.permute(0, 2, 3, 1), da.permute(0, 2, 3, 1),
+                                          x3.size(1), 1, True, None, dres.permute(0, 2, 3, 1), None,
+                                          dout.permute(0, 2, 3, 1))
+
+    cands = {"fused": lambda: conv1x1_bn_bwd_wide_hip(dy, wb, dres, x, x3), "split": split}
+    return _timed_pick(("dgrad_1x1_bn",) + key, cands)
+
+
 def _bn_partial(y: torch.Tensor) -> torch.Tensor:
     from . import require
 
@@ -727,7 +788,9 @@ class _Conv1x1Fn(torch.autograd.Function):
         fold = getattr(x, "_rla_fold", None)
         ctx.fold = fold if (fuse_bn and fork is None and fold is not None and getattr(fold, "x3", None) is not None
                             and fuse_bn_dgrad_enabled()
-                            and _bn_bwd_shape_ok(x2.size(0), cout, cin)) else None
+                            and (_bn_bwd_shape_ok(x2.size(0), cout, cin)
+                                 or (fuse_bn_dgrad_wide_mode() != "0"
+                                     and _bn_bwd_wide_shape_ok(x2.size(0), cout, cin)))) else None
         return y
 
     @staticmethod
@@ -754,7 +817,23 @@ class _Conv1x1Fn(torch.autograd.Function):
         be_d = be_w = None
         fork = ctx.fork if ctx.needs_input_grad[0] else None
         fold = ctx.fold
-        if fold is not None and fold.dres is not None and ctx.needs_input_grad[0]:
+        if fold is not None and cout > 128:
+            # the wide route (csrc/conv1x1_bn_bwd_wide.hip); on "split" everything below runs as
+            # without a fold and the producer BatchNorm's own pass consumes dres
+            if (fold.dres is not None and ctx.needs_input_grad[0] and fuse_bn_dgrad_wide_mode() != "0"
+                    and _bn_bwd_wide_shape_ok(x2.size(0), cout, cin)
+                    and _pick_dgrad_bn_wide(ctx.key, dy, x, wb, fold, dgrad) == "fused"):
+                from .bn import fold_stats
+
+                dx, part = conv1x1_bn_bwd_wide_hip(dy, wb, fold.dres, x, fold.x3)
+                fold.dres, fold.bwd_part = None, part
+                fold_stats["folded"] += 1
+                stats["bn_dgrad_fused_wide"] += 1
+                fold.bwd_d = dx  # bn backward checks it receives exactly this tensor
+            fold = None
+        if dx is not None:
+            pass
+        elif fold is not None and fold.dres is not None and ctx.needs_input_grad[0]:
             # d = (dy . W + dres_next) * (x > 0) and its BatchNorm partial sums in one
             # kernel; the producer BatchNorm's backward takes d as its dy
             from . import require
