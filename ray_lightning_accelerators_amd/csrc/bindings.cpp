@@ -1062,6 +1062,52 @@ py::dict conv1x1_bn_bwd_wide_plan(int64_t M, int64_t K, int64_t N) {
   return p;
 }
 
+// Input gradient of a forked 1x1 pair in one accumulator (csrc/conv1x1_fork_dgrad.hip): dy1
+// [N, H, W, C1], w1 [C1, Cin], dyd [N, OH, OW, Cd], wd [Cd, Cin] -- the FORWARD weights as stored
+// -- s = 1 or 2; returns dx [N, H, W, Cin] bf16, every element written once
+Tensor conv1x1_fork_dgrad(Tensor dy1, Tensor w1, Tensor dyd, Tensor wd, int64_t s) {
+  TORCH_CHECK(s == 1 || s == 2, "conv1x1_fork_dgrad: stride must be 1 or 2, got ", s);
+  TORCH_CHECK(dy1.dim() == 4 && dyd.dim() == 4, "conv1x1_fork_dgrad: dy1 and dyd must be [N, H, W, C] (NHWC)");
+  TORCH_CHECK(w1.dim() == 2 && wd.dim() == 2, "conv1x1_fork_dgrad: w1 and wd must be [Cout, Cin]");
+  const int64_t N = dy1.size(0), H = dy1.size(1), W = dy1.size(2), C1 = dy1.size(3);
+  const int64_t Cin = w1.size(1), Cd = wd.size(0), OH = (H - 1) / s + 1, OW = (W - 1) / s + 1;
+  TORCH_CHECK(w1.size(0) == C1, "conv1x1_fork_dgrad: w1 has ", w1.size(0), " output channels, dy1 has ", C1);
+  TORCH_CHECK(wd.size(1) == Cin, "conv1x1_fork_dgrad: wd has ", wd.size(1), " input channels, w1 has ", Cin);
+  TORCH_CHECK(dyd.size(0) == N && dyd.size(1) == OH && dyd.size(2) == OW && dyd.size(3) == Cd,
+              "conv1x1_fork_dgrad: dyd must be [", N, ", ", OH, ", ", OW, ", ", Cd, "], got ", dyd.sizes());
+  const uint16_t* dy1p = bf16_operand(dy1, "conv1x1_fork_dgrad: dy1", N * H * W * C1, dy1);
+  const uint16_t* w1p = bf16_operand(w1, "conv1x1_fork_dgrad: w1", C1 * Cin, dy1);
+  const uint16_t* dydp = bf16_operand(dyd, "conv1x1_fork_dgrad: dyd", N * OH * OW * Cd, dy1);
+  const uint16_t* wdp = bf16_operand(wd, "conv1x1_fork_dgrad: wd", Cd * Cin, dy1);
+  const rla::Conv1x1ForkDgradGeom g = rla::conv1x1_fork_dgrad_geom(N, H, W, Cin, C1, Cd, s);
+  TORCH_CHECK(rla::conv1x1_fork_dgrad_ok(g), "conv1x1_fork_dgrad: unsupported shape [", N, ", ", H, ", ", W, "], Cin = ",
+              Cin, ", C1 = ", C1, ", Cd = ", Cd, " (Cin % 64 == 0, 64 <= Cin <= 1024, C1 % 32 == 0, C1 <= 512, ",
+              "Cd % 32 == 0, Cd <= 2048)");
+  const at::hip::HIPGuardMasqueradingAsCUDA guard(dy1.device());
+  Tensor dx = at::empty({N, H, W, Cin}, dy1.options());
+  TORCH_CHECK(rla::launch_conv1x1_fork_dgrad(dy1p, w1p, dydp, wdp, reinterpret_cast<uint16_t*>(dx.data_ptr()), g,
+                                             cur_stream(dy1)),
+              "conv1x1_fork_dgrad: launch refused");
+  return dx;
+}
+
+// Read-only plan query (tests, docs): what a conv1x1_fork_dgrad launch runs under the current plan
+// CU count.  Workgroup b of `grid` walks units [units b / grid, units (b + 1) / grid).
+py::dict conv1x1_fork_dgrad_plan(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t C1, int64_t Cd, int64_t s) {
+  const rla::Conv1x1ForkDgradGeom g = rla::conv1x1_fork_dgrad_geom(N, H, W, Cin, C1, Cd, s);
+  TORCH_CHECK(rla::conv1x1_fork_dgrad_ok(g), "conv1x1_fork_dgrad_plan: unsupported shape");
+  py::dict p;
+  p["tile_rows"] = rla::conv1x1_fork_dgrad_tile_rows(g.s);
+  p["rows"] = g.rows;
+  p["tiles"] = g.tiles;
+  p["cols"] = g.cols;
+  p["units"] = g.units;
+  p["grid"] = g.grid;
+  p["stages"] = rla::conv1x1_fork_dgrad_stages();
+  p["lds_bytes"] = rla::conv1x1_fork_dgrad_lds_bytes();
+  return p;
+}
+
 // 1x1 conv forward with BatchNorm partial sums: x [M, K] (NHWC rows), w [N, K], both
 // bf16 contiguous; returns (y [M, N] bf16, part [gx, 2, N] fp32 for bn_finalize)
 std::vector<Tensor> conv1x1_stats(Tensor x, Tensor w, optional<Tensor> pre_ss, optional<Tensor> nbt_inc) {
@@ -1607,6 +1653,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv1x1_bn_bwd_wide_plan", &conv1x1_bn_bwd_wide_plan,
         "rows, row_ranges, tile_m, groups, units, grid, stages, lds_bytes of a conv1x1_bn_bwd_wide launch",
         py::arg("M"), py::arg("K"), py::arg("N"));
+  m.def("conv1x1_fork_dgrad", &conv1x1_fork_dgrad,
+        "input gradient of a forked 1x1 pair (stride 1 + stride s) in one accumulator -> dx [N, H, W, Cin]",
+        py::arg("dy1"), py::arg("w1"), py::arg("dyd"), py::arg("wd"), py::arg("s"));
+  m.def("conv1x1_fork_dgrad_ok",
+        [](int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t C1, int64_t Cd, int64_t s) {
+          return rla::conv1x1_fork_dgrad_ok(rla::conv1x1_fork_dgrad_geom(N, H, W, Cin, C1, Cd, s));
+        },
+        py::arg("N"), py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("C1"), py::arg("Cd"), py::arg("s"));
+  m.def("conv1x1_fork_dgrad_plan", &conv1x1_fork_dgrad_plan,
+        "tile_rows, rows, tiles, cols, units, grid, stages, lds_bytes of a conv1x1_fork_dgrad launch", py::arg("N"),
+        py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("C1"), py::arg("Cd"), py::arg("s"));
   m.def("conv1x1_stats_ok", [](int64_t M, int64_t K, int64_t N) { return rla::conv1x1_stats_ok(M, (int)K, (int)N); });
   m.def("maxpool_fwd", &maxpool_fwd,
         "NHWC bf16 max pool -> (y, one-byte window argmax); bn_ss: pool bf16(relu(x * scale + shift)) instead",

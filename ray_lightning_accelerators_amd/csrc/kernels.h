@@ -702,6 +702,32 @@ int conv1x1s2_stages();   // LDS ring depth
 bool launch_conv1x1s2(const uint16_t* x, const uint16_t* w, uint16_t* y, const Conv1x1S2Geom& g,
                       hipStream_t stream, float* part = nullptr);
 
+// Input gradient of a forked pair of 1x1 convolutions reading one tensor, in one accumulator
+// (csrc/conv1x1_fork_dgrad.hip): dx [N, H, W, Cin] = dy1 [N, H, W, C1] . w1 [C1][Cin], plus
+// dyd [N, OH, OW, Cd] . wd [Cd][Cin] at every s-th pixel (s = 1 or 2, OH = (H - 1) / s + 1);
+// the weights are the FORWARD weights as stored.  Tiled over quads (s = 2) or pixels (s = 1).
+struct Conv1x1ForkDgradGeom {
+  int N, H, W, Cin, C1, Cd, s, OH, OW;
+  int rows;   // what the tiles run over: quads N OH OW (s = 2) or pixels N H W (s = 1)
+  int tiles;  // of conv1x1_fork_dgrad_tile_rows(s) rows each
+  int cols;   // 64-channel column blocks
+  int units;  // tiles x cols, column-block-major: a workgroup walks a contiguous range
+  int grid;   // persistent workgroups: min(units, plan_cus())
+};
+// The one builder for the launch, the predicate and the plan query, under the current
+// plan_cus().  Arguments that are not positive, a stride other than 1 or 2, or sizes that
+// leave 32-bit row indexing give the all-zero geometry, which conv1x1_fork_dgrad_ok refuses;
+// Cin % 64 == 0, 64 <= Cin <= 1024, C1 % 32 == 0, C1 <= 512, Cd % 32 == 0, Cd <= 2048 are
+// conv1x1_fork_dgrad_ok's.
+Conv1x1ForkDgradGeom conv1x1_fork_dgrad_geom(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t C1, int64_t Cd,
+                                             int64_t s);
+bool conv1x1_fork_dgrad_ok(const Conv1x1ForkDgradGeom& g);
+int conv1x1_fork_dgrad_tile_rows(int s);  // quads (s = 2) or pixels (s = 1) per tile
+int conv1x1_fork_dgrad_stages();          // LDS ring depth
+int conv1x1_fork_dgrad_lds_bytes();
+bool launch_conv1x1_fork_dgrad(const uint16_t* dy1, const uint16_t* w1, const uint16_t* dyd, const uint16_t* wd,
+                               uint16_t* dx, const Conv1x1ForkDgradGeom& g, hipStream_t stream);
+
 // Input gradient of the 3x3 / stride 2 / pad 1 convolution on MFMA (csrc/conv3x3s2_dgrad.hip):
 // dx [N, H, W, Co] from dy [N, OH, OW, Cr] and the FORWARD weight w [Cr][3][3][Co] (Cr the
 // layer's output channels, Co its input channels, as conv3x3_dgrad_bn names them).  The work

@@ -22,7 +22,9 @@ use (like cudnn.benchmark): each operation builds ONE table ``{name: callable}``
 ``_pick`` names the winner and that table's callable runs.  ``RLA_CONV1X1`` and
 ``RLA_CONV_WGRAD`` pin a backend by its name in the table (``miopen|gemm|hip|...``),
 ``RLA_CONV3X3S2_DGRAD`` that of the stride-2 3x3 input gradient (``_pick_dgrad_s2``),
-``RLA_CONV1X1S2`` that of the stride-2 1x1 forward (``_pick_fwd_1x1s2``).
+``RLA_CONV1X1S2`` that of the stride-2 1x1 forward (``_pick_fwd_1x1s2``),
+``RLA_FORK_DGRAD=auto|0|1`` the input gradient of a forked 1x1 pair (``fork_dgrad_mode``:
+one kernel for both GEMMs, or the parked-dgrad route; ``dgrad_fork`` in ``choices()``).
 
 Around the convolutions themselves:
 
@@ -51,7 +53,7 @@ from torch import nn
 _choice: Dict[Tuple, str] = {}
 _timings: Dict[Tuple, Dict[str, float]] = {}
 stats = {"fast": 0, "fallback": 0, "bn_dgrad_fused": 0, "bn_dgrad_fused_3x3": 0, "stem": 0, "pre_applied": 0,
-         "bn_dgrad_fused_wide": 0}
+         "bn_dgrad_fused_wide": 0, "fork_dgrad_fused": 0}
 
 
 def _mode() -> str:
@@ -565,13 +567,173 @@ class GradFork:
     subsampled rows plus an add into every s-th pixel only (stride s > 1) -- and
     returns the sum.  Order-independent; autograd sees None + sum.  Only when BOTH
     consumers took a fast path (each registers in its forward): with one consumer on a
-    stock fallback, the fast one returns its own gradient and autograd adds as usual."""
+    stock fallback, the fast one returns its own gradient and autograd adds as usual.
+    A pair of 1x1 convolutions (stride 1 + stride 1 or 2) may instead park the first
+    backward's ``dy`` and compute dx in one kernel from both (:func:`fork_dgrad_mode`)."""
 
-    __slots__ = ("dx", "users")
+    __slots__ = ("dx", "users", "geo", "fused", "roles", "dy", "route")
 
     def __init__(self):
         self.dx: Optional[torch.Tensor] = None
         self.users = 0
+        # the fused route (csrc/conv1x1_fork_dgrad.hip, RLA_FORK_DGRAD): each user's geometry
+        # from its forward, whether the pair qualifies, (index of the stride-1 user whose
+        # gradient is dy1, index of the other), the parked (index, dy), the first backward's pick
+        self.geo: list = []
+        self.fused = False
+        self.roles = (0, 1)
+        self.dy = None
+        self.route: Optional[str] = None
+
+
+def fork_dgrad_mode() -> str:
+    """``RLA_FORK_DGRAD=auto|0|1``: a forked pair of 1x1 convolutions (a stride-1
+    ``Conv1x1NHWC`` and a 1x1 of stride 1 or 2: ResNet's conv1 + downsample) computes its
+    input gradient in ONE kernel, both GEMMs in one accumulator and dx stored once
+    (csrc/conv1x1_fork_dgrad.hip).  ``0``: never (the parked-dgrad route alone); ``1``:
+    wherever the kernel covers the pair; ``auto`` (default): per shape, whichever of the
+    kernel and the parked-dgrad route is faster (``dgrad_fork`` in :func:`choices`)."""
+    m = os.environ.get("RLA_FORK_DGRAD", "auto")
+    return m if m in ("0", "1") else "auto"
+
+
+def _fork_register(fork: Optional[GradFork], ctx, native: bool, x: torch.Tensor, wb: torch.Tensor, stride, padding,
+                   y: torch.Tensor) -> None:
+    """A forked user's forward: count it, keep its geometry, and with the second user decide
+    whether the pair's input gradient can take the fused kernel.  ``native``: the stride-1
+    ``Conv1x1NHWC``.  The strided user's gradient is dyd; between two stride-1 users of the
+    same kind the first to register is (Bottleneck runs its downsample conv first)."""
+    ctx.fork = fork
+    if fork is None:
+        return
+    ctx.fork_idx = fork.users
+    fork.users += 1
+    fork.geo.append({"native": native, "wb": wb, "stride": tuple(stride), "padding": tuple(padding),
+                     "yshape": tuple(y.shape)})
+    if fork.users != 2 or len(fork.geo) != 2 or fork_dgrad_mode() == "0":
+        fork.fused = False
+        return
+    a, b = fork.geo
+    d = 0 if not a["native"] else 1 if not b["native"] else 0
+    u1, ud = fork.geo[1 - d], fork.geo[d]
+    s = ud["stride"][0]
+    w1, wd = u1["wb"].reshape(u1["wb"].size(0), -1), ud["wb"].reshape(ud["wb"].size(0), -1)
+    n, cin, h, w = x.shape
+    fork.roles = (1 - d, d)
+    fork.fused = bool(
+        all(tuple(g["wb"].shape[2:]) in ((), (1, 1)) and g["padding"] == (0, 0) for g in (u1, ud))
+        and u1["stride"] == (1, 1) and ud["stride"] in ((1, 1), (2, 2))
+        and x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous(memory_format=torch.channels_last)
+        and all(t.dtype == torch.bfloat16 and t.size(1) == cin and t.is_contiguous() and t.data_ptr() % 16 == 0
+                for t in (w1, wd))
+        and u1["yshape"] == (n, w1.size(0), h, w)
+        and ud["yshape"] == (n, wd.size(0), (h - 1) // s + 1, (w - 1) // s + 1)
+        and _fork_dgrad_shape_ok(n, h, w, cin, w1.size(0), wd.size(0), s))
+
+
+def _fork_dgrad_shape_ok(n: int, h: int, w: int, cin: int, c1: int, cd: int, s: int) -> bool:
+    # not cached: the answer follows the planning CU count (see _conv3x3s2_shape_ok)
+    from . import require
+
+    return bool(require().conv1x1_fork_dgrad_ok(n, h, w, cin, c1, cd, s))
+
+
+def conv1x1_fork_dgrad_hip(dy1: torch.Tensor, w1: torch.Tensor, dyd: torch.Tensor, wd: torch.Tensor,
+                           s: int) -> torch.Tensor:
+    """Input gradient of a forked 1x1 pair on the MFMA kernel: ``dy1`` [N, C1, H, W] and ``dyd``
+    [N, Cd, OH, OW] channels_last bf16, ``w1`` [C1, Cin] and ``wd`` [Cd, Cin] the forward weights
+    as stored.  Returns dx [N, Cin, H, W] channels_last = dy1 . w1 + (every s-th pixel) dyd . wd,
+    one fp32 accumulator, one rounding, every element written once (bitwise reproducible)."""
+    from . import require
+
+    dx = require().conv1x1_fork_dgrad(dy1.permute(0, 2, 3, 1), w1, dyd.permute(0, 2, 3, 1), wd, s)
+    return dx.permute(0, 3, 1, 2)
+
+
+def _fork_split(dy1: torch.Tensor, w1: torch.Tensor, dyd: torch.Tensor, wd: torch.Tensor, x: torch.Tensor, s: int,
+                first_is_1: bool, full1: Optional[Callable] = None) -> torch.Tensor:
+    """The pair's input gradient by the parked-dgrad route, in the arrival order given: the
+    first user's full dgrad (a GEMM; MIOpen for the strided conv), then the second's added into
+    it (``addmm_``; for the strided conv a GEMM over the output pixels + ``strided_add_``).
+    ``full1``: the stride-1 user's full dgrad as its own ``dgrad`` table's pick computes it."""
+    from . import require
+
+    n, cin, h, w = x.shape
+    if first_is_1:
+        d = full1() if full1 is not None else _from2d(_gemm_dgrad(_nhwc2d(dy1), w1), n, h, w)
+        if s == 1:
+            _acc_dgrad(d, _nhwc2d(dyd), wd)
+        else:
+            require().strided_add_(d, _gemm_dgrad(_nhwc2d(dyd), wd), s)
+        return d
+    if s == 1:
+        d = _from2d(_gemm_dgrad(_nhwc2d(dyd), wd), n, h, w)
+    else:
+        d = _miopen_bwd(dyd, x, wd.view(wd.size(0), cin, 1, 1), (s, s), (0, 0), True, False)[0]
+    _acc_dgrad(d, _nhwc2d(dy1), w1)
+    return d
+
+
+def _fork_operands(fork: GradFork):
+    (i1, id_) = fork.roles
+    u1, ud = fork.geo[i1], fork.geo[id_]
+    return (u1["wb"].reshape(u1["wb"].size(0), -1), ud["wb"].reshape(ud["wb"].size(0), -1), ud["stride"][0],
+            u1["yshape"], ud["yshape"])
+
+
+def _fork_route(fork: GradFork, idx: int, dy: torch.Tensor, x: torch.Tensor, key=None, dgrad=None) -> str:
+    """``fused`` or ``split`` for a qualifying pair, asked by the backward that runs first (both
+    are fixed-order up to the library's GEMMs: ``1`` and deterministic mode take ``fused``
+    untimed; a graph capture with no cached pick takes ``split``).  ``split`` is timed as
+    today's whole route in this arrival order -- the stride-1 user's full dgrad by the plain
+    ``dgrad`` table's pick (``key`` / ``dgrad``: that table, from its backward), as
+    ``_pick_dgrad_bn_wide`` times its composite; the other user's gradient, not there yet, is
+    stood in for by a random tensor of its shape."""
+    if fork_dgrad_mode() == "1" or torch.are_deterministic_algorithms_enabled():
+        return "fused"
+    w1, wd, s, shape1, shaped = _fork_operands(fork)
+    first_is_1 = idx == fork.roles[0]
+    full1 = None
+    if first_is_1 and dgrad is not None:
+        be = _pick("dgrad", key, dgrad)
+        full1 = dgrad[be]
+    k = ("dgrad_fork", x.size(0) * x.size(2) * x.size(3), x.size(1), w1.size(0), wd.size(0), s, int(first_is_1))
+    if k in _choice:
+        return _choice[k]
+    if torch.cuda.is_current_stream_capturing():
+        return "split"
+    other = torch.randn(shaped if first_is_1 else shape1, device=dy.device, dtype=torch.bfloat16)
+    other = other.contiguous(memory_format=torch.channels_last)
+    dy1, dyd = (dy, other) if first_is_1 else (other, dy)
+    return _timed_pick(k, {"fused": lambda: conv1x1_fork_dgrad_hip(dy1, w1, dyd, wd, s),
+                           "split": lambda: _fork_split(dy1, w1, dyd, wd, x, s, first_is_1, full1)})
+
+
+def _fork_fused(fork: GradFork, idx: int, dy: torch.Tensor, x: torch.Tensor, key=None, dgrad=None):
+    """One backward of a qualifying pair.  Returns (settled, dx).  The first to run asks
+    :func:`_fork_route`: on ``fused`` it parks its ``dy`` and computes no dgrad (settled, dx
+    None); on ``split`` the pair takes the parked-dgrad route below as ever (not settled).  The
+    second calls the kernel with both gradients, the roles by layer and not by arrival; if a
+    gradient is not what the forward announced it adds the two up by :func:`_fork_split`."""
+    if fork.dx is not None or fork.route == "split":
+        if fork.dx is not None:
+            fork.route = None  # the second backward of a split pair: the next step asks again
+        return False, None
+    if fork.dy is None:
+        fork.route = _fork_route(fork, idx, dy, x, key, dgrad)
+        if fork.route != "fused":
+            return False, None
+        fork.dy = (idx, dy)
+        return True, None
+    (pidx, pdy), fork.dy, fork.route = fork.dy, None, None
+    w1, wd, s, shape1, shaped = _fork_operands(fork)
+    dy1, dyd = (pdy, dy) if pidx == fork.roles[0] else (dy, pdy)
+    if (pidx != idx and tuple(dy1.shape) == shape1 and tuple(dyd.shape) == shaped
+            and all(t.dtype == torch.bfloat16 and t.is_contiguous(memory_format=torch.channels_last)
+                    and t.data_ptr() % 16 == 0 for t in (dy1, dyd))):
+        stats["fork_dgrad_fused"] += 1
+        return True, conv1x1_fork_dgrad_hip(dy1, w1, dyd, wd, s)
+    return True, _fork_split(dy1, w1, dyd, wd, x, s, pidx == fork.roles[0])
 
 
 def _fork_dx(fork: Optional[GradFork], full, accumulate) -> Optional[torch.Tensor]:
@@ -780,9 +942,7 @@ class _Conv1x1Fn(torch.autograd.Function):
             y = _run("fwd", key, cands)
         ctx.save_for_backward(x, wb)
         ctx.key = key
-        ctx.fork = fork
-        if fork is not None:
-            fork.users += 1
+        _fork_register(fork, ctx, True, x, wb, (1, 1), (0, 0), y)
         # x is a residual BatchNorm+ReLU's output (its fold slot carries that layer's
         # input): the input gradient may absorb the BatchNorm's backward partial
         fold = getattr(x, "_rla_fold", None)
@@ -816,6 +976,10 @@ class _Conv1x1Fn(torch.autograd.Function):
         dx = dw = None
         be_d = be_w = None
         fork = ctx.fork if ctx.needs_input_grad[0] else None
+        settled = False
+        if fork is not None and fork.fused:
+            # a qualifying forked pair (RLA_FORK_DGRAD): park dy, or both GEMMs in one kernel
+            settled, dx = _fork_fused(fork, ctx.fork_idx, dy, x, ctx.key, dgrad)
         fold = ctx.fold
         if fold is not None and cout > 128:
             # the wide route (csrc/conv1x1_bn_bwd_wide.hip); on "split" everything below runs as
@@ -831,7 +995,7 @@ class _Conv1x1Fn(torch.autograd.Function):
                 stats["bn_dgrad_fused_wide"] += 1
                 fold.bwd_d = dx  # bn backward checks it receives exactly this tensor
             fold = None
-        if dx is not None:
+        if dx is not None or settled:
             pass
         elif fold is not None and fold.dres is not None and ctx.needs_input_grad[0]:
             # d = (dy . W + dres_next) * (x > 0) and its BatchNorm partial sums in one
@@ -982,9 +1146,7 @@ class _ConvNHWCFn(torch.autograd.Function):
                 y = _run("fwd_kxk", key, cands)
         ctx.save_for_backward(x, wb)
         ctx.geo = (tuple(stride), tuple(padding))
-        ctx.fork = fork
-        if fork is not None:
-            fork.users += 1
+        _fork_register(fork, ctx, False, x, wb, stride, padding, y)
         return y
 
     @staticmethod
@@ -1007,7 +1169,13 @@ class _ConvNHWCFn(torch.autograd.Function):
             wgrad["hip_gen"] = lambda: wgrad_hip(dy, x, (kh, kw), stride, padding, algo=1, pre_ss=st)
         dx = dw = None
         fork = ctx.fork if ctx.needs_input_grad[0] else None
-        if fork is not None and fork.users >= 2 and fork.dx is not None and (kh, kw) == (1, 1) \
+        settled = False
+        if fork is not None and fork.fused:
+            # a qualifying forked pair (RLA_FORK_DGRAD): park dy, or both GEMMs in one kernel
+            settled, dx = _fork_fused(fork, ctx.fork_idx, dy, x)
+        if settled:
+            pass
+        elif fork is not None and fork.users >= 2 and fork.dx is not None and (kh, kw) == (1, 1) \
                 and padding == (0, 0):
             # second of a forked pair, strided 1x1: GEMM over the output pixels, added
             # into every stride-th input pixel of the parked dgrad (1/s^2 of it)
@@ -1034,7 +1202,7 @@ class _ConvNHWCFn(torch.autograd.Function):
 
             dx = _fork_dx(fork, None, acc)
             fork = None  # the input gradient is settled
-        need_dx = bool(ctx.needs_input_grad[0]) and dx is None
+        need_dx = bool(ctx.needs_input_grad[0]) and dx is None and not settled
         be_d = be_w = None
         fold = ctx.fold
         if (need_dx and fold is not None and ctx.fork is None and fold.xin is not None and not fold.claimed

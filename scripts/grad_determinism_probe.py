@@ -59,8 +59,9 @@ def main():
 
     step()  # backend picks
     calls.update(s2_dgrad_hip=0, miopen_bwd_dx=0)
+    fused0 = C.stats["fork_dgrad_fused"]
     g1 = step()
-    per_step = dict(calls)
+    per_step = dict(calls, fork_dgrad_fused=C.stats["fork_dgrad_fused"] - fused0)
     g2 = step()
     names = [n for n, _ in m.named_parameters() if n in g1][::-1]  # backward order
     differing = [n for n in names if not torch.equal(g1[n], g2[n])]
@@ -72,7 +73,7 @@ def main():
                       "deterministic": deterministic, "first_in_backward_order": differing[0] if differing else None,
                       "calls_per_step": per_step,
                       "picks": {k: v["pick"] for k, v in C.choices().items()
-                                if k.startswith("dgrad_s2") or k.startswith("fwd_kxk")}}), flush=True)
+                                if k.startswith(("dgrad_s2", "fwd_kxk", "dgrad_fork"))}}), flush=True)
 
 
 if __name__ == "__main__":
