@@ -1432,6 +1432,67 @@ std::vector<int64_t> conv1x1s2_plan(int64_t N, int64_t H, int64_t W, int64_t Cin
           rla::conv1x1s2_stages(), g.OH, g.OW};
 }
 
+// 1x1 / stride 1 forward with an eval-mode BatchNorm, ReLU and residual add in its epilogue
+// (csrc/conv1x1_bn_act.hip): x [M, K] (NHWC rows), w [N, K], res [M, N] or none, all bf16;
+// mean / var / gamma / beta fp32 [N].  Returns out [M, N] bf16; the conv output is never written.
+const float* bn_act_vec(const Tensor& t, const char* name, int64_t N, const Tensor& like) {
+  check_dev(t, name, at::kFloat);
+  TORCH_CHECK(t.device() == like.device(), name, " must be on ", like.device(), ", not ", t.device());
+  TORCH_CHECK(t.dim() == 1 && t.numel() == N, name, " must be a vector of ", N, " elements, got ", t.numel());
+  return t.data_ptr<float>();
+}
+
+Tensor conv1x1_bn_act(Tensor x, Tensor w, Tensor mean, Tensor var, Tensor gamma, Tensor beta, double eps, bool relu,
+                      optional<Tensor> res) {
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && w.size(1) == x.size(1), "conv1x1_bn_act: x must be [M, K] and w [N, K]");
+  const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
+  const uint16_t* xp = bf16_operand(x, "conv1x1_bn_act: x", M * K, x);
+  const uint16_t* wp = bf16_operand(w, "conv1x1_bn_act: w", N * K, x);
+  const rla::Conv1x1BnActGeom g = rla::conv1x1_bn_act_geom(M, K, N);
+  TORCH_CHECK(rla::conv1x1_bn_act_ok(g), "conv1x1_bn_act: unsupported shape [", M, ", ", K, "] x [", N, ", ", K,
+              "] (K % 32, N % 64)");
+  const float* mp = bn_act_vec(mean, "conv1x1_bn_act: mean", N, x);
+  const float* vp = bn_act_vec(var, "conv1x1_bn_act: var", N, x);
+  const float* gp = bn_act_vec(gamma, "conv1x1_bn_act: gamma", N, x);
+  const float* bp = bn_act_vec(beta, "conv1x1_bn_act: beta", N, x);
+  const uint16_t* rp = nullptr;
+  if (res.has_value() && res->defined()) {
+    TORCH_CHECK(relu, "conv1x1_bn_act: a residual comes with the ReLU epilogue only");
+    TORCH_CHECK(res->dim() == 2 && res->size(0) == M && res->size(1) == N, "conv1x1_bn_act: res must be [", M, ", ", N,
+                "]");
+    rp = bf16_operand(*res, "conv1x1_bn_act: res", M * N, x);
+  }
+  const at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor out = at::empty({M, N}, x.options());
+  TORCH_CHECK(rla::launch_conv1x1_bn_act(xp, wp, rp, reinterpret_cast<uint16_t*>(out.data_ptr()), mp, vp, gp, bp,
+                                         (float)eps, relu, g, cur_stream(x)),
+              "conv1x1_bn_act: launch refused");
+  return out;
+}
+
+bool conv1x1_bn_act_supported(int64_t M, int64_t K, int64_t N) {
+  return rla::conv1x1_bn_act_ok(rla::conv1x1_bn_act_geom(M, K, N));
+}
+
+// Read-only plan query (tests, docs): what a conv1x1_bn_act launch runs under the current plan
+// CU count.  Pixel range b of `gx` walks tiles [b tiles_per_blk, (b + 1) tiles_per_blk).
+py::dict conv1x1_bn_act_plan(int64_t M, int64_t K, int64_t N) {
+  const rla::Conv1x1BnActGeom g = rla::conv1x1_bn_act_geom(M, K, N);
+  TORCH_CHECK(rla::conv1x1_bn_act_ok(g), "conv1x1_bn_act_plan: unsupported shape");
+  py::dict p;
+  p["tile_m"] = rla::conv1x1_bn_act_tile_m();
+  p["tile_n"] = rla::conv1x1_bn_act_tile_n();
+  p["rows"] = g.rows;
+  p["cols"] = g.cols;
+  p["tiles_per_blk"] = g.tiles_per_blk;
+  p["gx"] = g.gx;
+  p["grid"] = g.grid;
+  p["stages"] = rla::conv1x1_bn_act_stages();
+  p["wres"] = g.wres;
+  p["lds_bytes"] = rla::conv1x1_bn_act_lds_bytes();
+  return p;
+}
+
 // Input gradient of the 3x3 / stride 2 / pad 1 convolution (csrc/conv3x3s2_dgrad.hip):
 // dy [N, OH, OW, Cr] and the forward weight w [Cr, 3, 3, Co] as contiguous memory; returns dx as
 // contiguous [N, H, W, Co], every element written by the kernel.
@@ -1734,6 +1795,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv1x1s2_plan", &conv1x1s2_plan,
         "the 1x1 stride-2 kernel's (tile_m, tile_n, rows, cols, grid, stage_k, stages, OH, OW)", py::arg("N"),
         py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"), py::arg("stats") = false);
+  m.def("conv1x1_bn_act", &conv1x1_bn_act,
+        "1x1 / stride 1 forward with an eval-mode BatchNorm (+ ReLU, + residual) in its epilogue -> out [M, N]",
+        py::arg("x"), py::arg("w"), py::arg("mean"), py::arg("var"), py::arg("gamma"), py::arg("beta"), py::arg("eps"),
+        py::arg("relu"), py::arg("res") = py::none());
+  m.def("conv1x1_bn_act_ok", &conv1x1_bn_act_supported, "shapes conv1x1_bn_act covers", py::arg("M"), py::arg("K"),
+        py::arg("N"));
+  m.def("conv1x1_bn_act_plan", &conv1x1_bn_act_plan,
+        "conv1x1_bn_act's tile_m, tile_n, rows, cols, tiles_per_blk, gx, grid, stages, wres, lds_bytes", py::arg("M"),
+        py::arg("K"), py::arg("N"));
   m.def("conv3x3s2_dgrad", &conv3x3s2_dgrad,
         "3x3 / stride 2 / pad 1 input gradient on MFMA: dy [N, OH, OW, Cr], forward weight [Cr, 3, 3, Co] "
         "-> dx [N, H, W, Co]",

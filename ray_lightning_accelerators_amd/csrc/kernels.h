@@ -702,6 +702,35 @@ int conv1x1s2_stages();   // LDS ring depth
 bool launch_conv1x1s2(const uint16_t* x, const uint16_t* w, uint16_t* y, const Conv1x1S2Geom& g,
                       hipStream_t stream, float* part = nullptr);
 
+// 1x1 / stride 1 NHWC bf16 convolution forward with an eval-mode BatchNorm, ReLU and residual
+// add in its epilogue (csrc/conv1x1_bn_act.hip):
+//   out [M, N] = bf16(act(fma(x [M, K] . w [N, K]^T, scale, shift) + res [M, N])),
+//   scale = gamma / sqrt(var + eps), shift = beta - mean scale, computed in the kernel.
+// A workgroup owns one 64-channel column and walks tiles_per_blk 128-pixel tiles of it.
+struct Conv1x1BnActGeom {
+  int M, K, N;
+  int rows;           // 128-pixel tiles
+  int cols;           // 64-channel columns
+  int tiles_per_blk;  // consecutive tiles a workgroup walks
+  int gx;             // pixel ranges, a multiple of 8 (XCD deal)
+  int grid;           // workgroups: gx x cols
+  bool wres;          // K <= 128: the column's weight block stays in LDS
+};
+// The one builder for the launch, the predicate and the plan query, under the current
+// plan_cus().  Arguments that are not positive or leave 32-bit row indexing give the all-zero
+// geometry, which conv1x1_bn_act_ok refuses; K % 32 == 0 and N % 64 == 0 are conv1x1_bn_act_ok's.
+Conv1x1BnActGeom conv1x1_bn_act_geom(int64_t M, int64_t K, int64_t N);
+bool conv1x1_bn_act_ok(const Conv1x1BnActGeom& g);
+int conv1x1_bn_act_tile_m();
+int conv1x1_bn_act_tile_n();
+int conv1x1_bn_act_stages();  // LDS ring depth
+int conv1x1_bn_act_lds_bytes();
+// res (or null; with relu only): the shortcut, added after the affine map and before the ReLU.
+// The three epilogues: relu, relu + res, plain affine; res without relu is refused.
+bool launch_conv1x1_bn_act(const uint16_t* x, const uint16_t* w, const uint16_t* res, uint16_t* out,
+                           const float* mean, const float* var, const float* gamma, const float* beta, float eps,
+                           bool relu, const Conv1x1BnActGeom& g, hipStream_t stream);
+
 // Input gradient of a forked pair of 1x1 convolutions reading one tensor, in one accumulator
 // (csrc/conv1x1_fork_dgrad.hip): dx [N, H, W, Cin] = dy1 [N, H, W, C1] . w1 [C1][Cin], plus
 // dyd [N, OH, OW, Cd] . wd [Cd][Cin] at every s-th pixel (s = 1 or 2, OH = (H - 1) / s + 1);

@@ -25,7 +25,7 @@ from torch.utils.data import Dataset
 
 from ..lightning import LightningModule
 from ..ops.bn import BatchNormAct2d
-from ..ops.conv import BNStats, Conv1x1NHWC, GradFork
+from ..ops.conv import BNStats, Conv1x1NHWC, GradFork, conv1x1_bn_eval, conv1x1_bn_eval_ok
 from ..ops.pool import MaxPool2dNHWC, global_avg_pool_nhwc
 from ..ops.shadow import ConvBF16
 
@@ -79,11 +79,15 @@ class Bottleneck(nn.Module):
     def _conv_bn(conv, bn, x, **kw):
         """bn(conv(x)): a stride-1 1x1 conv, a 3x3 conv of stride 1 or 2 or the stride-2 1x1
         downsample conv may compute bn's batch statistics in its epilogue (ops.conv.BNStats;
-        bn then skips its partial pass over the output)."""
+        bn then skips its partial pass over the output).  In eval mode under ``no_grad`` a
+        stride-1 1x1 conv may run bn, the ReLU and the shortcut add in its own epilogue
+        (ops.conv.conv1x1_bn_eval)."""
         fork = kw.pop("fork", None)
         if isinstance(conv, (Conv1x1NHWC, ConvBF16)) and bn.training:
             st = BNStats()
             return bn(conv(x, fork=fork, bn_stats=st), bn_stats=st, **kw)
+        if conv1x1_bn_eval_ok(x, conv, bn, kw.get("residual")):
+            return conv1x1_bn_eval(x, conv, bn, kw.get("residual"))
         return bn(conv(x, fork=fork) if fork is not None else conv(x), **kw)
 
     def forward(self, x):

@@ -24,7 +24,9 @@ use (like cudnn.benchmark): each operation builds ONE table ``{name: callable}``
 ``RLA_CONV3X3S2_DGRAD`` that of the stride-2 3x3 input gradient (``_pick_dgrad_s2``),
 ``RLA_CONV1X1S2`` that of the stride-2 1x1 forward (``_pick_fwd_1x1s2``),
 ``RLA_FORK_DGRAD=auto|0|1`` the input gradient of a forked 1x1 pair (``fork_dgrad_mode``:
-one kernel for both GEMMs, or the parked-dgrad route; ``dgrad_fork`` in ``choices()``).
+one kernel for both GEMMs, or the parked-dgrad route; ``dgrad_fork`` in ``choices()``),
+``RLA_CONV1X1_BN_EVAL=auto|0|1`` the eval-mode forward of a stride-1 1x1 layer and its
+BatchNorm (``conv1x1_bn_eval``: one kernel, or the conv and the apply pass; ``fwd_bn_eval``).
 
 Around the convolutions themselves:
 
@@ -53,7 +55,7 @@ from torch import nn
 _choice: Dict[Tuple, str] = {}
 _timings: Dict[Tuple, Dict[str, float]] = {}
 stats = {"fast": 0, "fallback": 0, "bn_dgrad_fused": 0, "bn_dgrad_fused_3x3": 0, "stem": 0, "pre_applied": 0,
-         "bn_dgrad_fused_wide": 0, "fork_dgrad_fused": 0}
+         "bn_dgrad_fused_wide": 0, "fork_dgrad_fused": 0, "bn_eval_fused": 0}
 
 
 def _mode() -> str:
@@ -1077,6 +1079,113 @@ class Conv1x1NHWC(nn.Conv2d):
             return _Conv1x1Fn.apply(x, self.weight, bf16_weight(self.weight), fork, bn_stats, self.fuse_bn_dgrad)
         stats["fallback"] += 1
         return F.conv2d(x, self.weight)
+
+
+# ---- eval mode: conv + BatchNorm (+ ReLU, + residual) in one kernel ---------------------------
+
+def bn_eval_mode() -> str:
+    """``RLA_CONV1X1_BN_EVAL``: how an eval-mode BatchNorm after a stride-1 1x1 conv runs under
+    ``no_grad``.  ``auto``: the fused kernel (csrc/conv1x1_bn_act.hip) or the split route (the
+    conv's own pick, the coefficient ops and ``bn_apply``), timed per shape and epilogue; ``1``:
+    the fused kernel wherever it applies; ``0``: the split route, untouched."""
+    m = os.environ.get("RLA_CONV1X1_BN_EVAL", "auto")
+    return m if m in ("0", "1") else "auto"
+
+
+def conv1x1_bn_act_ok(m: int, cin: int, cout: int) -> bool:
+    """Shapes of the 1x1 forward with the eval-mode BatchNorm epilogue: cin % 32 == 0, cout % 64 == 0."""
+    return _conv1x1_bn_act_shape_ok(m, cin, cout)
+
+
+@functools.lru_cache(maxsize=256)
+def _conv1x1_bn_act_shape_ok(m: int, k: int, n: int) -> bool:
+    from . import require
+
+    return bool(require().conv1x1_bn_act_ok(m, k, n))
+
+
+def conv1x1_bn_act_hip(x: torch.Tensor, wb: torch.Tensor, mean: torch.Tensor, var: torch.Tensor,
+                       gamma: torch.Tensor, beta: torch.Tensor, eps: float, relu: bool,
+                       residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``act(bn(conv2d(x, wb)) + residual)`` with the BatchNorm on the given statistics, in one
+    MFMA kernel: ``x`` [N, Cin, H, W] and ``residual`` [N, Cout, H, W] channels_last bf16, ``wb``
+    [Cout, Cin] bf16, the four vectors fp32 [Cout].  The conv output is neither written nor
+    rounded; scale and shift are computed in the kernel.  Returns channels_last bf16."""
+    from . import require
+
+    n, _, h, w = x.shape
+    res2 = _nhwc2d(residual) if residual is not None else None
+    return _from2d(require().conv1x1_bn_act(_nhwc2d(x), wb, mean, var, gamma, beta, float(eps), relu, res2), n, h, w)
+
+
+def _hooked(*mods: nn.Module) -> bool:
+    g = torch.nn.modules.module
+    return bool(g._global_forward_hooks or g._global_forward_pre_hooks
+                or any(m._forward_hooks or m._forward_pre_hooks for m in mods))
+
+
+def conv1x1_bn_eval_ok(x: torch.Tensor, conv: nn.Module, bn: nn.Module, residual: Optional[torch.Tensor] = None) -> bool:
+    """Whether ``bn(conv(x), residual=residual)`` may run as :func:`conv1x1_bn_eval`: a
+    ``Conv1x1NHWC`` on its fast path and an eval-mode ``BatchNormAct2d`` on fp32 running
+    statistics with affine parameters, autograd off, no deferred BatchNorm on ``x``, no hooks on
+    either module (the fused route calls neither ``forward``), and the switch not at ``0``."""
+    if torch.is_grad_enabled() or bn.training or not isinstance(conv, Conv1x1NHWC) or bn_eval_mode() == "0":
+        return False  # the training step and the switched-off route leave here
+    from .bn import BatchNormAct2d, fused_ok
+
+    if not isinstance(bn, BatchNormAct2d) or not bn.track_running_stats or bn.weight is None or bn.bias is None \
+            or bn.running_mean is None or bn.running_var is None:
+        return False
+    if getattr(x, "_rla_pre", None) is not None or not fast_ok(x, conv) or _mode() == "off" or _hooked(conv, bn):
+        return False
+    if residual is not None and (bn.act != "relu" or residual.size(1) != conv.out_channels
+                                 or residual.shape[2:] != x.shape[2:] or residual.size(0) != x.size(0)
+                                 or not residual.is_cuda or not fused_ok(residual)):
+        return False
+    vecs = (bn.running_mean, bn.running_var, bn.weight, bn.bias)
+    if any(v.dtype != torch.float32 or v.device != x.device or not v.is_contiguous() for v in vecs):
+        return False
+    return conv1x1_bn_act_ok(x.size(0) * x.size(2) * x.size(3), x.size(1), conv.out_channels)
+
+
+def conv1x1_bn_eval(x: torch.Tensor, conv: "Conv1x1NHWC", bn: nn.Module,
+                    residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``bn(conv(x), residual=residual)`` for an eval-mode BatchNorm under ``no_grad``; the
+    caller checked :func:`conv1x1_bn_eval_ok`.  ``fused`` is the one-kernel route, ``split``
+    the modules' own forwards; ``RLA_CONV1X1_BN_EVAL=1`` and deterministic mode take ``fused``
+    untimed, ``auto`` the faster of the two per (M, Cin, Cout, epilogue) -- ``fwd_bn_eval`` in
+    :func:`choices` -- and a stream capture without a cached pick takes ``split``."""
+    from . import bn as _bn
+    from .shadow import bf16_weight
+
+    cout, cin = conv.out_channels, x.size(1)
+    relu = bn.act == "relu"
+
+    def split():
+        return bn(conv(x), residual=residual)
+
+    def fused():
+        shadow = bf16_weight(conv.weight)
+        # the arena's bf16 shadow when there is one, as _Conv1x1Fn reads it
+        wb = (shadow if shadow is not None else conv.weight.detach().to(torch.bfloat16)).reshape(cout, cin)
+        return conv1x1_bn_act_hip(x, wb, bn.running_mean, bn.running_var, bn.weight.detach(), bn.bias.detach(),
+                                  bn.eps, relu, residual)
+
+    if bn_eval_mode() != "1" and not torch.are_deterministic_algorithms_enabled():
+        k = ("fwd_bn_eval", x.size(0) * x.size(2) * x.size(3), cin, cout, 2 if residual is not None else int(relu))
+        if _choice.get(k) is None:
+            if torch.cuda.is_current_stream_capturing():
+                return split()
+            keep = dict(stats), dict(_bn.stats)  # the timing calls are not the model's
+            try:
+                _timed_pick(k, {"fused": fused, "split": split})
+            finally:
+                stats.update(keep[0])
+                _bn.stats.update(keep[1])
+        if _choice[k] == "split":
+            return split()
+    stats["bn_eval_fused"] += 1
+    return fused()
 
 
 class _ConvNHWCFn(torch.autograd.Function):
