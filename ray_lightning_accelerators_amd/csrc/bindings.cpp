@@ -1493,6 +1493,32 @@ py::dict conv1x1_bn_act_plan(int64_t M, int64_t K, int64_t N) {
   return p;
 }
 
+// 3x3 / stride 1 / pad 1 forward with an eval-mode BatchNorm (+ ReLU) in its epilogue
+// (csrc/conv3x3.hip ACT): x [N, H, W, Cin] and w [Cout, 3, 3, Cin] as contiguous bf16 memory,
+// mean / var / gamma / beta fp32 [Cout].  Returns out [N, H, W, Cout] bf16; the conv output is
+// never written.  The plan is the plain forward's (conv3x3_plan).
+Tensor conv3x3_bn_act(Tensor x, Tensor w, int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout, Tensor mean,
+                      Tensor var, Tensor gamma, Tensor beta, double eps, bool relu) {
+  const rla::Conv3x3Geom g = rla::conv3x3_geom(N, H, W, Cin, Cout);
+  TORCH_CHECK(rla::conv3x3_ok(g), "conv3x3_bn_act: unsupported shape (Cin % 16, Cout % 64, halo tile size)");
+  const uint16_t* xp = bf16_operand(x, "conv3x3_bn_act: x", N * H * W * Cin, x);
+  const uint16_t* wp = bf16_operand(w, "conv3x3_bn_act: w", Cout * 9 * Cin, x);
+  const rla::Conv3x3BnAct act{bn_act_vec(mean, "conv3x3_bn_act: mean", Cout, x),
+                              bn_act_vec(var, "conv3x3_bn_act: var", Cout, x),
+                              bn_act_vec(gamma, "conv3x3_bn_act: gamma", Cout, x),
+                              bn_act_vec(beta, "conv3x3_bn_act: beta", Cout, x), (float)eps, relu ? 1 : 0};
+  const at::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor out = at::empty({N, H, W, Cout}, x.options());
+  TORCH_CHECK(rla::launch_conv3x3(xp, wp, reinterpret_cast<uint16_t*>(out.data_ptr()), g, false, cur_stream(x),
+                                  nullptr, nullptr, nullptr, nullptr, &act),
+              "conv3x3_bn_act: launch refused");
+  return out;
+}
+
+bool conv3x3_bn_act_supported(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout) {
+  return rla::conv3x3_ok(rla::conv3x3_geom(N, H, W, Cin, Cout));
+}
+
 // Input gradient of the 3x3 / stride 2 / pad 1 convolution (csrc/conv3x3s2_dgrad.hip):
 // dy [N, OH, OW, Cr] and the forward weight w [Cr, 3, 3, Co] as contiguous memory; returns dx as
 // contiguous [N, H, W, Co], every element written by the kernel.
@@ -1804,6 +1830,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv1x1_bn_act_plan", &conv1x1_bn_act_plan,
         "conv1x1_bn_act's tile_m, tile_n, rows, cols, tiles_per_blk, gx, grid, stages, wres, lds_bytes", py::arg("M"),
         py::arg("K"), py::arg("N"));
+  m.def("conv3x3_bn_act", &conv3x3_bn_act,
+        "3x3 / stride 1 / pad 1 forward with an eval-mode BatchNorm (+ ReLU) in its epilogue -> out [N, H, W, Cout]",
+        py::arg("x"), py::arg("w"), py::arg("N"), py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"),
+        py::arg("mean"), py::arg("var"), py::arg("gamma"), py::arg("beta"), py::arg("eps"), py::arg("relu"));
+  m.def("conv3x3_bn_act_ok", &conv3x3_bn_act_supported, "shapes conv3x3_bn_act covers", py::arg("N"), py::arg("H"),
+        py::arg("W"), py::arg("Cin"), py::arg("Cout"));
   m.def("conv3x3s2_dgrad", &conv3x3s2_dgrad,
         "3x3 / stride 2 / pad 1 input gradient on MFMA: dy [N, OH, OW, Cr], forward weight [Cr, 3, 3, Co] "
         "-> dx [N, H, W, Co]",

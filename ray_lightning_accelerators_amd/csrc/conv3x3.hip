@@ -145,16 +145,28 @@ struct CvSet {
 // 64 scales and shifts sit in an LDS table.  The compile-time-shape input-gradient
 // instances have the registers for it (256-pixel tiles: 106 AGPRs before, 184 with the
 // sums), the 56x56 one with a single register stage (launch_bwd).
+//
+// ACT (forward only, exclusive with ST, PRE and BWD): an eval-mode BatchNorm and an optional
+// ReLU (ACT = 2) in the epilogue, y = bf16(act(fma(acc, scale, shift))) with scale = gamma /
+// sqrt(var + eps) and shift = fma(-mean, scale, beta): the per-channel map is applied to the
+// fp32 accumulator ahead of its one rounding, so the conv output is neither written nor
+// re-read.  A workgroup owns one 64-channel block for all its tiles: threads 0..63 compute the
+// block's scale and shift in the prologue (conv1x1_bn_act.hip's operation sequence: both eval
+// kernels share one definition) into BWD's 512-byte LDS table, and the rounding loop reads one
+// float4 of each per group of 4 accumulators.  Everything behind the rounding is the plain
+// forward's, and so are the instances, the pipeline depths and the work split.
 constexpr int kPreMaxC = 512;
 template <int NX, bool FLIP, int JB, int DEPTH, int WC = 0, int CC = 0, bool ST = false, bool PRE = false,
-          bool BWD = false>
+          bool BWD = false, int ACT = 0>
 __global__ __launch_bounds__(kCvThreads) void conv3x3_kernel(const uint16_t* __restrict__ x,
                                                              const uint16_t* __restrict__ w,
                                                              uint16_t* __restrict__ y, Conv3x3Geom g,
                                                              float* __restrict__ part,
                                                              const float* __restrict__ pre_ss = nullptr,
                                                              int64_t* __restrict__ nbt_inc = nullptr,
-                                                             const uint16_t* __restrict__ xb = nullptr) {
+                                                             const uint16_t* __restrict__ xb = nullptr,
+                                                             Conv3x3BnAct act = Conv3x3BnAct{}) {
+  static_assert(!ACT || !(FLIP || ST || PRE || BWD), "ACT is an epilogue of the plain forward");
   static_assert(!(ST && FLIP), "the forward statistics are a forward epilogue");
   static_assert(!(PRE && FLIP), "PRE is a forward variant");
   static_assert(!BWD || FLIP, "BWD is an input-gradient epilogue");
@@ -163,8 +175,8 @@ __global__ __launch_bounds__(kCvThreads) void conv3x3_kernel(const uint16_t* __r
   __shared__ __attribute__((aligned(16))) __bf16 lds[2 * BE];
   // [channel][scale, shift] interleaved: one 16-byte read covers a word's two channels
   __shared__ __attribute__((aligned(16))) float pre_tab[PRE ? 2 * kPreMaxC : 4];
-  // BWD: this workgroup's 64 output channels, [scale | shift]
-  __shared__ __attribute__((aligned(16))) float bwd_tab[BWD ? 2 * kTN : 4];
+  // BWD / ACT: this workgroup's 64 output channels, [scale | shift]
+  __shared__ __attribute__((aligned(16))) float bwd_tab[BWD || ACT ? 2 * kTN : 4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (WC) g.W = WC;
   if (CC) g.Cin = CC;
@@ -205,6 +217,15 @@ __global__ __launch_bounds__(kCvThreads) void conv3x3_kernel(const uint16_t* __r
     if (tid < 2 * kTN) bwd_tab[tid] = pre_ss[(2 + (tid >> 6)) * g.Cout + nblk * kTN + (tid & 63)];
   }
   if (ntiles == 0) return;
+  if constexpr (ACT != 0) {
+    // visible to every thread before the first epilogue (the prologue's barrier follows it)
+    if (tid < kTN) {
+      const int c = nblk * kTN + tid;
+      const float sc = act.gamma[c] / sqrtf(act.var[c] + act.eps);
+      bwd_tab[tid] = sc;
+      bwd_tab[kTN + tid] = __builtin_fmaf(-act.mean[c], sc, act.beta[c]);
+    }
+  }
   const int nchunks = g.Cin / kKC;
   const int nst = ntiles * nchunks;
   const int xpieces = g.vrows * WP * 2;  // 16-byte pieces of a chunk's halo image
@@ -452,8 +473,22 @@ __global__ __launch_bounds__(kCvThreads) void conv3x3_kernel(const uint16_t* __r
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           bf16x4 b;
+          if constexpr (ACT != 0) {
+            // the lane's channels 32 i + 8 q + 4 (lane >> 5) .. + 3: one float4 of each
+            const float* t = bwd_tab + 32 * i + 8 * q + 4 * (lane >> 5);
+            const float4 sc = *reinterpret_cast<const float4*>(t);
+            const float4 sf = *reinterpret_cast<const float4*>(t + kTN);
+            const float scv[4] = {sc.x, sc.y, sc.z, sc.w}, sfv[4] = {sf.x, sf.y, sf.z, sf.w};
 #pragma unroll
-          for (int e = 0; e < 4; ++e) b[e] = (__bf16)acc[i][j][4 * q + e];
+            for (int e = 0; e < 4; ++e) {
+              float a = __builtin_fmaf(acc[i][j][4 * q + e], scv[e], sfv[e]);
+              if constexpr (ACT == 2) a = a > 0.f ? a : 0.f;
+              b[e] = (__bf16)a;
+            }
+          } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) b[e] = (__bf16)acc[i][j][4 * q + e];
+          }
           if constexpr (ST) {
             if (ok) {
 #pragma unroll
@@ -676,13 +711,14 @@ struct C3Pre {
   const float* ss;
   int64_t* nbt;
   const uint16_t* xb;  // BWD: the preceding BatchNorm's input
+  Conv3x3BnAct act;    // ACT: the eval-mode BatchNorm behind the forward
 };
 
-template <int NX, bool FLIP, int JB, int DEPTH, int WC, int CC, bool ST, bool PRE, bool BWD = false>
+template <int NX, bool FLIP, int JB, int DEPTH, int WC, int CC, bool ST, bool PRE, bool BWD = false, int ACT = 0>
 static void launch_one(const uint16_t* x, const uint16_t* w, uint16_t* y, const Conv3x3Geom& g, hipStream_t st,
                        dim3 grid, float* part, const C3Pre& pre) {
-  hipLaunchKernelGGL((conv3x3_kernel<NX, FLIP, JB, DEPTH, WC, CC, ST, PRE, BWD>), grid, dim3(kCvThreads), 0, st, x,
-                     w, y, g, part, pre.ss, pre.nbt, pre.xb);
+  hipLaunchKernelGGL((conv3x3_kernel<NX, FLIP, JB, DEPTH, WC, CC, ST, PRE, BWD, ACT>), grid, dim3(kCvThreads), 0, st,
+                     x, w, y, g, part, pre.ss, pre.nbt, pre.xb, pre.act);
 }
 
 // The compile-time-shape instances (tile size, NX, WC, CC): ResNet-50's stride-1 3x3
@@ -709,35 +745,36 @@ Conv3x3Instance conv3x3_instance(const Conv3x3Geom& g, bool pre) {
   return Conv3x3Instance{pieces <= 4 ? 4 : (pieces >= kMaxNX ? kMaxNX : pieces), false};
 }
 
-template <bool FLIP, int JB, int DEPTH, bool ST, bool PRE>
+// ACT: the plain forward's instance choice, pipeline depth and work split (conv3x3_instance(g, false))
+template <bool FLIP, int JB, int DEPTH, bool ST, bool PRE, int ACT = 0>
 static void launch_nx(const uint16_t* x, const uint16_t* w, uint16_t* y, const Conv3x3Geom& g, hipStream_t st,
                       dim3 grid, float* part, const C3Pre& pre) {
   const Conv3x3Instance ins = conv3x3_instance(g, PRE);
   if constexpr (!PRE) {
     if (ins.fixed) {  // (g.tm, g.W) names the kC3Fixed row conv3x3_instance matched
       if constexpr (JB == 4) {
-        if (g.W == 56) launch_one<7, FLIP, JB, DEPTH, 56, 64, ST, PRE>(x, w, y, g, st, grid, part, pre);
-        else launch_one<5, FLIP, JB, DEPTH, 28, 128, ST, PRE>(x, w, y, g, st, grid, part, pre);
+        if (g.W == 56) launch_one<7, FLIP, JB, DEPTH, 56, 64, ST, PRE, false, ACT>(x, w, y, g, st, grid, part, pre);
+        else launch_one<5, FLIP, JB, DEPTH, 28, 128, ST, PRE, false, ACT>(x, w, y, g, st, grid, part, pre);
       } else {
-        if (g.W == 28) launch_one<4, FLIP, JB, DEPTH, 28, 128, ST, PRE>(x, w, y, g, st, grid, part, pre);
-        else if (g.W == 14) launch_one<4, FLIP, JB, DEPTH, 14, 256, ST, PRE>(x, w, y, g, st, grid, part, pre);
-        else launch_one<4, FLIP, JB, DEPTH, 7, 512, ST, PRE>(x, w, y, g, st, grid, part, pre);
+        if (g.W == 28) launch_one<4, FLIP, JB, DEPTH, 28, 128, ST, PRE, false, ACT>(x, w, y, g, st, grid, part, pre);
+        else if (g.W == 14) launch_one<4, FLIP, JB, DEPTH, 14, 256, ST, PRE, false, ACT>(x, w, y, g, st, grid, part, pre);
+        else launch_one<4, FLIP, JB, DEPTH, 7, 512, ST, PRE, false, ACT>(x, w, y, g, st, grid, part, pre);
       }
       return;
     }
   }
   switch (ins.nx) {
     case 4:
-      launch_one<4, FLIP, JB, DEPTH, 0, 0, ST, PRE>(x, w, y, g, st, grid, part, pre);
+      launch_one<4, FLIP, JB, DEPTH, 0, 0, ST, PRE, false, ACT>(x, w, y, g, st, grid, part, pre);
       break;
     case 5:
-      launch_one<5, FLIP, JB, DEPTH, 0, 0, ST, PRE>(x, w, y, g, st, grid, part, pre);
+      launch_one<5, FLIP, JB, DEPTH, 0, 0, ST, PRE, false, ACT>(x, w, y, g, st, grid, part, pre);
       break;
     case 6:
-      launch_one<6, FLIP, JB, DEPTH, 0, 0, ST, PRE>(x, w, y, g, st, grid, part, pre);
+      launch_one<6, FLIP, JB, DEPTH, 0, 0, ST, PRE, false, ACT>(x, w, y, g, st, grid, part, pre);
       break;
     default:
-      launch_one<7, FLIP, JB, DEPTH, 0, 0, ST, PRE>(x, w, y, g, st, grid, part, pre);
+      launch_one<7, FLIP, JB, DEPTH, 0, 0, ST, PRE, false, ACT>(x, w, y, g, st, grid, part, pre);
       break;
   }
 }
@@ -785,12 +822,28 @@ bool conv3x3_pre_ok(const Conv3x3Geom& g) { return conv3x3_ok(g) && g.Cin <= kPr
 bool conv3x3_bwd_ok(const Conv3x3Geom& g) { return conv3x3_ok(g) && g.Cout <= kPreMaxC; }
 
 bool launch_conv3x3(const uint16_t* x, const uint16_t* w, uint16_t* y, const Conv3x3Geom& g, bool flip,
-                    hipStream_t st, float* part, const float* pre_ss, int64_t* nbt_inc, const uint16_t* bwd_x) {
+                    hipStream_t st, float* part, const float* pre_ss, int64_t* nbt_inc, const uint16_t* bwd_x,
+                    const Conv3x3BnAct* act) {
+  if (act) {
+    // eval-mode BatchNorm (+ ReLU) epilogue: the plain forward only, with all four vectors
+    if (flip || part || pre_ss || bwd_x || !act->mean || !act->var || !act->gamma || !act->beta || !conv3x3_ok(g))
+      return false;
+    const dim3 grid((unsigned)(g.wpb * (g.Cout / kTN)));
+    const C3Pre pre{nullptr, nullptr, nullptr, *act};
+    if (g.tm == 512) {
+      if (act->relu) launch_nx<false, 4, 2, false, false, 2>(x, w, y, g, st, grid, nullptr, pre);
+      else launch_nx<false, 4, 2, false, false, 1>(x, w, y, g, st, grid, nullptr, pre);
+    } else {
+      if (act->relu) launch_nx<false, 2, 4, false, false, 2>(x, w, y, g, st, grid, nullptr, pre);
+      else launch_nx<false, 2, 4, false, false, 1>(x, w, y, g, st, grid, nullptr, pre);
+    }
+    return true;
+  }
   if (bwd_x) {
     // BatchNorm-backward epilogue: the input gradient only, with both the statistics and the sums' row buffer
     if (!flip || !part || !pre_ss || !conv3x3_bwd_ok(g)) return false;
     const dim3 grid((unsigned)(g.wpb * (g.Cout / kTN)));
-    const C3Pre pre{pre_ss, nullptr, bwd_x};
+    const C3Pre pre{pre_ss, nullptr, bwd_x, Conv3x3BnAct{}};
     if (g.tm == 512) launch_bwd<4, 2, 1>(x, w, y, g, st, grid, part, pre);
     else launch_bwd<2, 4, 4>(x, w, y, g, st, grid, part, pre);
     return true;
@@ -799,7 +852,7 @@ bool launch_conv3x3(const uint16_t* x, const uint16_t* w, uint16_t* y, const Con
     return false;
   // persistent: one workgroup per (pixel range, output-channel block) -- one per CU
   const dim3 grid((unsigned)(g.wpb * (g.Cout / kTN)));
-  const C3Pre pre{pre_ss, nbt_inc, nullptr};
+  const C3Pre pre{pre_ss, nbt_inc, nullptr, Conv3x3BnAct{}};
   // 512-pixel tiles: twice the accumulators, so two register stages in flight.  A
   // deferred BatchNorm (pre_ss) comes with the statistics epilogue only (the ResNet path)
   if (g.tm == 512) {

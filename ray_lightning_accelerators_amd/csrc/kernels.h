@@ -653,11 +653,21 @@ Conv3x3Instance conv3x3_instance(const Conv3x3Geom& g, bool pre);
 // backward in the epilogue -- bwd_x [N, H, W, Cout] is that BatchNorm's input, pre_ss its
 // [4, Cout] statistics; y is d = fma(bwd_x, scale, shift) > 0 ? dx : 0 and part
 // [g.wpb][2][Cout] the sums of d and d * bwd_x over each range (bn_partial's backward layout)
+// act (plain forward only: no flip, part, pre_ss or bwd_x): an eval-mode BatchNorm and an optional
+// ReLU in the epilogue -- y = bf16(act(fma(acc, scale, shift))), scale = gamma / sqrt(var + eps),
+// shift = fma(-mean, scale, beta), computed in the kernel from the four fp32 [Cout] vectors; the
+// conv output is never written.  Instance, pipeline depth and work split are the plain forward's.
+struct Conv3x3BnAct {
+  const float *mean, *var, *gamma, *beta;
+  float eps;
+  int relu;
+};
 bool conv3x3_pre_ok(const Conv3x3Geom& g);
 bool conv3x3_bwd_ok(const Conv3x3Geom& g);
 bool launch_conv3x3(const uint16_t* x, const uint16_t* w, uint16_t* y, const Conv3x3Geom& g, bool flip,
                     hipStream_t stream, float* part = nullptr, const float* pre_ss = nullptr,
-                    int64_t* nbt_inc = nullptr, const uint16_t* bwd_x = nullptr);
+                    int64_t* nbt_inc = nullptr, const uint16_t* bwd_x = nullptr,
+                    const Conv3x3BnAct* act = nullptr);
 
 // 3x3 / stride 2 / pad 1 NHWC bf16 convolution forward on MFMA (csrc/conv3x3s2.hip):
 // y [N, OH, OW, Cout] = conv(x [N, H, W, Cin], w [Cout][3][3][Cin]), OH = (H - 1) / 2 + 1,

@@ -25,7 +25,8 @@ from torch.utils.data import Dataset
 
 from ..lightning import LightningModule
 from ..ops.bn import BatchNormAct2d
-from ..ops.conv import BNStats, Conv1x1NHWC, GradFork, conv1x1_bn_eval, conv1x1_bn_eval_ok
+from ..ops.conv import (BNStats, Conv1x1NHWC, GradFork, conv1x1_bn_eval, conv1x1_bn_eval_ok, conv3x3_bn_eval,
+                        conv3x3_bn_eval_ok, stem_bn_eval)
 from ..ops.pool import MaxPool2dNHWC, global_avg_pool_nhwc
 from ..ops.shadow import ConvBF16
 
@@ -81,13 +82,15 @@ class Bottleneck(nn.Module):
         downsample conv may compute bn's batch statistics in its epilogue (ops.conv.BNStats;
         bn then skips its partial pass over the output).  In eval mode under ``no_grad`` a
         stride-1 1x1 conv may run bn, the ReLU and the shortcut add in its own epilogue
-        (ops.conv.conv1x1_bn_eval)."""
+        (ops.conv.conv1x1_bn_eval), a stride-1 3x3 conv bn and the ReLU (ops.conv.conv3x3_bn_eval)."""
         fork = kw.pop("fork", None)
         if isinstance(conv, (Conv1x1NHWC, ConvBF16)) and bn.training:
             st = BNStats()
             return bn(conv(x, fork=fork, bn_stats=st), bn_stats=st, **kw)
         if conv1x1_bn_eval_ok(x, conv, bn, kw.get("residual")):
             return conv1x1_bn_eval(x, conv, bn, kw.get("residual"))
+        if conv3x3_bn_eval_ok(x, conv, bn, kw.get("residual"), kw.get("pool")):
+            return conv3x3_bn_eval(x, conv, bn)
         return bn(conv(x, fork=fork) if fork is not None else conv(x), **kw)
 
     def forward(self, x):
@@ -161,8 +164,13 @@ class ResNet(nn.Module):
             st = BNStats()
             x = self.bn1(self.conv1(x, bn_stats=st), bn_stats=st, pool=self.maxpool)
         else:
-            x = self.bn1(self.conv1(x))
-            x = self.maxpool(x if self.fused_bn else F.relu(x, inplace=True))
+            # eval mode under no_grad: the stem kernel, then bn1 + ReLU inside the max pool's
+            # pass on the running statistics (ops.conv.stem_bn_eval), where that route applies
+            y = stem_bn_eval(x, self.conv1, self.bn1, self.maxpool) if self.fused_bn else None
+            if y is None:
+                y = self.bn1(self.conv1(x))
+                y = self.maxpool(y if self.fused_bn else F.relu(y, inplace=True))
+            x = y
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         if self.fused_bn:
             return self.fc(global_avg_pool_nhwc(x))  # NHWC backward kernel (ops/pool.py)

@@ -277,6 +277,15 @@ class _BNActFn(torch.autograd.Function):
         return dx, dgamma, dbeta, dres, None, None, None, None, None, None, None, None, None, None, None, None
 
 
+def eval_scale_shift(bn: nn.BatchNorm2d):
+    """fp32 contiguous (scale, shift) of ``bn`` on its running statistics: the one expression of
+    the eval-mode apply pass and of the routes that fold the map elsewhere (ops.conv.stem_bn_eval)."""
+    invstd = (bn.running_var + bn.eps).rsqrt()
+    scale = invstd * bn.weight if bn.weight is not None else invstd
+    shift = (bn.bias if bn.bias is not None else torch.zeros_like(invstd)) - bn.running_mean * scale
+    return scale.float().contiguous(), shift.float().contiguous()
+
+
 class BatchNormAct2d(nn.BatchNorm2d):
     """``act(BatchNorm2d(x) + residual)`` with ``act`` in {"relu", None}."""
 
@@ -361,11 +370,9 @@ class BatchNormAct2d(nn.BatchNorm2d):
             if not torch.is_grad_enabled() or not (x.requires_grad or (self.weight is not None
                                                                           and self.weight.requires_grad)):
                 stats["fused"] += 1
-                invstd = (self.running_var + self.eps).rsqrt()
-                scale = invstd * self.weight if self.weight is not None else invstd
-                shift = (self.bias if self.bias is not None else torch.zeros_like(invstd)) - self.running_mean * scale
+                scale, shift = eval_scale_shift(self)
                 y = torch.empty_like(x, memory_format=torch.channels_last)
-                require().bn_apply(_nhwc(x), scale.float().contiguous(), shift.float().contiguous(),
+                require().bn_apply(_nhwc(x), scale, shift,
                                    _nhwc(residual) if residual is not None else None, relu, _nhwc(y))
                 return y
         stats["fallback"] += 1

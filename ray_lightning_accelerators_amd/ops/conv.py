@@ -26,7 +26,9 @@ use (like cudnn.benchmark): each operation builds ONE table ``{name: callable}``
 ``RLA_FORK_DGRAD=auto|0|1`` the input gradient of a forked 1x1 pair (``fork_dgrad_mode``:
 one kernel for both GEMMs, or the parked-dgrad route; ``dgrad_fork`` in ``choices()``),
 ``RLA_CONV1X1_BN_EVAL=auto|0|1`` the eval-mode forward of a stride-1 1x1 layer and its
-BatchNorm (``conv1x1_bn_eval``: one kernel, or the conv and the apply pass; ``fwd_bn_eval``).
+BatchNorm (``conv1x1_bn_eval``: one kernel, or the conv and the apply pass; ``fwd_bn_eval``),
+``RLA_CONV3X3_BN_EVAL=auto|0|1`` the same for a stride-1 3x3 layer (``conv3x3_bn_eval``;
+``fwd_kxk_bn_eval``) and the eval-mode stem on the in-tree kernels (``stem_bn_eval``).
 
 Around the convolutions themselves:
 
@@ -55,7 +57,8 @@ from torch import nn
 _choice: Dict[Tuple, str] = {}
 _timings: Dict[Tuple, Dict[str, float]] = {}
 stats = {"fast": 0, "fallback": 0, "bn_dgrad_fused": 0, "bn_dgrad_fused_3x3": 0, "stem": 0, "pre_applied": 0,
-         "bn_dgrad_fused_wide": 0, "fork_dgrad_fused": 0, "bn_eval_fused": 0}
+         "bn_dgrad_fused_wide": 0, "fork_dgrad_fused": 0, "bn_eval_fused": 0, "bn_eval_fused_3x3": 0,
+         "bn_eval_stem": 0}
 
 
 def _mode() -> str:
@@ -1188,6 +1191,118 @@ def conv1x1_bn_eval(x: torch.Tensor, conv: "Conv1x1NHWC", bn: nn.Module,
     return fused()
 
 
+def bn_eval_3x3_mode() -> str:
+    """``RLA_CONV3X3_BN_EVAL``: how an eval-mode BatchNorm after a stride-1 3x3 conv, and the
+    stem's conv + BatchNorm + max pool, run under ``no_grad``.  ``auto``: the 3x3 kernel with the
+    BatchNorm in its epilogue (csrc/conv3x3.hip ACT) or the split route (the library convolution,
+    the coefficient ops and ``bn_apply``), timed per shape; the stem on the in-tree kernels
+    wherever they apply.  ``1``: the fused kernel wherever it applies; ``0``: the split routes,
+    untouched."""
+    m = os.environ.get("RLA_CONV3X3_BN_EVAL", "auto")
+    return m if m in ("0", "1") else "auto"
+
+
+def _bf16_autocast(x: torch.Tensor) -> bool:
+    """A CUDA tensor under bf16 autocast, with the native kernels on (``ops.use_native``)."""
+    from . import use_native
+
+    return (x.is_cuda and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16
+            and use_native(x))
+
+
+def _eval_bn_ok(bn: nn.Module, x: torch.Tensor) -> bool:
+    """An eval-mode ``BatchNormAct2d`` on fp32 contiguous running statistics and affine parameters
+    on ``x``'s device."""
+    from .bn import BatchNormAct2d
+
+    if bn.training or not isinstance(bn, BatchNormAct2d) or not bn.track_running_stats:
+        return False
+    vecs = (bn.running_mean, bn.running_var, bn.weight, bn.bias)
+    return not any(v is None or v.dtype != torch.float32 or v.device != x.device or not v.is_contiguous()
+                   for v in vecs)
+
+
+def conv3x3_bn_act_hip(x: torch.Tensor, wb: torch.Tensor, mean: torch.Tensor, var: torch.Tensor,
+                       gamma: torch.Tensor, beta: torch.Tensor, eps: float, relu: bool) -> torch.Tensor:
+    """``act(bn(conv2d(x, wb, stride=1, padding=1)))`` with the BatchNorm on the given statistics,
+    in one MFMA kernel: ``x`` [N, Cin, H, W] and ``wb`` [Cout, Cin, 3, 3] channels_last bf16, the
+    four vectors fp32 [Cout].  The conv output is neither written nor rounded; scale and shift
+    are computed in the kernel.  Returns channels_last bf16."""
+    from . import require
+
+    n, cin, h, w = x.shape
+    cout = wb.size(0)
+    y = require().conv3x3_bn_act(x.permute(0, 2, 3, 1), wb.permute(0, 2, 3, 1), n, h, w, cin, cout, mean, var, gamma,
+                                 beta, float(eps), relu)
+    return y.permute(0, 3, 1, 2)
+
+
+def conv3x3_bn_eval_ok(x: torch.Tensor, conv: nn.Module, bn: nn.Module, residual: Optional[torch.Tensor] = None,
+                       pool: Optional[nn.Module] = None) -> bool:
+    """Whether ``bn(conv(x))`` may run as :func:`conv3x3_bn_eval`: autograd off, an eval-mode
+    ``BatchNormAct2d`` (:func:`_eval_bn_ok`), a ``ConvBF16`` that is 3x3 / stride 1 / pad 1
+    without dilation, groups or bias, a bf16 channels_last CUDA input under bf16 autocast, no
+    residual, pool or deferred BatchNorm, no hooks on either module (the fused route calls
+    neither ``forward``), ``RLA_CONV3X3`` not ``off`` and the switch not at ``0``."""
+    if torch.is_grad_enabled() or bn.training or bn_eval_3x3_mode() == "0":
+        return False  # the training step and the switched-off route leave here
+    from .shadow import ConvBF16
+
+    if not isinstance(conv, ConvBF16) or residual is not None or pool is not None:
+        return False
+    if not (conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
+            and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None and conv.padding_mode == "zeros"):
+        return False
+    if not (x.dim() == 4 and x.dtype == torch.bfloat16 and x.numel() > 0 and _bf16_autocast(x)
+            and x.size(1) == conv.in_channels and x.is_contiguous(memory_format=torch.channels_last)
+            and x.data_ptr() % 16 == 0 and getattr(x, "_rla_pre", None) is None):
+        return False
+    if not _eval_bn_ok(bn, x) or _hooked(conv, bn) or os.environ.get("RLA_CONV3X3", "auto") == "off":
+        return False
+    from . import require
+
+    # not cached: the answer follows the plan CU count and RLA_CONV3X3_TM (see _conv3x3s2_shape_ok)
+    return bool(require().conv3x3_bn_act_ok(x.size(0), x.size(2), x.size(3), x.size(1), conv.out_channels))
+
+
+def conv3x3_bn_eval(x: torch.Tensor, conv: nn.Conv2d, bn: nn.Module) -> torch.Tensor:
+    """``bn(conv(x))`` for a stride-1 3x3 conv and an eval-mode BatchNorm under ``no_grad``; the
+    caller checked :func:`conv3x3_bn_eval_ok`.  ``fused`` is the one-kernel route, ``split`` the
+    modules' own forwards; ``RLA_CONV3X3_BN_EVAL=1`` and deterministic mode take ``fused``
+    untimed, ``auto`` the faster of the two per (N, H, W, Cin, Cout, relu) -- ``fwd_kxk_bn_eval``
+    in :func:`choices` -- and a stream capture without a cached pick takes ``split``."""
+    from . import bn as _bn
+    from .shadow import bf16_weight
+
+    relu = bn.act == "relu"
+
+    def split():
+        return bn(conv(x))
+
+    def fused():
+        shadow = bf16_weight(conv.weight)
+        # the arena's bf16 shadow when there is one, as ConvBF16 reads it
+        wb = shadow if shadow is not None else conv.weight.detach().to(torch.bfloat16)
+        return conv3x3_bn_act_hip(x, wb.contiguous(memory_format=torch.channels_last), bn.running_mean,
+                                  bn.running_var, bn.weight.detach(), bn.bias.detach(), bn.eps, relu)
+
+    if bn_eval_3x3_mode() != "1" and not torch.are_deterministic_algorithms_enabled():
+        k = ("fwd_kxk_bn_eval", x.size(0), x.size(2), x.size(3), x.size(1), conv.out_channels, int(relu))
+        if _choice.get(k) is None:
+            if torch.cuda.is_current_stream_capturing():
+                return split()
+            keep = dict(stats), dict(_bn.stats)  # the timing calls are not the model's
+            try:
+                _timed_pick(k, {"fused": fused, "split": split})
+            finally:
+                stats.update(keep[0])
+                _bn.stats.update(keep[1])
+        if _choice[k] == "split":
+            return split()
+    stats["bn_eval_fused_3x3"] += 1
+    return fused()
+
+
 class _ConvNHWCFn(torch.autograd.Function):
     """KxK (or strided) bf16 NHWC convolution: MIOpen or, for 3x3 / stride 1 / pad 1, the
     MFMA kernels for the forward and dgrad, for 3x3 / stride 2 / pad 1 the MFMA forward
@@ -1375,6 +1490,39 @@ def stem_hip(x: torch.Tensor, wb: torch.Tensor, stats: bool = False):
     out = require().stem_fwd(xn, wb.permute(0, 2, 3, 1).contiguous(), stats)
     y = out[0].permute(0, 3, 1, 2)
     return (y, out[1]) if stats else y
+
+
+def stem_bn_eval(x: torch.Tensor, conv: nn.Module, bn: nn.Module, pool: nn.Module) -> Optional[torch.Tensor]:
+    """``pool(bn(conv(x)))`` for the ResNet stem in eval mode under ``no_grad`` on the in-tree
+    kernels: the MFMA stem forward, then the max pool with the BatchNorm + ReLU folded into its
+    window reads (csrc/pool.hip), on the scale and shift ``BatchNormAct2d``'s eval branch
+    computes -- bitwise ``maxpool(bn_apply(stem_hip(x)))``, without the normalised activation's
+    write and re-read.  None where the route does not apply: autograd on, a training or foreign
+    BatchNorm, a pool the fold does not cover, hooks, no bf16 autocast, ``RLA_STEM=off``,
+    ``RLA_CONV3X3_BN_EVAL=0`` or a shape outside :func:`stem_fast_ok`."""
+    if torch.is_grad_enabled() or bn.training or bn_eval_3x3_mode() == "0":
+        return None
+    from .shadow import ConvBF16, bf16_weight
+
+    if not isinstance(conv, ConvBF16) or not (x.dim() == 4 and x.size(1) == 3 and _bf16_autocast(x)):
+        return None
+    if not _eval_bn_ok(bn, x) or _hooked(conv, bn, pool) or os.environ.get("RLA_STEM", "auto") == "off":
+        return None
+    geo = bn._pool_geometry(pool, None)
+    xb = x.to(torch.bfloat16)
+    if geo is None or not stem_fast_ok(xb, conv):
+        return None
+    from . import require
+    from .bn import eval_scale_shift
+
+    shadow = bf16_weight(conv.weight)
+    y = stem_hip(xb, shadow if shadow is not None else conv.weight.detach().to(torch.bfloat16))
+    scale, shift = eval_scale_shift(bn)
+    zero = torch.zeros_like(scale)
+    k, s, pad = geo
+    yp = require().maxpool_fwd(y.permute(0, 2, 3, 1), k, s, pad, torch.stack((zero, zero, scale, shift)), None)[0]
+    stats["bn_eval_stem"] += 1
+    return yp.permute(0, 3, 1, 2)
 
 
 def stem_wgrad_hip(x: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
